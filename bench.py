@@ -8,6 +8,10 @@ Inputs are resident in HBM before the timed region.  Prints ONE JSON line on ran
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2]      (N > 1 without a launcher: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own: the per-launch
+HIP-event pass behind the roofline lines and the CPU baseline of the oracle.  --dump-outputs DIR writes what the last timed step
+computed (loss, class scores, mask predictions, parameter gradients; predict: the seg logits) as DIR/<name>.npy in float32.
 """
 import argparse
 import json
@@ -22,6 +26,7 @@ if ROOT not in sys.path:
 DTYPE = "f32 (fp32-equivalent: bf16 hi+mid+lo split operands on bf16 MFMA, fp32 accumulate; spike maps stored as bf16, exact)"
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # same guide: dense bf16 MFMA peak (no sparsity)
+DUMP_BUDGET_ELEMS = 15_000_000   # --dump-outputs: at most 60 MB of float32 in all
 
 
 def parse():
@@ -53,9 +58,15 @@ def parse():
                          "all-reduce) + clip_grad_norm_(0.01) + AdamW with the config's per-parameter multipliers, as three HIP "
                          "launches over the flat gradient buffer (train.FlatAdamW), captured behind the step when N = 1.  The "
                          "headline metric excludes the optimiser (BASELINE.md section 3); this line includes it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip the per-launch HIP-event pass on the LIF kernels")
-    ap.add_argument("--dump-events", default=None, help="write (kernel, algorithmic bytes, us) of every timed launch here")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-launch HIP-event pass (roofline lines, --dump-events) and the "
+                         "CPU baseline (cpu_baseline, gpu_over_cpu); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; an array over its share of the "
+                         "60 MB budget is written as <name>_sample.npy, a fixed seeded sample of its elements)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip the per-launch HIP-event pass on the LIF kernels")
+    ap.add_argument("--dump-events", default=None, help="--full: write (kernel, algorithmic bytes, us) of every timed launch here")
     ap.add_argument("--wgrad-stream", action="store_true",
                     help="launch the sunk weight-gradient kernels on a side stream (measured: 69.4 vs 67.2 ms/step -- slower)")
     ap.add_argument("--branch-streams", type=int, default=0,
@@ -77,7 +88,26 @@ def parse():
     ap.add_argument("--allow-eager", action="store_true",
                     help="N > 1: fall back to eager launches when the hipGraph capture fails (host-bound, ~2x slower: a curve "
                          "that mixes graph and eager points is meaningless, so the default is to fail)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_events = True
+    return args
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor as DIR/<name>.npy in float32.  The budget is shared equally; a tensor larger than its share
+    is written flattened as <name>_sample.npy: its elements at sorted indices drawn by numpy's default_rng(0), so the same
+    arguments select the same elements in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_ELEMS // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=share))
+            t, name = t.reshape(-1)[torch.from_numpy(idx).to(t.device)], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline(workload, timed_steps=3):
@@ -151,6 +181,8 @@ def predict_bench(args, s2f, ops, dev, w, B, rank, world):
         graph.replay()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
     if rank == 0:
         print(json.dumps({
             "metric": f"predict images/sec ({args.workload}: eval mode, whole-image inference to seg logits) [secondary]",
@@ -246,6 +278,13 @@ def main():
     graphed_model = None
     want_split_graphs = False
     hungarian = None
+    held = {}               # the headline step's outputs, for --dump-outputs: a captured step's are its graph's static tensors
+
+    def headline_loss(cls, masks):
+        # detached: a reference to the outputs themselves would keep the step's autograd graph alive into the next step
+        held["cls"], held["masks"] = cls.detach(), masks.detach()
+        return s2f.headline_loss(cls, masks)
+
     if args.loss == "hungarian":
         args.no_cpu_baseline = args.no_kernel_events = True
         gen = torch.Generator().manual_seed(1 + rank)
@@ -288,8 +327,9 @@ def main():
         if seg is not None:
             sum(model(img, [seg[i] for i in range(B)], mode="loss").values()).backward()
         else:
-            cls, masks = model(img)
-            s2f.headline_loss(cls, masks).backward()
+            loss = headline_loss(*model(img))
+            loss.backward()
+            held["loss"] = loss.detach()
         ops.wgrad_join()
         red.gather()
         red.reduce()
@@ -337,7 +377,7 @@ def main():
         # reset + grad clear + forward + loss + backward captured once as a hipGraph; the RCCL all-reduce stays eager
         from spike2former_amd.graph import GraphedStep
         try:
-            graphed = GraphedStep(model, s2f.headline_loss, img, grad_buffer=red, warmup=max(args.warmup, 2),
+            graphed = GraphedStep(model, headline_loss, img, grad_buffer=red, warmup=max(args.warmup, 2),
                                   optimizer=optim if world == 1 else None)
         except RuntimeError as e:                   # N > 1 with --allow-eager only: eager launches, labelled as such
             if world == 1 or not args.allow_eager:
@@ -378,6 +418,17 @@ def main():
         overlapped.finish()               # the last step's all-reduce belongs to the timed region
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: the loss and the model's outputs (headline loss only) and every parameter's
+        # gradient, averaged over the ranks, in model.parameters() order (the flat buffer's own order depends on compact())
+        got = dict(held)
+        if graphed is not None:
+            got["loss"] = graphed.static_loss
+        elif overlapped is not None:            # captured with s2f.headline_loss: its outputs are not kept
+            got = {"loss": overlapped.loss}
+        slot = dict(zip(map(id, red.params), red.views))
+        got["grads"] = torch.cat([slot[id(p)].reshape(-1) for p in model.parameters() if id(p) in slot])
+        dump_outputs(args.dump_outputs, got)
     # Per-launch durations of the neuron kernels: HIP events cannot be read back from inside a replayed hipGraph, so the
     # same kernels on the same tensors are timed in eager steps right after the timed region (events on the launch stream).
     events = None

@@ -221,3 +221,31 @@ def test_spike_map_handles_for_a_second_reader():
     plain = ops.Spikes(data, tok)
     assert plain.second() is plain and plain.flatten(0, 1).tok2 is None
     assert ops.Spikes(data).second().tok is None
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path, monkeypatch):
+    """bench.py: the secondary measurements run only under --full; --dump-outputs writes float32 files of at most 64 MB in all,
+    and a large output's sample is the same elements in every run."""
+    import os
+    import sys
+
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert a.steps == 7 and not a.full and a.no_cpu_baseline and a.no_kernel_events
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not a.no_cpu_baseline and not a.no_kernel_events
+    big = torch.randn(40_000_000, generator=torch.Generator().manual_seed(0))
+    outs = {"loss": torch.tensor(0.25), "cls": torch.ones(2, 3, dtype=torch.bfloat16), "grads": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["cls.npy", "grads_sample.npy", "loss.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64e6
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert np.load(tmp_path / "a" / "cls.npy").shape == (2, 3)
+    s = np.load(tmp_path / "a" / "grads_sample.npy")
+    assert np.isin(s, big.numpy()).all()
