@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 32
+#define S2F_ABI_VERSION 33
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -486,6 +486,38 @@ int s2f_upsample2x_bwd(const float* gy, float* gx, int64_t planes, int h, int w,
  * AND the transformer decoder (pixel_decoder.py:437-449, 466-471); the gradient the second reader sends back is summed here instead
  * of by an add launch of the autograd engine. */
 int s2f_upsample2x_bwd_add(const float* gy, const float* add, float* gx, int64_t planes, int h, int w, void* stream);
+
+/* ---- general bilinear resizing and the inference post-processing (csrc/resize.hip) ----------------------------------------------
+ * F.interpolate(x, size=(H, W), mode='bilinear', align_corners=...) of [planes, h, w] fp32 maps for any sizes (enlarging or
+ * shrinking, 1-pixel maps included), with ATen's arithmetic for an explicit size; the predict path at image sizes that are not
+ * multiples of 32 (the exact-2x even-width case stays on s2f_upsample2x_*).  Source window: plane p's logical pixel (r, c) is
+ * x[p * plane_stride + (row0 + r) * row_stride + col0 + c] (the padding crop of postprocess_result, mmseg segmentors/base.py:
+ * 160-175, without a copy), after the flips the flags ask for; y is a contiguous [planes, H, W].
+ * flags: S2F_RESIZE_ALIGN_CORNERS | S2F_RESIZE_SIGMOID (y = sigmoid(resize), the head's predict) | S2F_RESIZE_FLIP_H / _V (the
+ * window is flipped before resizing: a flipped test-time view undone). */
+#define S2F_RESIZE_ALIGN_CORNERS 1
+#define S2F_RESIZE_SIGMOID 2
+#define S2F_RESIZE_FLIP_H 4
+#define S2F_RESIZE_FLIP_V 8
+int s2f_resize_fwd(const float* x, float* y, int64_t planes, int64_t plane_stride, int row_stride, int row0, int col0, int h, int w,
+                   int H, int W, int flags, void* stream);
+/* gx [planes, h, w] = adjoint of the (window-free, flip-free) resize applied to gy [planes, H, W], + add (add? NULL = absent: the
+ * gradient of a second reader of the input, as s2f_upsample2x_bwd_add).  A gather with a fixed summation order: bit-repeatable.
+ * flags: S2F_RESIZE_ALIGN_CORNERS only. */
+int s2f_resize_bwd_add(const float* gy, const float* add, float* gx, int64_t planes, int h, int w, int H, int W, int flags,
+                       void* stream);
+/* Per pixel of x [K, HW]: K > 1 -> label = argmax over K (int64; torch.argmax: the first maximum, NaN wins);
+ * K == 1 -> (sigmoid ? sigmoid(x) : x) > threshold, into label (int64) or label_f (float 0 / 1): exactly one of the two.
+ * (EncoderDecoder.postprocess_result's arg-max / threshold, mmseg segmentors/base.py:190-198.) */
+int s2f_seg_argmax(const float* x, int64_t* label, float* label_f, int K, int64_t HW, int sigmoid, float threshold, void* stream);
+/* Test-time augmentation (mmseg segmentors/seg_tta.py:14-48) for one image and one view: the view's logits x [K] x (window, flags as
+ * s2f_resize_fwd) are resized to the accumulator's [H, W] and acc [K, H, W] (first ? = : +=) softmax over K (max-subtracted, expf,
+ * divided by the sum); K == 1: sigmoid, after a first sigmoid if flags has S2F_RESIZE_SIGMOID (the reference's one-class merge
+ * applies sigmoid to already-sigmoid seg_logits). */
+int s2f_tta_accumulate(const float* x, float* acc, int K, int64_t plane_stride, int row_stride, int row0, int col0, int h, int w,
+                       int H, int W, int flags, int first, void* stream);
+/* acc [K, HW] /= n_views in place, then the arg-max / threshold of s2f_seg_argmax (no sigmoid) into label or label_f. */
+int s2f_tta_finish(float* acc, int64_t* label, float* label_f, int K, int64_t HW, int n_views, float threshold, void* stream);
 
 /* ---- batched transposition of the last two dimensions: x [B, R, C] -> y [B, C, R] (fp32) -----------------------------------
  * Replaces the `.permute(0, 1, 3, 4, 2)` / `.permute(0, 1, 4, 2, 3)` copies around the DCNv3 sampling core

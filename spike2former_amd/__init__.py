@@ -16,6 +16,7 @@ from .pixel_decoder import DCNTransformerEncoderPixelDecoder  # noqa: F401
 from .registry import HOOKS, MODELS, ConfigDict, register_upstream  # noqa: F401
 from . import reparam  # noqa: F401
 from .segmentor import EncoderDecoder, ResetModelHook, headline_loss  # noqa: F401
+from .tta import SegTTAModel  # noqa: F401
 from .train import LinearThenPoly, OptimWrapper, parse_losses, train_step  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,4 +1,4 @@
-"""Tiled transposes, exact-2x bilinear up-sampling, the mask-loss kernels of the Hungarian-matched loss."""
+"""Tiled transposes, exact-2x and general bilinear resizing, the mask-loss kernels of the Hungarian-matched loss."""
 import torch
 
 from .config import cfg
@@ -239,18 +239,91 @@ class _Up2x(torch.autograd.Function):
         return gx, None
 
 
+class _Resize(torch.autograd.Function):
+    """F.interpolate(x, size, mode='bilinear') for any sizes on s2f_resize_fwd; backward: the gather adjoint s2f_resize_bwd_add
+    (no atomics: bit-repeatable).  -> (y, pass-through of x or an empty stand-in), the pass-through as in _Up2x: the gradient of a
+    second reader of x is summed inside the adjoint kernel."""
+
+    @staticmethod
+    def forward(ctx, x, size, align_corners, skip):
+        _need_cuda(x)
+        x_in = x
+        x = x.contiguous()
+        N, C, h, w = x.shape
+        H, W = size
+        y = torch.empty(N, C, H, W, dtype=torch.float32, device=x.device)
+        flags = lib_flags(align_corners)
+        check(lib.s2f_resize_fwd(_ptr(x), _ptr(y), N * C, h * w, w, 0, 0, h, w, H, W, flags, _stream()), "s2f_resize_fwd")
+        ctx.meta = (N, C, h, w, H, W, flags)
+        ctx.set_materialize_grads(False)
+        if skip:
+            return y, x_in
+        aux = x.new_empty(0)
+        ctx.mark_non_differentiable(aux)
+        return y, aux
+
+    @staticmethod
+    def backward(ctx, gy, gskip):
+        N, C, h, w, H, W, flags = ctx.meta
+        if gy is None:
+            return gskip, None, None, None
+        gy = gy.contiguous()
+        if gskip is not None:
+            gskip = gskip.contiguous()
+        gx = torch.empty(N, C, h, w, dtype=torch.float32, device=gy.device)
+        check(lib.s2f_resize_bwd_add(_ptr(gy), _ptr(gskip), _ptr(gx), N * C, h, w, H, W, flags, _stream()), "s2f_resize_bwd_add")
+        return gx, None, None, None
+
+
+RESIZE_ALIGN_CORNERS, RESIZE_SIGMOID, RESIZE_FLIP_H, RESIZE_FLIP_V = 1, 2, 4, 8       # include/s2f.h S2F_RESIZE_*
+
+
+def lib_flags(align_corners=False, sigmoid=False, flip=None):
+    """the S2F_RESIZE_* flags word; flip: None | 'horizontal' | 'vertical'"""
+    return ((RESIZE_ALIGN_CORNERS if align_corners else 0) | (RESIZE_SIGMOID if sigmoid else 0)
+            | (RESIZE_FLIP_H if flip == "horizontal" else 0) | (RESIZE_FLIP_V if flip == "vertical" else 0))
+
+
+def _general_ok(x):
+    return cfg.GENERAL_RESIZE and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0
+
+
+def resize_bilinear(x, size, align_corners=False, sigmoid=False, skip=False):
+    """F.interpolate(x [N, C, h, w], size, mode='bilinear', align_corners) (.sigmoid() after it with `sigmoid`) on the general
+    kernel s2f_resize_fwd, any sizes; differentiable (s2f_resize_bwd_add) unless `sigmoid`, which is for inference only.
+    `skip`: -> (y, x') as upsample_bilinear's."""
+    H, W = (int(v) for v in size)
+    if sigmoid:
+        assert not skip and not (torch.is_grad_enabled() and x.requires_grad), "the fused sigmoid has no adjoint"
+        _need_cuda(x)
+        x = x.contiguous()
+        N, C, h, w = x.shape
+        y = torch.empty(N, C, H, W, dtype=torch.float32, device=x.device)
+        check(lib.s2f_resize_fwd(_ptr(x), _ptr(y), N * C, h * w, w, 0, 0, h, w, H, W, lib_flags(align_corners, True), _stream()),
+              "s2f_resize_fwd")
+        return y
+    if skip:
+        if cfg.FANOUT_PORTS:
+            return _Resize.apply(x, (H, W), bool(align_corners), True)
+        return _Resize.apply(x, (H, W), bool(align_corners), False)[0], x
+    return _Resize.apply(x, (H, W), bool(align_corners), False)[0]
+
+
 def upsample_bilinear(x, size, sigmoid=False, skip=False):
-    """F.interpolate(x, size, mode='bilinear', align_corners=False); the exact-2x case runs the HIP kernel.  `sigmoid`: followed by
-    .sigmoid() -- inside the same pass where no gradient is wanted (the inference post-processing).
+    """F.interpolate(x, size, mode='bilinear', align_corners=False); the exact-2x even-width case runs the 2x kernels, every other
+    fp32 CUDA [N, C, h, w] map the general resize (s2f_resize_fwd / s2f_resize_bwd_add).  `sigmoid`: followed by .sigmoid() --
+    inside the same pass where no gradient is wanted (the inference post-processing).
     `skip`: -> (y, x') with x' = x for a second reader of x, whose gradient the adjoint kernel then sums (cfg.FANOUT_PORTS; x' is x
     itself where that does not apply)."""
-    if skip:
-        h, w = x.shape[-2:]
-        if cfg.FANOUT_PORTS and tuple(size) == (2 * h, 2 * w) and w % 2 == 0 and x.dim() == 4 and x.is_cuda and not sigmoid:
-            return _Up2x.apply(x, True)
-        return upsample_bilinear(x, size, sigmoid), x
     h, w = x.shape[-2:]
-    if tuple(size) == (2 * h, 2 * w) and w % 2 == 0:
+    two_x = tuple(size) == (2 * h, 2 * w) and w % 2 == 0
+    if skip:
+        if cfg.FANOUT_PORTS and two_x and x.dim() == 4 and x.is_cuda and not sigmoid:
+            return _Up2x.apply(x, True)
+        if not two_x and not sigmoid and _general_ok(x):
+            return resize_bilinear(x, size, skip=True)
+        return upsample_bilinear(x, size, sigmoid), x
+    if two_x:
         if sigmoid and w % 4 == 0 and x.dim() == 4 and not (torch.is_grad_enabled() and x.requires_grad):
             _need_cuda(x)
             x = x.contiguous()
@@ -260,9 +333,76 @@ def upsample_bilinear(x, size, sigmoid=False, skip=False):
             return y
         y = _Up2x.apply(x, False)[0]
         return y.sigmoid() if sigmoid else y
+    if _general_ok(x):
+        if sigmoid and not (torch.is_grad_enabled() and x.requires_grad):
+            return resize_bilinear(x, size, sigmoid=True)
+        y = resize_bilinear(x, size)
+        return y.sigmoid() if sigmoid else y
     fallback("upsample_bilinear", f"{(h, w)} -> {tuple(size)}")
     y = torch.nn.functional.interpolate(x, size=tuple(size), mode="bilinear", align_corners=False)
     return y.sigmoid() if sigmoid else y
+
+
+# ------------------------------------------------------------------------------------------------ inference post-processing
+def _window(x, crop):
+    """x [K, Hp, Wp] (a plane-contiguous map) and crop = (top, bottom, left, right) -> (plane stride, row stride, row0, col0, h, w)"""
+    Hp, Wp = x.shape[-2:]
+    top, bottom, left, right = (int(v) for v in (crop or (0, 0, 0, 0)))
+    assert x.stride(-1) == 1 and x.stride(-2) == Wp and x.stride(0) == Hp * Wp, "a contiguous [K, H, W] map"
+    return Hp * Wp, Wp, top, left, Hp - top - bottom, Wp - left - right
+
+
+def resize_window(x, size, crop=None, flip=None, align_corners=False, sigmoid=False):
+    """x [K, Hp, Wp] fp32 CUDA -> [K, H, W]: the window x[:, top:Hp-bottom, left:Wp-right] (crop = (top, bottom, left, right)),
+    flipped (None | 'horizontal' | 'vertical'), bilinearly resized to `size` (then sigmoid) -- one s2f_resize_fwd pass, no copy of
+    the window (EncoderDecoder.postprocess_result)."""
+    _need_cuda(x)
+    x = x.contiguous()
+    ps, ld, r0, c0, h, w = _window(x, crop)
+    H, W = (int(v) for v in size)
+    y = torch.empty(x.shape[0], H, W, dtype=torch.float32, device=x.device)
+    check(lib.s2f_resize_fwd(_ptr(x), _ptr(y), x.shape[0], ps, ld, r0, c0, h, w, H, W, lib_flags(align_corners, sigmoid, flip),
+                             _stream()), "s2f_resize_fwd")
+    return y
+
+
+def seg_argmax(x, threshold=0.3, sigmoid=False, float_out=False):
+    """x [K, H, W] fp32 CUDA -> [1, H, W]: K > 1 the int64 arg-max over K (torch.argmax: first maximum, NaN wins); K == 1
+    (sigmoid(x) if `sigmoid` else x) > threshold as int64 or, with float_out, as float 0 / 1 (s2f_seg_argmax)."""
+    _need_cuda(x)
+    x = x.contiguous()
+    K, H, W = x.shape
+    f = float_out and K == 1
+    out = torch.empty(1, H, W, dtype=torch.float32 if f else torch.int64, device=x.device)
+    check(lib.s2f_seg_argmax(_ptr(x), None if f else _ptr(out), _ptr(out) if f else None, K, H * W, int(sigmoid), float(threshold),
+                             _stream()), "s2f_seg_argmax")
+    return out
+
+
+def tta_accumulate(acc, x, first, crop=None, flip=None, align_corners=False, pre_sigmoid=False):
+    """acc [K, H, W] (first ? = : +=) softmax over K of x's window (crop / flip / resize as resize_window) -- K == 1: sigmoid,
+    after a first one with pre_sigmoid (s2f_tta_accumulate; mmseg seg_tta.py:29-34)"""
+    _need_cuda(x, acc)
+    x = x.contiguous()
+    assert acc.is_contiguous() and acc.dtype == torch.float32 and acc.shape[0] == x.shape[0]
+    ps, ld, r0, c0, h, w = _window(x, crop)
+    K, H, W = acc.shape
+    check(lib.s2f_tta_accumulate(_ptr(x), _ptr(acc), K, ps, ld, r0, c0, h, w, H, W, lib_flags(align_corners, pre_sigmoid, flip),
+                                 int(bool(first)), _stream()), "s2f_tta_accumulate")
+    return acc
+
+
+def tta_finish(acc, n_views, threshold=0.3):
+    """acc [K, H, W] /= n_views in place; -> the int64 arg-max [1, H, W] (K > 1) or the float 0 / 1 map acc > threshold (K == 1),
+    as seg_tta.py:35-40 (s2f_tta_finish)"""
+    _need_cuda(acc)
+    assert acc.is_contiguous() and acc.dtype == torch.float32
+    K, H, W = acc.shape
+    out = torch.empty(1, H, W, dtype=torch.float32 if K == 1 else torch.int64, device=acc.device)
+    f = K == 1
+    check(lib.s2f_tta_finish(_ptr(acc), None if f else _ptr(out), _ptr(out) if f else None, K, H * W, int(n_views), float(threshold),
+                             _stream()), "s2f_tta_finish")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ mask losses (row f1)

@@ -75,31 +75,51 @@ class EncoderDecoder(nn.Module):
 
     def postprocess_result(self, seg_logits, data_samples=None):
         """Logits -> per-image results (base.py:127-200): padding removed, flip undone, resized to `ori_shape`
-        (bilinear, the head's align_corners), arg-max (sigmoid threshold for one class)."""
+        (bilinear, the head's align_corners), arg-max (sigmoid threshold for one class).  fp32 CUDA logits: crop + flip + resize
+        (+ the one-class sigmoid) are one s2f_resize_fwd pass and the arg-max / threshold one s2f_seg_argmax pass."""
         batch_size, C, H, W = seg_logits.shape
         only_prediction = data_samples is None
         if only_prediction:
             data_samples = [SegDataSample() for _ in range(batch_size)]
+        ours = seg_logits.is_cuda and seg_logits.dtype == torch.float32
+        if ours:
+            seg_logits = seg_logits.contiguous()
+        threshold = getattr(self.decode_head, "threshold", 0.3)
         for i in range(batch_size):
             if not only_prediction:
                 img_meta = data_samples[i].metainfo
                 padding_size = img_meta["img_padding_size"] if "img_padding_size" in img_meta else img_meta.get("padding_size", [0] * 4)
                 padding_left, padding_right, padding_top, padding_bottom = padding_size
-                i_seg_logits = seg_logits[i:i + 1, :, padding_top:H - padding_bottom, padding_left:W - padding_right]
                 flip = img_meta.get("flip", None)
                 if flip:
                     flip_direction = img_meta.get("flip_direction", None)
                     assert flip_direction in ["horizontal", "vertical"]
+                if ours:
+                    i_seg_logits = ops.resize_window(seg_logits[i], tuple(img_meta["ori_shape"]),
+                                                     crop=(padding_top, padding_bottom, padding_left, padding_right),
+                                                     flip=flip_direction if flip else None, align_corners=self.align_corners,
+                                                     sigmoid=C == 1)
+                    i_seg_pred = ops.seg_argmax(i_seg_logits, threshold, float_out=True)
+                    data_samples[i].seg_logits = PixelData(i_seg_logits)
+                    data_samples[i].pred_sem_seg = PixelData(i_seg_pred)
+                    continue
+                i_seg_logits = seg_logits[i:i + 1, :, padding_top:H - padding_bottom, padding_left:W - padding_right]
+                if flip:
                     i_seg_logits = i_seg_logits.flip(dims=(3,)) if flip_direction == "horizontal" else i_seg_logits.flip(dims=(2,))
                 i_seg_logits = F.interpolate(i_seg_logits, size=tuple(img_meta["ori_shape"]), mode="bilinear",
                                              align_corners=self.align_corners).squeeze(0)
             else:
                 i_seg_logits = seg_logits[i]
-            if C > 1:
+            if ours and C > 1:
+                i_seg_pred = ops.seg_argmax(i_seg_logits)
+            elif ours:
+                i_seg_logits = i_seg_logits.sigmoid()
+                i_seg_pred = ops.seg_argmax(i_seg_logits, threshold, float_out=True)
+            elif C > 1:
                 i_seg_pred = i_seg_logits.argmax(dim=0, keepdim=True)
             else:
                 i_seg_logits = i_seg_logits.sigmoid()
-                i_seg_pred = (i_seg_logits > getattr(self.decode_head, "threshold", 0.3)).to(i_seg_logits)
+                i_seg_pred = (i_seg_logits > threshold).to(i_seg_logits)
             data_samples[i].seg_logits = PixelData(i_seg_logits)
             data_samples[i].pred_sem_seg = PixelData(i_seg_pred)
         return data_samples
@@ -112,6 +132,21 @@ class EncoderDecoder(nn.Module):
             batch_img_metas = [dict(ori_shape=inputs.shape[2:], img_shape=inputs.shape[2:], pad_shape=inputs.shape[2:],
                                     padding_size=[0, 0, 0, 0])] * inputs.shape[0]
         return self.postprocess_result(self.inference(inputs, batch_img_metas), data_samples)
+
+    def preprocess(self, data, training=False):
+        """data_preprocessor(data, training) -> dict(inputs, data_samples).  Without a data_preprocessor the inputs are only
+        stacked (a list of [3, H, W]) and moved to the model's device."""
+        if self.data_preprocessor is not None:
+            return self.data_preprocessor(data, training)
+        if not isinstance(data, dict):
+            data = dict(inputs=data[0], data_samples=data[1] if len(data) > 1 else None)
+        inputs = data["inputs"]
+        inputs = torch.stack(list(inputs)) if isinstance(inputs, (list, tuple)) else inputs
+        return dict(inputs=inputs.to(next(self.parameters()).device).float(), data_samples=data.get("data_samples"))
+
+    def test_step(self, data):
+        """mmengine BaseModel.test_step: data_preprocessor(data, False), then mode='predict' -> list of SegDataSample."""
+        return self(**self.preprocess(data, False), mode="predict")
 
     def forward(self, inputs, data_samples=None, mode="tensor"):
         """mode = 'tensor' | 'loss' | 'predict' as in the reference (base.py:86-124); 'logits' (an addition) stops after
