@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 33
+#define S2F_ABI_VERSION 34
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -691,7 +691,10 @@ int s2f_sum_lead(const float* x, int T, int64_t M, float* out, void* stream);
  * casts, small sums -- to these instead of ATen's kernels, and reports what it could not route).
  *   s2f_ew          out[..] = f(a[..], b?[..]) over an index space of ndim <= 6 dimensions; size / sa / sb / so: extents and ELEMENT strides
  *                   (0 = broadcast), host arrays of ndim entries.  op: 0 copy | 1 a + alpha b | 2 a b | 3 a / b | 4 sigmoid(a) |
- *                   5 (a (1 - b)) b  [sigmoid_backward(grad = a, output = b)] | 6 a alpha + beta | 7 a / alpha | 8 a - alpha b.
+ *                   5 (a (1 - b)) b  [sigmoid_backward(grad = a, output = b)] | 6 a alpha | 7 a alpha + beta | 8 a - alpha b |
+ *                   9 a + beta alpha | 10 beta  [a fill: a is not read and may be null]  (ABI 34: ops 6, 7, 9, 10).  The
+ *                   products of ops 1, 7 and 8 are fused into the add (one rounding), op 9's is rounded first: ATen's add / sub /
+ *                   addcmul with a tensor and with a host scalar as `other`.
  *                   a_bf16: a is bf16 (a dtype cast); flat != 0: every operand contiguous over the same elements (16-byte accesses).
  *   s2f_reduce_sum  out[o] = scale * sum_r a[off(o) + off(r)]: kept index space (nd_o <= 6; may be 0) and reduced index space (1 <= nd_r <= 6),
  *                   the reduced space cut into pieces whose partial sums are stored and added in order (deterministic);

@@ -113,8 +113,9 @@ __global__ __launch_bounds__(kBlock) void sum_lead_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------------------------------
 // Generic strided element-wise and reduction kernels: the residual glue of the step (autograd's gradient accumulation where two
 // consumers meet, scalar multiples, sigmoid, layout copies, dtype casts, small sums) that ops/glue_mode.py routes here instead of
-// ATen.  Index space of up to 6 dimensions, element strides per operand (0 = broadcast).  Same IEEE operations as ATen's kernels for
-// add / mul / div / copy (bit-identical results); sigmoid = 1 / (1 + expf(-x)).
+// ATen.  Index space of up to 6 dimensions, element strides per operand (0 = broadcast).  Every op is written as the expression of
+// ATen's functor (AddFunctor `a + b * alpha`, MulFunctor, DivFunctor, addcmul, sigmoid `1 / (1 + exp(-x))`, sigmoid_backward), so the
+// results are ATen's bit for bit (tests/test_gpu_glue.py); a fill writes its value without reading the target.
 constexpr int kMaxDim = 6;
 struct EwArgs {
   const void* a;
@@ -126,18 +127,28 @@ struct EwArgs {
   float alpha, beta;
 };
 // ops: 0 copy a | 1 a + alpha b | 2 a * b | 3 a / b | 4 sigmoid(a) | 5 (a * (1 - b)) * b  [sigmoid_backward(grad = a, out = b)]
-//      6 a * alpha + beta | 7 a / alpha | 8 a - alpha b
+//      6 a * alpha  [times a host scalar; ATen's division by a CPU scalar is the product with its fp32 reciprocal]
+//      7 a * alpha + beta  [host scalar first: beta + a * alpha] | 8 a - alpha b | 9 a + beta * alpha  [plus a host scalar beta]
+//      10 beta  [a fill: a is never read]
+// ATen's add (ufunc::add, `self + alpha * other`; sub = add with -alpha; addcmul's `a + value * (b * c)`) is one fused multiply-add
+// where `other` is a tensor element (ops 1, 7, 8: explicit fmaf).  Where `other` is a host scalar, ATen's vectorised loop adds the
+// hoisted, rounded product alpha * other and its strided loops fuse it (they differ in the last bit when alpha != 1); op 9 is the
+// rounded product on every layout.  Nothing else may fuse.
+constexpr int kOpFill = 10;
 __device__ __forceinline__ float ew_apply(int op, float a, float b, float alpha, float beta) {
+#pragma clang fp contract(off)
   switch (op) {
     case 0: return a;
-    case 1: return alpha == 1.f ? a + b : a + alpha * b;
+    case 1: return fmaf(alpha, b, a);
     case 2: return a * b;
     case 3: return a / b;
     case 4: return 1.0f / (1.0f + expf(-a));
     case 5: return (a * (1.0f - b)) * b;
-    case 6: return beta == 0.f ? a * alpha : a * alpha + beta;
-    case 7: return a / alpha;
-    default: return a - alpha * b;
+    case 6: return a * alpha;
+    case 7: return fmaf(alpha, a, beta);
+    case 8: return fmaf(-alpha, b, a);
+    case 9: return a + alpha * beta;
+    default: return beta;
   }
 }
 __device__ __forceinline__ float ew_load_a(const void* a, long long i, int bf16) {
@@ -151,12 +162,12 @@ __global__ __launch_bounds__(kBlock) void ew_flat_kernel(EwArgs p) {
   const float4* B = reinterpret_cast<const float4*>(p.b);
   float4* O = reinterpret_cast<float4*>(p.out);
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (long long)gridDim.x * kBlock) {
-    const float4 a = A[i], b = p.b ? B[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 a = p.op == kOpFill ? make_float4(0.f, 0.f, 0.f, 0.f) : A[i], b = p.b ? B[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     O[i] = make_float4(ew_apply(p.op, a.x, b.x, p.alpha, p.beta), ew_apply(p.op, a.y, b.y, p.alpha, p.beta),
                        ew_apply(p.op, a.z, b.z, p.alpha, p.beta), ew_apply(p.op, a.w, b.w, p.alpha, p.beta));
   }
   for (long long i = 4 * n4 + (long long)blockIdx.x * kBlock + threadIdx.x; i < p.n; i += (long long)gridDim.x * kBlock)
-    p.out[i] = ew_apply(p.op, reinterpret_cast<const float*>(p.a)[i], p.b ? p.b[i] : 0.f, p.alpha, p.beta);
+    p.out[i] = ew_apply(p.op, p.op == kOpFill ? 0.f : reinterpret_cast<const float*>(p.a)[i], p.b ? p.b[i] : 0.f, p.alpha, p.beta);
 }
 
 // the same with the innermost dimension walked in 16-byte groups: size[ndim - 1] counts float4s, every operand's innermost stride is 1 (b may be
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void ew_strided4_kernel(EwArgs p) {
         ia += c * p.sa[d] * m, ib += c * p.sb[d] * m, io += c * p.so[d] * m;
       }
     }
-    const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.a) + ia);
+    const float4 a = p.op == kOpFill ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.a) + ia);
     const float4 b = p.b ? *reinterpret_cast<const float4*>(p.b + ib) : make_float4(0.f, 0.f, 0.f, 0.f);
     *reinterpret_cast<float4*>(p.out + io) = make_float4(ew_apply(p.op, a.x, b.x, p.alpha, p.beta), ew_apply(p.op, a.y, b.y, p.alpha, p.beta),
                                                           ew_apply(p.op, a.z, b.z, p.alpha, p.beta), ew_apply(p.op, a.w, b.w, p.alpha, p.beta));
@@ -191,7 +202,7 @@ __global__ __launch_bounds__(kBlock) void ew_strided_kernel(EwArgs p) {
         ia += c * p.sa[d], ib += c * p.sb[d], io += c * p.so[d];
       }
     }
-    p.out[io] = ew_apply(p.op, ew_load_a(p.a, ia, p.a_bf16), p.b ? p.b[ib] : 0.f, p.alpha, p.beta);
+    p.out[io] = ew_apply(p.op, p.op == kOpFill ? 0.f : ew_load_a(p.a, ia, p.a_bf16), p.b ? p.b[ib] : 0.f, p.alpha, p.beta);
   }
 }
 
@@ -343,8 +354,9 @@ extern "C" int s2f_sum_lead(const float* x, int T, int64_t M, float* out, void* 
 
 extern "C" int s2f_ew(int op, const void* a, const float* b, float* out, int ndim, const int64_t* size, const int64_t* sa, const int64_t* sb,
                       const int64_t* so, float alpha, float beta, int a_bf16, int flat, void* stream) {
-  S2F_REQUIRE(a && out && ndim >= 0 && ndim <= kMaxDim && op >= 0 && op <= 8, S2F_EINVAL, "s2f_ew: null pointer, ndim > %d or unknown op", kMaxDim);
-  S2F_REQUIRE(b || (op == 0 || op == 4 || op == 6 || op == 7), S2F_EINVAL, "s2f_ew: op %d needs a second operand", op);
+  S2F_REQUIRE((a || op == kOpFill) && out && ndim >= 0 && ndim <= kMaxDim && op >= 0 && op <= kOpFill, S2F_EINVAL,
+              "s2f_ew: null pointer, ndim > %d or unknown op", kMaxDim);
+  S2F_REQUIRE(b || !(op == 1 || op == 2 || op == 3 || op == 5 || op == 8), S2F_EINVAL, "s2f_ew: op %d needs a second operand", op);
   EwArgs p{};
   p.a = a, p.b = b, p.out = out, p.ndim = ndim, p.op = op, p.a_bf16 = a_bf16, p.alpha = alpha, p.beta = beta;
   long long n = 1;

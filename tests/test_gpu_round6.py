@@ -415,9 +415,12 @@ def test_conv3x3_weight_gradient_in_the_weights_layout(B, M, C, H, W):
         assert (((out - base).double() - w.grad).abs() / scale).max().item() <= 4e-6
 
 
-def test_transpose_pass_through_and_fan_out_are_the_engine_sums():
+@pytest.mark.parametrize("n,silent", [(2, ()), (12, ()), (12, (3, 8)), (16, ()), (17, ()), (33, (3, 8, 13, 18, 23, 28))],
+                         ids=["2", "12", "12-with-silent", "16", "17", "33-with-silent"])
+def test_transpose_pass_through_and_fan_out_are_the_engine_sums(n, silent):
     """ops.transpose_last2(skip=True) and ops.fan_out: the second reader's gradient summed inside the transposition's adjoint, the
-    gradients of n readers summed by one launch in the engine's accumulation order -- ports on == ports off, bit for bit."""
+    gradients of n readers summed by s2f_sum_n in the engine's accumulation order (16 addends per launch, chained beyond that; the
+    `silent` readers send no gradient) -- ports on == ports off, bit for bit."""
     from spike2former_amd import ops
     out = []
     for on in (False, True):
@@ -430,12 +433,13 @@ def test_transpose_pass_through_and_fan_out_are_the_engine_sums():
             y, xs = ops.transpose_last2(x, skip=True)
             ((y * w1).sum() + (xs * w2).sum()).backward()
             p = torch.randn(2, 256, 100, generator=g).cuda().requires_grad_(True)
-            ws = [torch.randn(2, 256, 100, generator=g).cuda() for _ in range(12)]
-            fans = ops.fan_out(p, 12)
-            assert len(fans) == 12 and all(torch.equal(f, p) for f in fans)
+            ws = [torch.randn(2, 256, 100, generator=g).cuda() for _ in range(n)]
+            fans = ops.fan_out(p, n)
+            assert len(fans) == n and all(torch.equal(f, p) for f in fans)
             loss = 0
-            for f, w in zip(fans, ws):          # readers in forward order: the engine accumulates their gradients last reader first
-                loss = loss + (f * w).sum()
+            for i, (f, w) in enumerate(zip(fans, ws)):          # readers in forward order: the engine accumulates their gradients last reader first
+                if i not in silent:
+                    loss = loss + (f * w).sum()
             loss.backward()
             out.append((x.grad.clone(), p.grad.clone()))
         finally:

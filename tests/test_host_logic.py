@@ -249,3 +249,123 @@ def test_bench_plain_run_and_dump_outputs(tmp_path, monkeypatch):
     assert np.load(tmp_path / "a" / "cls.npy").shape == (2, 3)
     s = np.load(tmp_path / "a" / "grads_sample.npy")
     assert np.isin(s, big.numpy()).all()
+
+
+def _walk(shape, strides):
+    """every operand's element offsets over the index space, in row-major index order"""
+    idx = np.indices(shape).reshape(len(shape), -1) if shape else np.zeros((0, 1), dtype=np.int64)
+    return [tuple(np.asarray(st, dtype=np.int64) @ idx) for st in strides]
+
+
+@pytest.mark.parametrize("shape,strides,want_dims", [
+    ((4, 5, 6), [(30, 6, 1), (30, 6, 1)], 1),                                  # contiguous: one dimension
+    ((4, 1, 5, 1, 6), [(30, 30, 6, 6, 1), (30, 7, 6, 1, 1)], 1),                # extent-1 dimensions dropped, whatever their strides
+    ((1, 1, 1), [(1, 1, 1), (5, 2, 9)], 1),                                    # nothing left: one dimension of extent 1
+    ((4, 5, 6), [(30, 6, 1), (1, 4, 20)], 3),                                  # permuted operand: nothing merges
+    ((4, 5, 6), [(30, 6, -1), (30, 6, 1)], 2),                                 # h_flip's inner flip: a negative stride does not merge
+    ((4, 5, 6), [(-30, -6, -1), (30, 6, 1)], 1),                               # every dimension flipped: a reversed walk, one dimension
+    ((4, 5, 6), [(-30, 6, 1), (30, 6, 1)], 2),                                 # outer flip: the inner pair still merges
+    ((4, 5, 6), [(0, 6, 1), (30, 6, 1)], 2),                                   # broadcast outer: it stops a merge with the rest
+    ((4, 5, 6), [(6, 0, 1), (30, 6, 1)], 3),                                   # broadcast middle
+    ((4, 5, 6), [(0, 0, 0), (30, 6, 1)], 1),                                   # 0-dim operand broadcast everywhere
+    ((4, 5, 6), [(0, 0, 1), (30, 6, 1)], 2),
+    ((2, 3, 2, 3, 2, 3), [(1, 2, 6, 12, 36, 72), (108, 36, 18, 6, 3, 1)], 6),  # a fully reversed permutation keeps six dimensions
+])
+def test_glue_coalesce_keeps_every_operands_offsets(shape, strides, want_dims):
+    """glue_mode._coalesce: merged dimensions address exactly the elements, in the same order, for every operand -- and adjacent
+    dimensions merge only where every operand walks them contiguously (a broadcast or flipped operand stops a merge)"""
+    from spike2former_amd.ops import glue
+    size, cs = glue._coalesce(shape, [list(s) for s in strides])
+    assert len(size) == want_dims and (all(n > 1 for n in size) or size == [1])
+    assert int(np.prod(size)) == int(np.prod(shape))
+    assert _walk(list(size), cs) == _walk(list(shape), strides)
+
+
+def test_glue_coalesce_on_flip_strides():
+    """the strides h_flip builds (negated on the flipped dimensions, base at the far corner) coalesce to the same walk"""
+    from spike2former_amd.ops import glue
+    x = torch.arange(120.).view(2, 3, 4, 5)
+    for dims in [(3,), (0,), (0, 1, 2, 3), (1, 2), (-1, 0)]:
+        sa, off = list(x.stride()), 0
+        for d in {d % 4 for d in dims}:
+            off += (x.shape[d] - 1) * sa[d]
+            sa[d] = -sa[d]
+        size, (ca, co) = glue._coalesce(tuple(x.shape), [sa, [60, 20, 5, 1]])
+        got = torch.empty(120)
+        got[np.array(_walk(size, [co])[0])] = x.flatten()[off + np.array(_walk(size, [ca])[0])]
+        assert torch.equal(got, torch.flip(x, dims).flatten()), dims
+
+
+def _aten_shape(fn):
+    try:
+        return list(fn().shape)
+    except (RuntimeError, IndexError, ValueError):
+        return None
+
+
+@pytest.mark.parametrize("device", ["cpu", "meta"])
+def test_glue_shape_checks_match_aten(device):
+    """the host checks in front of GlueMode's cat / cat.out / stack / constant_pad_nd launches: the shape ATen computes, and None
+    exactly where ATen refuses the call -- mismatched pieces never reach s2f_copy_segments / s2f_ew (they would write past `out`)"""
+    from spike2former_amd.ops import glue
+    mk = lambda *s: torch.empty(s, device=device)          # noqa: E731
+    cats = [([(2, 3), (4, 3)], 0), ([(2, 3), (2, 5)], 1), ([(2, 3), (2, 5)], -1), ([(2, 3), (4, 4)], 0), ([(2, 3), (2, 4)], 0),
+            ([(2, 3), (3,)], 0), ([(2, 3), (0,), (1, 3)], 0), ([(0,), (2, 3)], 1), ([(0,), (0,)], 0), ([(2, 3)], 2), ([(2, 3)], -3),
+            ([(), ()], 0), ([(2, 3, 4), (2, 3, 4)], 1), ([(2, 3, 4), (2, 4, 4)], 2), ([(1, 4), (2, 4), (3, 4)], 0), ([(4, 0), (4, 2)], 1)]
+    for shapes, dim in cats:
+        want = _aten_shape(lambda: torch.cat([mk(*s) for s in shapes], dim))
+        if want == [0]:
+            want = None          # (only legacy empty pieces: nothing to route)
+        assert glue.cat_shape(shapes, dim) == want, (shapes, dim)
+        # cat.out: h_cat_out takes the call only for an `out` of exactly that shape
+        if want is not None:
+            out = mk(*want)
+            assert list(torch.cat([mk(*s) for s in shapes], dim, out=out).shape) == want
+    stacks = [([(2, 3), (2, 3)], 0), ([(2, 3), (2, 3)], 1), ([(2, 3), (2, 3)], 2), ([(2, 3), (2, 3)], -1), ([(2, 3), (2, 3)], 3),
+              ([(2, 3), (2, 3)], -4), ([(2, 3), (3, 2)], 0), ([(2, 3), (2, 3, 1)], 0), ([], 0), ([(), ()], 0)]
+    for shapes, dim in stacks:
+        want = _aten_shape(lambda: torch.stack([mk(*s) for s in shapes], dim))
+        assert glue.stack_shape(shapes, dim) == want, (shapes, dim)
+    pads = [((2, 3), [1, 2]), ((2, 3), [1, 2, 3, 4]), ((2, 3), [1, 2, 3, 4, 5, 6]), ((2, 3), [1]), ((2, 3, 4), [0, 0, 2, 0]),
+            ((5,), [3, 3]), ((5,), [1, 1, 1, 1]), ((), [1, 1]), ((2, 3), [])]
+    for shape, pad in pads:
+        want = _aten_shape(lambda: torch.constant_pad_nd(mk(*shape), pad))
+        assert glue.pad_shape(shape, pad) == want, (shape, pad)
+    # negative padding crops in ATen; the glue leaves it to ATen
+    assert glue.pad_shape((4, 4), [-1, 0]) is None and _aten_shape(lambda: torch.constant_pad_nd(mk(4, 4), [-1, 0])) == [4, 3]
+
+
+def test_glue_handlers_refuse_bad_shapes_before_any_launch(monkeypatch):
+    """the handlers hand ATen-refused shapes back (NotImplemented) before they allocate or launch.  CPU tensors would not get that
+    far (_ok wants CUDA), so stand-ins carry just the attributes the checks read: any allocation or launch would fail on them."""
+    from spike2former_amd.ops import glue
+
+    class Fake:
+        is_cuda, dtype, device = True, torch.float32, torch.device("cuda", 0)
+
+        def __init__(self, *shape):
+            self.shape = torch.Size(shape)
+
+        def numel(self):
+            return int(np.prod(self.shape))
+
+        def dim(self):
+            return len(self.shape)
+
+        def is_conj(self):
+            return False
+
+    is_tensor = torch.is_tensor
+    monkeypatch.setattr(torch, "is_tensor", lambda t: isinstance(t, Fake) or is_tensor(t))
+    assert glue.h_cat([Fake(2, 3), Fake(2, 4)], 0) is NotImplemented
+    assert glue.h_cat([Fake(2, 3), Fake(4, 3)], 1) is NotImplemented
+    assert glue.h_cat([Fake(2, 3), Fake(2, 3)], 2) is NotImplemented
+    assert glue.h_cat_out([Fake(2, 3), Fake(2, 4)], 0, out=Fake(4, 3)) is NotImplemented
+    assert glue.h_cat_out([Fake(2, 3), Fake(2, 3)], 0, out=Fake(5, 3)) is NotImplemented
+    assert glue.h_stack([Fake(2, 3), Fake(3, 2)], 0) is NotImplemented
+    assert glue.h_stack([Fake(2, 3), Fake(2, 3)], 3) is NotImplemented
+    assert glue.h_constant_pad_nd(Fake(2, 3), [1, 1, 1, 1, 1, 1]) is NotImplemented
+    assert glue.h_constant_pad_nd(Fake(2, 3), [1, 1, 1]) is NotImplemented
+    assert glue.h_flip(Fake(2, 3), [0, 0]) is NotImplemented and glue.h_flip(Fake(2, 3), [2]) is NotImplemented
+    assert glue.h_sum_dim(Fake(2, 3), [0, -2]) is NotImplemented and glue.h_sum_dim(Fake(2, 3), [2]) is NotImplemented
+    assert glue.h_repeat(Fake(2, 3), [2]) is NotImplemented and glue.h_repeat(Fake(2, 3), [1, -1]) is NotImplemented
