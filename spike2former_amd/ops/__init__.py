@@ -1,7 +1,9 @@
 """torch.autograd wrappers around the C ABI, by kernel family: neuron (lif.hip), bn (bn_lif.hip), gemm (pgemm / gemm / gemm_bf16),
 conv (dwconv.hip + the k x k lowering), attention (sdsa.hip, dcnv3.hip), misc (transposes, up-sampling, mask losses); `core` holds
-the shared plumbing and `config` every process-global switch (ops.cfg).  `ops.NAME` keeps working for every function and for every
-switch: reading or assigning `ops.PGEMM`, `ops.GRAD_SINKS`, ... goes to `ops.cfg`."""
+the shared plumbing and `config` the process-global switches that are left (ops.cfg: runtime objects, semantics, debugging aids and
+the A/B switches the tests and bench.py set).  `ops.NAME` keeps working for every function and for every switch: reading or assigning
+`ops.STRICT`, `ops.GRAD_SINKS`, ... goes to `ops.cfg`; assigning an ALL-CAPS name that is no switch raises instead of creating a
+module attribute nothing reads."""
 import sys
 import types
 
@@ -28,6 +30,9 @@ class _OpsModule(types.ModuleType):
     def __setattr__(self, name, value):
         if name in config.Config.FIELDS:
             setattr(cfg, name, value)
+        elif name.isupper() and name not in self.__dict__:
+            raise AttributeError(f"module 'spike2former_amd.ops' has no switch {name!r}: the switches live in ops.cfg "
+                                 f"(ops.cfg.FIELDS); a retired one is fixed at the value docs/EXPERIMENTS.md lists")
         else:
             super().__setattr__(name, value)
 

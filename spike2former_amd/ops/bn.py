@@ -195,7 +195,7 @@ class _BN2Act(torch.autograd.Function):
 
 def bn2_act_ok(z):
     N, C = z.shape[0], z.shape[1]
-    return bool(cfg.BN2_FUSED and z.is_cuda and z.numel() and lib.s2f_bn2_fused_ok(N, C, z.numel() // (N * C)))
+    return bool(z.is_cuda and z.numel() and lib.s2f_bn2_fused_ok(N, C, z.numel() // (N * C)))
 
 
 def bn2_act(z, bn1, bn2, residual=None, lif=False, want_pre=True, v_in=None, keep_v=False, D=8, vth=1.0, stats=None):

@@ -141,12 +141,13 @@ class _ConvDense(torch.autograd.Function):
             y = torch.empty(N, M, H * W, dtype=torch.float32, device=x.device)
             _time_next("spike_gemm_fwd", 4 * N * H * W * (C + M), 2 * N * M * H * W * C * 9,
                        moved=N * H * W * ((2 if xb else 4) * C + 4 * M))
-            P = _want_partials(stats and cfg.PGEMM_CONV and xb and cfg.SPIKE_GEMM_TERMS == 3 and bias is None, N, M, H * W)
+            pg = xb and cfg.SPIKE_GEMM_TERMS == 3          # what the packed-weight pipeline takes
+            P = _want_partials(stats and pg and bias is None, N, M, H * W)
             if P:
                 part = torch.empty(M, P, 2, dtype=torch.float32, device=x.device)
                 check(lib.s2f_pgemm_conv3x3_bf16_stats(_ptr(pack_weight_conv3(weight)), _ptr(x), _ptr(y), _ptr(part), N, M, C, H, W,
                                                        _stream()), "s2f_pgemm_conv3x3_bf16_stats")
-            elif cfg.PGEMM_CONV and xb and cfg.SPIKE_GEMM_TERMS == 3:
+            elif pg:
                 check(lib.s2f_pgemm_conv3x3_bf16(_ptr(pack_weight_conv3(weight)), _ptr(x), _ptr(bias), _ptr(y), N, M, C, H, W, 0,
                                                  _stream()), "s2f_pgemm_conv3x3_bf16")
             else:
@@ -169,7 +170,7 @@ class _ConvDense(torch.autograd.Function):
             y = torch.empty(N, M, L, dtype=torch.float32, device=x.device)
             _time_next("spike_gemm_fwd", 4 * N * L * (cols.shape[1] + M), 2 * N * M * L * cols.shape[1],
                        moved=N * L * ((2 if xb else 4) * cols.shape[1] + 4 * M))
-            pg = cfg.PGEMM and xb and L % 4 == 0 and L >= 8 and cfg.SPIKE_GEMM_TERMS == 3
+            pg = xb and L >= 8 and cfg.SPIKE_GEMM_TERMS == 3          # as _SpikeGemm (use_mfma: L % 4 == 0)
             P = _want_partials(stats and pg and bias is None, N, M, L)
             if P:
                 part = torch.empty(M, P, 2, dtype=torch.float32, device=x.device)
@@ -186,7 +187,7 @@ class _ConvDense(torch.autograd.Function):
         else:
             if xb:
                 cols = cols.float()
-            if cfg.PGEMM_DX and L % 4 == 0 and L >= cfg.PGEMM_MIN_N:
+            if L % 4 == 0 and L >= _PGEMM_MIN_N:
                 # general fp32 input (the stem reads the image): the transposed product on the pack of W^T, 6 passes
                 y = torch.empty(N, M, L, dtype=torch.float32, device=x.device)
                 _time_next("dx_gemm", 4 * N * L * (cols.shape[1] + M), 2 * N * M * L * cols.shape[1])
@@ -221,14 +222,14 @@ class _ConvDense(torch.autograd.Function):
         xb = cols.dtype == torch.bfloat16
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             if (cfg.CONV3X3_DX_IMPLICIT and kh == 3 and kw == 3 and stride == 1 and padding == 1 and M % 32 == 0 and W % 4 == 0
-                    and gy.is_cuda and H * W >= cfg.CONV3X3_DX_MIN_PIXELS):
+                    and gy.is_cuda):
                 # transposed convolution dX = flip(W)^T (*) dY as an implicit 6-pass split GEMM: no unfold(dY), no col2im
                 gx = torch.empty(N, C, H, W, dtype=torch.float32, device=gy.device)
                 _time_next("dx_gemm", 4 * N * H * W * (C + M), 2 * N * M * H * W * C * 9)
                 # measured (tools/probe_pgemm.py conv): the pipelined kernel wins for <= 64 output rows (narrow tiles: 442 vs 729 us
                 # on [32 <- 128] at 256 x 256) and for long contractions (>= 256 channels); the round-2 kernel keeps a 5-10 % edge
                 # on wide outputs over short contractions
-                if cfg.PGEMM_CONV and (cfg.CONV3X3_DX_PIPE == 2 or (cfg.CONV3X3_DX_PIPE == 1 and (C <= 64 or M >= 256))):
+                if C <= 64 or M >= 256:
                     check(lib.s2f_pgemm_conv3x3_f32(_ptr(pack_weight_conv3(weight, transposed=True)), _ptr(gy), _ptr(gx), N, C, M, H,
                                                     W, 0, _stream()), "s2f_pgemm_conv3x3_f32")
                 else:
@@ -246,17 +247,13 @@ class _ConvDense(torch.autograd.Function):
             K = w2d.shape[1]
             if ctx.implicit:
                 x = cols                                                  # the saved tensor is the activation itself
-                # bf16 spikes: the kernels store the gradient in the weight's own layout [M, C, 3, 3] (they contract tap-major) and add
-                # into the parameter's slot of the flat gradient buffer when there is one -- no zeroed staging tensor, no permuted add
+                # the kernels contract tap-major into a [M, 3, 3, C] staging tensor (the pipelined one adds into it, zeroed first); a
+                # permuted add moves it to the sink (storing in the weight's own layout measured slower: docs/EXPERIMENTS.md)
                 sink = _sink_for(weight)
-                direct = xb and cfg.CONV_DW_DIRECT
-                if direct:
-                    gt = sink if sink is not None else torch.zeros(M, C, 3, 3, dtype=torch.float32, device=gy.device)
-                else:
-                    gt = torch.empty(M, 3, 3, C, dtype=torch.float32, device=gy.device)    # tap-major, as the kernel contracts
+                gt = torch.empty(M, 3, 3, C, dtype=torch.float32, device=gy.device)
                 _time_next("spike_gemm_dw", 4 * N * H * W * (C + M), 2 * N * M * H * W * K,
                            moved=N * H * W * ((2 if xb else 4) * C + 4 * M))
-                if xb and cfg.DW_PIPE_CONV and M >= 128 and C >= 64 and lib.s2f_spike_conv3x3_dw_pipe_ok(N, M, C, H, W):
+                if xb and M >= 128 and C >= 64 and lib.s2f_spike_conv3x3_dw_pipe_ok(N, M, C, H, W):
                     # the LDS-DMA pipelined kernel (csrc/dwp.hip): the horizontal taps come from a copy shifted by one element.
                     # Its tile is 128 output channels x 256 (tap, input channel) rows: narrower layers stay on the round-2 kernel
                     # (measured, tools/probe_dwp_conv.py: M = 32 / 64 lose 10-70 %, C = 32 ties)
@@ -264,26 +261,22 @@ class _ConvDense(torch.autograd.Function):
                     xs = torch.empty(x.numel() + 16, dtype=x.dtype, device=x.device)
                     check(lib.s2f_shift1_bf16(_ptr(x), _ptr(xs), x.numel(), _stream()), "s2f_shift1_bf16")
                     arr = (ctypes.c_int64 * 9)(_ptr(gy), _ptr(x), _ptr(xs), _ptr(gt), N, M, C, H, W)
-                    if not direct:
-                        gt.zero_()
-                    check(lib.s2f_spike_conv3x3_dw_pipe(arr, 1, (cfg.DWP_SCHEDULE & 1) | (2 if direct else 0), cfg.DWP_WGS, _stream()),
-                          "s2f_spike_conv3x3_dw_pipe")
+                    gt.zero_()
+                    check(lib.s2f_spike_conv3x3_dw_pipe(arr, 1, 0, 0, _stream()), "s2f_spike_conv3x3_dw_pipe")
                 elif xb:
-                    check(lib.s2f_spike_conv3x3_dw_bf16(_ptr(gy), _ptr(x), _ptr(gt), N, M, C, H, W, 3 if direct else 0, _stream()),
+                    check(lib.s2f_spike_conv3x3_dw_bf16(_ptr(gy), _ptr(x), _ptr(gt), N, M, C, H, W, 0, _stream()),
                           "s2f_spike_conv3x3_dw_bf16")
                 else:
                     check(lib.s2f_spike_conv3x3_dw(_ptr(gy), _ptr(x), _ptr(gt), N, M, C, H, W, 0, _stream()), "s2f_spike_conv3x3_dw")
-                if direct:
-                    gw = None if sink is not None else gt
-                elif sink is not None:
+                if sink is not None:
                     sink.view(M, C, 3, 3).add_(gt.permute(0, 3, 1, 2))
                     gw = None
                 else:
                     gw = gt.permute(0, 3, 1, 2).contiguous()
-            elif use_mfma and cfg.SPIKE_GEMM_DW and M >= 16:
+            elif use_mfma and M >= 16:
                 sink = _sink_for(weight)
                 gw = torch.empty(M, K, dtype=torch.float32, device=gy.device) if sink is None else None
-                if (cfg.DEFER_DW and sink is not None and xb and N * Ho * Wo <= cfg.DEFER_DW_MAX_CONTRACTION and cfg.WGRAD_STREAM is None):
+                if _may_defer_dw(sink, N, Ho * Wo) and xb:          # (cols is im2col's own allocation: aligned)
                     _defer_dw(gy, cols, sink, N, M, K, Ho * Wo)
                     return _grad_pair(ctx.has_tok, gx) + (None, gy.sum((0, 2)) if (has_bias and ctx.needs_input_grad[3]) else None,
                                                           None, None, None, None)
@@ -297,7 +290,7 @@ class _ConvDense(torch.autograd.Function):
                 else:
                     check(lib.s2f_spike_gemm_dw(_ptr(gy), _ptr(cols), _ptr(gw if sink is None else sink), N, M, K, Ho * Wo,
                                                 int(sink is not None), 1, st), "s2f_spike_gemm_dw")
-            elif cfg.PGEMM_DX and (Ho * Wo) % 4 == 0 and cols.dtype == torch.float32:
+            elif (Ho * Wo) % 4 == 0 and cols.dtype == torch.float32:
                 # both operands general fp32 (the stem): 6-pass weight-gradient kernel, straight into the sink when there is one
                 sink = _sink_for(weight)
                 gw = torch.empty(M, K, dtype=torch.float32, device=gy.device) if sink is None else None

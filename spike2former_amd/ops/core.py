@@ -187,6 +187,17 @@ def wgrad_join():
 _DW_PENDING = {64: [], 32: []}
 
 
+# (round 5, with the pipelined grouped kernel: 131 072 -- the 128 x 128 maps' layers join the grouped launch -- 36.31 ms against
+#  36.48 at 32 768 and 36.39-36.44 beyond, same box)
+_DEFER_DW_MAX_CONTRACTION = 131072
+
+
+def _may_defer_dw(sink, B, L):
+    """The deferral rule of every weight-gradient site: into a sink, on the step's own stream, a contraction B * L short enough to gain
+    from the grouped launch.  What the queue's kernel asks of the operands (bf16 spikes, alignment, L % 4 == 0) the caller adds."""
+    return cfg.DEFER_DW and sink is not None and B * L <= _DEFER_DW_MAX_CONTRACTION and cfg.WGRAD_STREAM is None
+
+
 def _defer_dw(gy, x, sink, B, M, K, L):
     _DW_PENDING[64 if (L % 64 == 0 or L >= 512) else 32].append((gy, x, sink, B, M, K, L))
 
@@ -196,7 +207,7 @@ _DWG_PENDING = []          # general (fp32 x fp32) weight gradients: (dY ptr, dy
 
 def _defer_dw_general(gy, gy_off, dy_bs, x, x_off, x_bs, sink, B, M, K, L):
     """-> True if the weight gradient  sink += sum_b dY[b] X[b]^T  was queued for the grouped launch of wgrad_flush()."""
-    if not (cfg.DEFER_DW and sink is not None and B * L <= cfg.DEFER_DW_MAX_CONTRACTION and cfg.WGRAD_STREAM is None and L % 4 == 0):
+    if not (_may_defer_dw(sink, B, L) and L % 4 == 0):          # the grouped general kernel contracts in groups of 4
         return False
     _DWG_PENDING.append((gy.data_ptr() + 4 * gy_off, dy_bs, x.data_ptr() + 4 * x_off, x_bs, sink, B, M, K, L, (gy, x)))
     return True
@@ -224,42 +235,36 @@ def wgrad_flush():
                    sum(2 * j[5] * j[6] * j[7] * j[8] for j in chunk))
         check(lib.s2f_gemm_dw_general_grouped(arr, len(chunk), _stream()), "s2f_gemm_dw_general_grouped")
         del _DWG_PENDING[:56]
+
+    def grouped(jobs, launch, name):
+        """empties `jobs` [(dY, X, sink, B, M, K, L)] in launches of at most 56"""
+        while jobs:
+            chunk = jobs[:56]
+            flat = []
+            for gy, x, sink, B, M, K, L in chunk:
+                flat += [gy.data_ptr(), x.data_ptr(), sink.data_ptr(), B, M, K, L]
+            arr = (ctypes.c_int64 * len(flat))(*flat)
+            _time_next("spike_gemm_dw", sum(4 * B * L * (K + M) for _, _, _, B, M, K, L in chunk),
+                       sum(2 * B * M * L * K for _, _, _, B, M, K, L in chunk),
+                       moved=sum(B * L * (2 * K + 4 * M) for _, _, _, B, M, K, L in chunk))
+            check(launch(arr, len(chunk)), name)
+            del jobs[:56]
+
     if cfg.DW_PIPE:
         # the jobs the pipelined kernel takes (L % 4 == 0, L >= 32) leave their step classes for ONE list: a grouped launch spreads equal
         # shares of all its jobs over the CUs, so the more it holds the better
         pipe = []
-        for bkv, jobs in _DW_PENDING.items():
-            rest = []
-            for j in jobs:
-                # the pipelined kernel copies 16-byte pieces of both operands by LDS-DMA (S2F_EALIGN otherwise) and its symmetric
-                # schedule takes whole 32-element steps only: ONE job it rejects would fail the whole grouped launch in the middle of
-                # a backward pass, so anything else stays on the round-2 grouped kernel, which takes 8-byte-aligned operands
-                ok = (lib.s2f_spike_gemm_dw_pipe_ok(j[3], j[4], j[5], j[6]) and j[0].data_ptr() % 16 == 0 and j[1].data_ptr() % 16 == 0
-                      and (j[6] % 32 == 0 or cfg.DWP_SCHEDULE == 0))
-                (pipe if ok else rest).append(j)
-            jobs[:] = rest
-        while pipe:
-            chunk, pipe = pipe[:56], pipe[56:]
-            flat = []
-            for gy, x, sink, B, M, K, L in chunk:
-                flat += [gy.data_ptr(), x.data_ptr(), sink.data_ptr(), B, M, K, L]
-            arr = (ctypes.c_int64 * len(flat))(*flat)
-            _time_next("spike_gemm_dw", sum(4 * B * L * (K + M) for _, _, _, B, M, K, L in chunk),
-                       sum(2 * B * M * L * K for _, _, _, B, M, K, L in chunk),
-                       moved=sum(B * L * (2 * K + 4 * M) for _, _, _, B, M, K, L in chunk))
-            check(lib.s2f_spike_gemm_dw_pipe_grouped(arr, len(chunk), cfg.DWP_SCHEDULE, cfg.DWP_WGS, _stream()), "s2f_spike_gemm_dw_pipe_grouped")
+        for jobs in _DW_PENDING.values():
+            # the pipelined kernel copies 16-byte pieces of both operands by LDS-DMA (S2F_EALIGN otherwise): ONE job it rejects would
+            # fail the whole grouped launch in the middle of a backward pass, so anything else stays on the round-2 grouped kernel,
+            # which takes 8-byte-aligned operands
+            ok = [bool(lib.s2f_spike_gemm_dw_pipe_ok(*j[3:7])) and j[0].data_ptr() % 16 == 0 and j[1].data_ptr() % 16 == 0 for j in jobs]
+            pipe += [j for j, o in zip(jobs, ok) if o]
+            jobs[:] = [j for j, o in zip(jobs, ok) if not o]
+        # (schedule 0: two halves in opposite phase, takes ragged jobs; 0 workgroups: one per CU)
+        grouped(pipe, lambda arr, n: lib.s2f_spike_gemm_dw_pipe_grouped(arr, n, 0, 0, _stream()), "s2f_spike_gemm_dw_pipe_grouped")
     for bkv, jobs in _DW_PENDING.items():
-        while jobs:
-            chunk, rest = jobs[:56], jobs[56:]
-            flat = []
-            for gy, x, sink, B, M, K, L in chunk:
-                flat += [gy.data_ptr(), x.data_ptr(), sink.data_ptr(), B, M, K, L]
-            arr = (ctypes.c_int64 * len(flat))(*flat)
-            _time_next("spike_gemm_dw", sum(4 * B * L * (K + M) for _, _, _, B, M, K, L in chunk),
-                       sum(2 * B * M * L * K for _, _, _, B, M, K, L in chunk),
-                       moved=sum(B * L * (2 * K + 4 * M) for _, _, _, B, M, K, L in chunk))
-            check(lib.s2f_spike_gemm_dw_grouped(arr, len(chunk), bkv, _stream()), "s2f_spike_gemm_dw_grouped")
-            jobs[:] = rest
+        grouped(jobs, lambda arr, n: lib.s2f_spike_gemm_dw_grouped(arr, n, bkv, _stream()), "s2f_spike_gemm_dw_grouped")
 
 
 # ---- concurrency inside one step -------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@ def bmm_small(a, b, reduce_batch=False):
     return c
 
 
+_PGEMM_MIN_N = 128          # the forward products of s2f_pgemm_dx_f32 want at least one 128-column tile
 
 
 class _DenseGemm(torch.autograd.Function):
@@ -42,7 +43,7 @@ class _DenseGemm(torch.autograd.Function):
     X [B, G*K, L] -> [B, G*M, L].  Forward and input gradient on s2f_pgemm_dx_f32 (the transposed product on the pack of W^T
     resp. W, X / dY split hi + mid + lo in the kernel: 6 passes), weight gradient on s2f_gemm_dw_general; a group is a call
     with offset pointers and the batch strides of the full tensors (no copies).  Shapes the kernels do not take (L % 4 != 0,
-    L < 128) fall back to the library GEMM."""
+    L < 128) run on ops.bmm_small."""
 
     @staticmethod
     def forward(ctx, stats, x, *ws):
@@ -52,7 +53,7 @@ class _DenseGemm(torch.autograd.Function):
         B, _, L = x.shape
         x = x.contiguous()
         ctx.save_for_backward(x, *ws)
-        ctx.fast = cfg.PGEMM_DX and L % 4 == 0 and L >= cfg.PGEMM_MIN_N
+        ctx.fast = L % 4 == 0 and L >= _PGEMM_MIN_N          # rows of whole 16-byte groups, at least one 128-column tile
         if ctx.fast:
             y = torch.empty(B, G * M, L, dtype=torch.float32, device=x.device)
             P = _want_partials(stats, B, G * M, L)
@@ -151,8 +152,8 @@ _SPLIT_CACHE = {}
 # the implicit form wins from 32x32 up -- same-box A/B of the step: threshold 128x128 43.92, 64x64 43.39, 32x32 43.44 ms -- and
 # the bf16 column matrices of the 64x64 / 32x32 stages (ATen im2col) are gone.
 # input gradient of the 3x3 convolutions as an implicit transposed convolution on the 6-pass split GEMM (no unfold / col2im)
-# Round 3: the LDS-DMA pipelined kernels (csrc/pgemm.hip).  PGEMM: forward spike GEMMs on s2f_pgemm_nn_bf16 (packed weight, bf16
-# spikes, any N % 4 == 0 since the register-staged form); PGEMM_DX: every fp32 x fp32 product that ran on the library in rounds 1-2 -- the input
+# Round 3: the LDS-DMA pipelined kernels (csrc/pgemm.hip): forward spike GEMMs on s2f_pgemm_nn_bf16 (packed weight, bf16
+# spikes, any N % 4 == 0 since the register-staged form); every fp32 x fp32 product that ran on the library in rounds 1-2 -- the input
 # gradients of the 1x1 convolutions and the forward products of the convolutions whose input is not a spike map -- on
 # s2f_pgemm_dx_f32 (6 bf16 passes = fp32 accuracy), their weight gradients on s2f_gemm_dw_general.
 # Round 4: BatchNorm statistics from the producing GEMM's epilogue, without atomics (s2f.h "BatchNorm statistics from the producing
@@ -408,7 +409,7 @@ class _SpikeGemm(torch.autograd.Function):
         y = torch.empty(B, M, N, dtype=torch.float32, device=x.device)
         xb = x.dtype == torch.bfloat16
         _time_next("spike_gemm_fwd", 4 * B * N * (K + M), 2 * B * M * N * K, moved=B * N * ((2 if xb else 4) * K + 4 * M))
-        pg = cfg.PGEMM and xb and N % 4 == 0 and N >= 8 and cfg.SPIKE_GEMM_TERMS == 3
+        pg = xb and N % 4 == 0 and N >= 8 and cfg.SPIKE_GEMM_TERMS == 3          # what the packed-weight pipeline takes
         P = _want_partials(stats and pg and bias is None, B, M, N)
         part = torch.empty(M, P, 2, dtype=torch.float32, device=x.device) if P else None
         if P:
@@ -443,19 +444,19 @@ class _SpikeGemm(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             M, K = w2d.shape
             L = x.shape[2]
-            if cfg.SPIKE_GEMM_DW and L % 4 == 0 and M >= 16:     # 32- / 64- / 128-row tiles by M
+            if L % 4 == 0 and M >= 16:     # the matrix-core kernels: 32- / 64- / 128-row tiles by M
                 sink = _sink_for(w2d)
                 gw = torch.empty(M, K, dtype=torch.float32, device=x.device) if sink is None else None
                 xb = x.dtype == torch.bfloat16
-                if (cfg.DEFER_DW and sink is not None and xb and B * L <= cfg.DEFER_DW_MAX_CONTRACTION and cfg.WGRAD_STREAM is None
-                        and x.data_ptr() % 8 == 0):
+                # (x may be a slice of a bf16 map at any 2-byte offset; the grouped kernels read 8-byte pieces)
+                if _may_defer_dw(sink, B, L) and xb and x.data_ptr() % 8 == 0:
                     _defer_dw(gy, x, sink, B, M, K, L)
                     return _grad_pair(ctx.has_tok, gx) + (None, gy.sum((0, 2)) if (ctx.has_bias and ctx.needs_input_grad[3]) else None,
                                                           None)
                 _time_next("spike_gemm_dw", 4 * B * L * (K + M), 2 * B * M * L * K, moved=B * L * ((2 if xb else 4) * K + 4 * M))
                 side = _wgrad_stream(sink, gy, x)
                 st = side.cuda_stream if side is not None else _stream()
-                if (xb and cfg.DW_PIPE and cfg.DW_PIPE_SINGLE and M >= 128 and K >= 128 and lib.s2f_spike_gemm_dw_pipe_ok(B, M, K, L)
+                if (xb and cfg.DW_PIPE and M >= 128 and K >= 128 and lib.s2f_spike_gemm_dw_pipe_ok(B, M, K, L)
                         and gy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0):
                     # long contractions launch on their own: the LDS-DMA pipeline where its 128 x 256 tile is filled
                     check(lib.s2f_spike_gemm_dw_pipe(_ptr(gy), _ptr(x), _ptr(gw if sink is None else sink), B, M, K, L,
@@ -477,7 +478,7 @@ def dx_gemm(w2d, gy):
     """Input gradient of a 1x1 convolution: gx[b] = W^T @ gy[b]  (two general fp32 operands): the transposed product on the
     forward pack of W with gy split hi + mid + lo in the kernel (s2f_pgemm_dx_f32, 6 passes)."""
     B, M, N = gy.shape
-    if cfg.PGEMM_DX and N % 4 == 0 and gy.is_cuda:
+    if N % 4 == 0 and gy.is_cuda:
         K = w2d.shape[1]
         gx = torch.empty(B, K, N, dtype=torch.float32, device=gy.device)
         _time_next("dx_gemm", 4 * B * N * (K + M), 2 * B * M * N * K)
@@ -490,7 +491,7 @@ def dx_gemm(w2d, gy):
 def gemm_bn_lif_eval_ok(x, N):
     """The eval-mode fusion takes bf16 spikes with N % 4 == 0, N >= 8 (the decoder's 100-token maps too), and builds no autograd
     graph."""
-    return (cfg.PGEMM and isinstance(x, Spikes) and x.data.dtype == torch.bfloat16 and x.data.is_cuda and N % 4 == 0
+    return (isinstance(x, Spikes) and x.data.dtype == torch.bfloat16 and x.data.is_cuda and N % 4 == 0
             and N >= 8 and x.data.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and x.requires_grad))
 
 
@@ -521,7 +522,7 @@ def gemm_bn_lif_eval(x, w2d, conv_bias, running_mean, running_var, gamma, beta, 
 def dense_gemm_bn_lif_eval_ok(x, N):
     """The eval-mode fusion of a 1x1 convolution whose input is a general fp32 map (not spikes): N % 4 == 0, at least one 128-column
     tile, no autograd graph."""
-    return (cfg.PGEMM_DX and torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda and N % 4 == 0 and N >= cfg.PGEMM_MIN_N
+    return (torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda and N % 4 == 0 and N >= _PGEMM_MIN_N
             and x.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and x.requires_grad))
 
 
@@ -647,7 +648,7 @@ def _mm_tm(x2d, w_oc):
     """x2d [n, c] @ w_oc[o, c]^T -> [n, o] on s2f_gemm_dw_general (both operands contraction-contiguous; no contraction split:
     repeats bit for bit); ops.bmm_small for c % 4 != 0."""
     n, c = x2d.shape
-    if not (cfg.LINEAR_TM and c % 4 == 0 and x2d.is_cuda and n > 0):
+    if not (c % 4 == 0 and x2d.is_cuda and n > 0):
         return bmm_small(x2d.unsqueeze(0), w_oc.t().unsqueeze(0))[0]
     y = torch.zeros(n, w_oc.shape[0], dtype=torch.float32, device=x2d.device)
     check(lib.s2f_gemm_dw_general(_ptr(x2d.contiguous()), 0, _ptr(w_oc.contiguous()), 0, _ptr(y), 1, n, w_oc.shape[0], c, 3, _stream()),
@@ -661,7 +662,7 @@ def _mtm_tm(a2d, b2d, out=None):
     [o, c] fp32 destination (16-byte aligned)."""
     n, o = a2d.shape
     c = b2d.shape[1]
-    if not (cfg.LINEAR_TM and c % 4 == 0 and a2d.is_cuda and n > 0):
+    if not (c % 4 == 0 and a2d.is_cuda and n > 0):
         r = bmm_small(a2d.t().unsqueeze(0), b2d.unsqueeze(0))[0]
         return r if out is None else out.copy_(r)
     ap = torch.empty(int(lib.s2f_pack_elems(n, o)), dtype=torch.int16, device=a2d.device)
@@ -703,7 +704,7 @@ def linear_tm(x, weight, bias=None):
     if not (x.is_cuda and x.dtype == torch.float32 and x.numel() > 0):
         fallback("linear_tm", f"c={c} dtype={x.dtype} cuda={x.is_cuda}")
         return torch.nn.functional.linear(x, weight, bias)
-    fn = _LinearTM if (cfg.LINEAR_TM and c % 4 == 0) else _LinearSmall
+    fn = _LinearTM if c % 4 == 0 else _LinearSmall
     return fn.apply(x.reshape(-1, c), weight, bias).view(*x.shape[:-1], weight.shape[0])
 
 
@@ -762,7 +763,7 @@ class _MaskEinsum(torch.autograd.Function):
         HW = mf.shape[-1]
         ge = gmf = None
         if ctx.needs_input_grad[0]:
-            if ctx.mfma and cfg.MASK_EINSUM_DE_MFMA:
+            if ctx.mfma:
                 # dE[t, b] = g[b] (Q x HW) @ MF[t, b]^T: both operands contraction-contiguous fp32 -> the weight-gradient
                 # kernel with both sides split hi+mid+lo (6 passes), split-K over HW with fp32 atomics
                 ge = torch.zeros_like(e)
@@ -804,7 +805,7 @@ class _MaskEinsumFolded(torch.autograd.Function):
     the convolution's own forward (69 GFLOP at C2), its weight gradient and the 537 MB fp32 mask_features tensor it wrote for
     the einsum to read back never exist, and dE needs 3 MFMA passes (spike operand) instead of 6.  Same value as the
     reference's two steps up to the association of fp32 sums (nothing thresholds this output).
-    Backward: G[t,b] = scale E[t,b]^T g[b] (3 passes, E exact in bf16) -> dS = W^T G (the convolution's input gradient);
+    Backward: dS[t,b] = (scale E[t,b] W)^T g[b] (the forward's [Q, C] matrix again; ragged HW: W^T (scale E^T g) on ops.bmm_small);
     H[t,b] = g[b] S[t,b]^T (weight-gradient kernel on a spike operand) -> dE = scale (H W^T + rowsum(g) bias^T),
     dW = scale sum E^T H, dbias = scale sum E^T rowsum(g)."""
 
@@ -822,7 +823,7 @@ class _MaskEinsumFolded(torch.autograd.Function):
         if bias is not None:
             rowb = (e.sum(0) * bias.view(1, 1, -1)).sum(-1).contiguous()       # [B, Q]: sum_t E[t, b] bias (a reduction, no GEMV)
         out = torch.empty(B, Q, HW, dtype=torch.float32, device=dev)
-        if cfg.PGEMM and cfg.MASK_FWD_PGEMM and HW % 8 == 0 and C % 32 == 0:
+        if HW % 8 == 0 and C % 32 == 0:
             # the pipelined NN kernel (LDS-DMA fed, csrc/pgemm.hip): one pack of (E W)[b] per batch element
             pe = int(lib.s2f_pack_elems(Q, T * C))
             a_pack = torch.empty(B, pe, dtype=torch.int16, device=dev)
@@ -842,20 +843,20 @@ class _MaskEinsumFolded(torch.autograd.Function):
                                                  Q if rowb is not None else 0, scale, _ptr(out), B, Q, HW, T * C, Mpad, Kpad, _stream()),
                   "s2f_spike_gemm_fwd_bf16_ex")
         ctx.save_for_backward(e, sdata, W, bias, ew)
-        ctx.cfg = (scale, T, B, bool(e_exact))
+        ctx.cfg = (scale, T, B)          # (e_exact: the fold contracts over the spikes, E W is general either way)
         return out
 
     @staticmethod
     def backward(ctx, g):
         e, sdata, W, bias, ew = ctx.saved_tensors
-        scale, T, B, e_exact = ctx.cfg
+        scale, T, B = ctx.cfg
         Q, Co = e.shape[2], e.shape[3]
         C, HW = sdata.shape[1], sdata.shape[2]
         g = g.contiguous()
         dev = g.device
         gs = ge = gW = gb = None
         S = sdata.view(T, B, C, HW)
-        if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and cfg.MASK_BWD_FOLDED and cfg.LINEAR_TM and HW % 4 == 0:
+        if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and HW % 4 == 0:
             # dS[t, b] = W^T (scale E[t, b]^T g[b]) = (scale E[t, b] W)^T g[b]: the fold of the forward, read backwards -- ONE product
             # per (t, b) over the Q queries with the [Q, C] matrix the forward already formed, instead of the [Co x Q] product into a
             # [T, B, Co, HW] intermediate (537 MB at C2) followed by the convolution's input-gradient GEMM over it.  Both operands
@@ -867,26 +868,18 @@ class _MaskEinsumFolded(torch.autograd.Function):
                 for b in range(B):
                     _mtm_tm(ews[t, b], g[b], out=gs[t * B + b])
         elif ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            # dS[t, b] = W^T (scale E[t, b]^T g[b]): the first product as in _MaskEinsum (E exact in bf16: 3 passes), the
-            # second is the mask_feature convolution's input gradient
+            # ragged rows (HW % 4 != 0): dS[t, b] = W^T (scale E[t, b]^T g[b]) in two steps on ops.bmm_small -- the second is the
+            # mask_feature convolution's input gradient
             G = torch.empty(T, B, Co, HW, dtype=torch.float32, device=dev)
-            if e_exact and HW % 4 == 0:
-                et = e.permute(0, 1, 3, 2).reshape(T * B * Co, Q)
-                a_split, Rpad, Kp = _split_rows(et, 128)
-                for t in range(T):
-                    check(lib.s2f_split_gemm(_ptr(a_split) + 2 * t * B * Co * Kp, Co * Kp, Rpad * Kp, 1, _ptr(g), Q * HW, Q, 0, 3,
-                                             _ptr(G[t]), Co * HW, scale, B, Co, HW, Q, (Co + 127) // 128 * 128, Kp, _stream()),
-                          "s2f_split_gemm")
-            else:
-                es = e * scale
-                for t in range(T):
-                    G[t].copy_(bmm_small(es[t].transpose(1, 2), g))
+            es = e * scale
+            for t in range(T):
+                G[t].copy_(bmm_small(es[t].transpose(1, 2), g))
             gs = dx_gemm(W, G.view(T * B, Co, HW))
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
             H = torch.empty(T, B, Q, C, dtype=torch.float32, device=dev)
             xb = sdata.dtype == torch.bfloat16
             _time_next("spike_gemm_dw", 4 * T * B * HW * (C + Q), 2 * T * B * Q * HW * C, moved=T * B * HW * ((2 if xb else 4) * C + 4 * Q))
-            if xb and cfg.MASK_EINSUM_DW_GROUPED and T * B <= 56 and HW % 4 == 0:
+            if xb and T * B <= 56 and HW % 4 == 0:
                 # the T * B products H[t, b] = g[b] S[t, b]^T as ONE grouped launch (12 output tiles each over a 65 536-long
                 # contraction: one by one they run at 183 TF/s) into the zeroed H
                 import ctypes
@@ -897,8 +890,8 @@ class _MaskEinsumFolded(torch.autograd.Function):
                         flat += [g[b].data_ptr(), S[t, b].data_ptr(), H[t, b].data_ptr(), 1, Q, C, HW]
                 arr = (ctypes.c_int64 * len(flat))(*flat)
                 if (cfg.DW_PIPE and lib.s2f_spike_gemm_dw_pipe_ok(1, Q, C, HW) and g.data_ptr() % 16 == 0 and S.data_ptr() % 16 == 0
-                        and (Q * HW) % 4 == 0 and (C * HW) % 8 == 0 and (HW % 32 == 0 or cfg.DWP_SCHEDULE == 0)):
-                    check(lib.s2f_spike_gemm_dw_pipe_grouped(arr, T * B, cfg.DWP_SCHEDULE, cfg.DWP_WGS, _stream()), "s2f_spike_gemm_dw_pipe_grouped")
+                        and (Q * HW) % 4 == 0 and (C * HW) % 8 == 0):
+                    check(lib.s2f_spike_gemm_dw_pipe_grouped(arr, T * B, 0, 0, _stream()), "s2f_spike_gemm_dw_pipe_grouped")
                 else:
                     check(lib.s2f_spike_gemm_dw_grouped(arr, T * B, 64, _stream()), "s2f_spike_gemm_dw_grouped")
             else:
@@ -936,7 +929,7 @@ def class_mask_product(cls_score, mask_probs):
     if torch.is_grad_enabled() and (cls_score.requires_grad or mask_probs.requires_grad):
         fallback("class_mask_product", "autograd wanted through the inference post-processing")
         return torch.einsum("bqc,bqhw->bchw", cls_score, mask_probs)
-    if not (cfg.LINEAR_TM and cls_score.is_cuda and (h * w) % 4 == 0 and cls_score.dtype == torch.float32):
+    if not ((h * w) % 4 == 0 and cls_score.dtype == torch.float32):          # (host tensors returned above)
         return bmm_small(cls_score.transpose(1, 2), mask_probs.reshape(B, Q, h * w)).view(B, K, h, w)
     out = torch.empty(B, K, h, w, dtype=torch.float32, device=cls_score.device)          # every image's product lands in its slice
     for b in range(B):

@@ -369,3 +369,72 @@ def test_glue_handlers_refuse_bad_shapes_before_any_launch(monkeypatch):
     assert glue.h_flip(Fake(2, 3), [0, 0]) is NotImplemented and glue.h_flip(Fake(2, 3), [2]) is NotImplemented
     assert glue.h_sum_dim(Fake(2, 3), [0, -2]) is NotImplemented and glue.h_sum_dim(Fake(2, 3), [2]) is NotImplemented
     assert glue.h_repeat(Fake(2, 3), [2]) is NotImplemented and glue.h_repeat(Fake(2, 3), [1, -1]) is NotImplemented
+
+
+# the switches that are left after the settled A/B comparisons were retired (docs/EXPERIMENTS.md, "Retired switches")
+_SWITCHES = ("KERNEL_EVENTS", "GRAD_SINKS", "WGRAD_STREAM", "BRANCH_STREAMS", "LONG_STREAMS", "LONG_WHAT", "SPIKES_BF16",
+             "SPIKE_GEMM_TERMS", "SPIKE_GEMM_ENABLED", "SPIKE_GEMM_CHECK", "CONV3X3_IMPLICIT", "CONV3X3_IMPLICIT_MIN_PIXELS",
+             "CONV3X3_DX_IMPLICIT", "DEFER_DW", "DW_PIPE", "BN_PARTIALS", "BN_PARTIALS_SINGLE", "DENSE_GROUPED", "RESPLIT_IN_GRAPH",
+             "FANOUT_PORTS", "GLUE_MODE", "STRICT_GLUE", "STRICT", "GENERAL_RESIZE")
+_RETIRED = ("PGEMM", "PGEMM_DX", "PGEMM_CONV", "PGEMM_MIN_N", "DEFER_DW_MAX_CONTRACTION", "CONV3X3_DX_MIN_PIXELS", "CONV3X3_DX_PIPE",
+            "CONV_DW_DIRECT", "DW_PIPE_SINGLE", "DW_PIPE_CONV", "DWP_SCHEDULE", "DWP_WGS", "SPIKE_GEMM_DW", "MASK_EINSUM_DW_GROUPED",
+            "MASK_EINSUM_DE_MFMA", "MASK_FWD_PGEMM", "MASK_BWD_FOLDED", "BN2_FUSED", "LINEAR_TM")
+
+
+def test_config_fields_are_the_switches_that_are_left():
+    from spike2former_amd.ops.config import Config
+    assert tuple(Config.FIELDS) == _SWITCHES
+    runtime = {"KERNEL_EVENTS", "GRAD_SINKS", "WGRAD_STREAM", "BRANCH_STREAMS", "LONG_STREAMS"}
+    assert set(Config().snapshot()) == set(_SWITCHES) - runtime - {"STRICT", "STRICT_GLUE"}
+    assert len(_RETIRED) == 19 and not set(_RETIRED) & set(Config.FIELDS)
+
+
+def test_a_stale_switch_fails_loudly():
+    from spike2former_amd import ops
+    with pytest.raises(AttributeError, match="ops.cfg"):
+        ops.PGEMM = False
+    with pytest.raises(AttributeError):
+        ops.cfg.DWP_SCHEDULE = 1
+    with pytest.raises(AttributeError, match="ops.cfg"):
+        ops.NO_SUCH_SWITCH = 1
+    for name in _RETIRED + ("NO_SUCH_SWITCH",):
+        assert name not in vars(ops) and not hasattr(ops.cfg, name)
+        with pytest.raises(AttributeError):
+            getattr(ops, name)
+        with pytest.raises(AttributeError):
+            setattr(ops, name, 1)
+        with pytest.raises(AttributeError):
+            setattr(ops.cfg, name, 1)
+    strict, fallbacks = ops.STRICT, ops.FALLBACKS
+    try:
+        ops.STRICT = not strict                     # a switch: forwarded to ops.cfg
+        assert ops.cfg.STRICT is (not strict) and "STRICT" not in vars(ops)
+        ops.FALLBACKS = {}                          # an existing module attribute stays assignable
+        assert ops.FALLBACKS == {}
+    finally:
+        ops.STRICT, ops.FALLBACKS = strict, fallbacks
+
+
+def test_a_retired_environment_variable_changes_nothing():
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path.insert(0, sys.argv[1]); from spike2former_amd.ops.config import Config; "
+            "print('SNAPSHOT', json.dumps(Config().snapshot(), sort_keys=True))")
+    retired = {"S2F_PGEMM": "0", "S2F_PGEMM_DX": "0", "S2F_PGEMM_CONV": "0", "S2F_DEFER_DW_MAX": "1", "S2F_CONV3_DX_PIPE": "2",
+               "S2F_MASK_DW_GROUPED": "0", "S2F_MASK_FWD_PGEMM": "0", "S2F_MASK_BWD_FOLDED": "0", "S2F_DW_PIPE_SINGLE": "0",
+               "S2F_DW_PIPE_CONV": "0", "S2F_DWP_SCHEDULE": "1", "S2F_DWP_WGS": "64", "S2F_BN2_FUSED": "0", "S2F_LINEAR_TM": "0",
+               "S2F_CONV_DW_DIRECT": "1"}
+    clean = {k: v for k, v in os.environ.items() if k not in retired}
+
+    def snapshot(env):
+        out = subprocess.run([sys.executable, "-c", code, root], env=env, check=True, capture_output=True, text=True).stdout
+        return json.loads([l for l in out.splitlines() if l.startswith("SNAPSHOT ")][-1][len("SNAPSHOT "):])
+    base = snapshot(clean)
+    assert set(base) == set(_SWITCHES) - {"KERNEL_EVENTS", "GRAD_SINKS", "WGRAD_STREAM", "BRANCH_STREAMS", "LONG_STREAMS", "STRICT",
+                                          "STRICT_GLUE"}
+    assert snapshot(dict(clean, S2F_PGEMM="0")) == base
+    assert snapshot(dict(clean, **retired)) == base
+    assert snapshot(dict(clean, S2F_DW_PIPE="0")) == dict(base, DW_PIPE=False)          # a switch that stayed is still read

@@ -75,7 +75,3 @@ cp gpurun_out/prof_${T}p_categories.txt gpurun_out/${T}_categories_predict.txt
 cp gpurun_out/prof_${T}p_kernels.txt gpurun_out/${T}_step_kernels_predict.txt
 cd $R
 bash tools/prof_ab_env.sh ${T}_dwpipe S2F_DW_PIPE=0 S2F_DW_PIPE=1 > /dev/null 2>&1
-cd $R
-bash tools/prof_ab_env.sh ${T}_maskfwd S2F_MASK_FWD_PGEMM=0 S2F_MASK_FWD_PGEMM=1 > /dev/null 2>&1
-cd $R
-bash tools/prof_ab_env.sh ${T}_dwpipe_conv S2F_DW_PIPE_CONV=0 S2F_DW_PIPE_CONV=1 > /dev/null 2>&1
