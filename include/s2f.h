@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 34
+#define S2F_ABI_VERSION 35
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -41,7 +41,7 @@ const char* s2f_last_error(void);
  * (hipExtLaunchKernelGGL start/stop events = the dispatch packet's own begin/end timestamps, what rocprofv3 reports).
  *   s2f_event_create/destroy: a hipEvent_t as void*.
  *   s2f_time_next_call(start, stop): arms THIS thread; the next s2f_lif_fwd / s2f_lif_bwd / s2f_bn_stats /
- *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm call stamps `start` with the begin of
+ *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist call stamps `start` with the begin of
  *       its first kernel and `stop` with the end of its last one, then disarms.  Not valid during stream capture.
  *   s2f_event_elapsed_us: stop - start in microseconds (both must have completed: synchronise first). */
 void* s2f_event_create(void);
@@ -518,6 +518,35 @@ int s2f_tta_accumulate(const float* x, float* acc, int K, int64_t plane_stride, 
                        int H, int W, int flags, int first, void* stream);
 /* acc [K, HW] /= n_views in place, then the arg-max / threshold of s2f_seg_argmax (no sigmoid) into label or label_f. */
 int s2f_tta_finish(float* acc, int64_t* label, float* label_f, int K, int64_t HW, int n_views, float threshold, void* stream);
+
+/* ---- evaluation: the class histograms behind mIoU / mDice / mFscore (csrc/segmetric.hip, ABI 35) ---------------------------------
+ * One image of IoUMetric.intersect_and_union (mmseg/evaluation/metrics/iou_metric.py:164-205: two boolean-mask gathers, three
+ * torch.histc(bins = K, min = 0, max = K - 1) on float copies, three device -> host copies, float32 sums over the images) as ONE
+ * launch that ADDS into totals, an int64 [3, K] device buffer the caller owns and zeroes: row 0 the intersection, row 1 the prediction
+ * areas, row 2 the label areas (the union is row 1 + row 2 - row 0, formed on the host).  For pixel p of HW, with l the label:
+ *   - the pixel takes part iff l != ignore_index;
+ *   - totals[1][c] += 1 when pred == c, totals[2][c] += 1 when l == c, totals[0][c] += 1 when pred == l == c, each for 0 <= c < K
+ *     only: a prediction or a label outside the classes counts nowhere (what histc does outside [min, max]) -- a pixel labelled 200 at
+ *     K = 150 takes part and its prediction still counts in row 1.
+ * Integer adds: independent of the arrival order, bit-repeatable, exact to 2^63 (the reference's float32 sums stop being exact at 2^24
+ * pixels per class).  Nothing is allocated and nothing synchronises: capturable in a hipGraph.
+ * pred: [HW] contiguous, S2F_SEG_PRED_I64 (what s2f_seg_argmax / s2f_tta_finish write for K > 1) or S2F_SEG_PRED_F32 (their one-class
+ * 0 / 1 maps; a float counts in class c iff it equals c exactly, which is the reference's comparison after label.to(pred)).
+ * label: S2F_SEG_LABEL_U8 (an annotation file as read) or S2F_SEG_LABEL_I64 (PackSegInputs); pixel p = (row p / W, column p % W) is
+ * label[row * label_row_stride + column * label_pixel_stride] (ELEMENT strides; W, 1 = contiguous; 1, H = a label stored transposed,
+ * the branch of iou_metric.py:187-190, read in place).
+ * flags: S2F_SEG_REDUCE_ZERO_LABEL applies LoadAnnotations' reduce_zero_label mapping to the raw label first (0 -> 255, 255 -> 255,
+ * every other value - 1), then the rules above: an un-shifted annotation scored directly.
+ * Bounds: 0 < HW < 2^31 - 8 (32-bit workgroup counters), HW % W == 0, 0 < K <= S2F_SEG_HIST_MAX_CLASSES (three rows of K 32-bit
+ * counters in LDS: 24 KiB at the bound). */
+#define S2F_SEG_HIST_MAX_CLASSES 2048
+#define S2F_SEG_PRED_I64 0
+#define S2F_SEG_PRED_F32 1
+#define S2F_SEG_LABEL_U8 0
+#define S2F_SEG_LABEL_I64 1
+#define S2F_SEG_REDUCE_ZERO_LABEL 1
+int s2f_seg_hist(const void* pred, int pred_dtype, const void* label, int label_dtype, int64_t label_row_stride,
+                 int64_t label_pixel_stride, int W, int64_t HW, int K, int ignore_index, int flags, int64_t* totals, void* stream);
 
 /* ---- batched transposition of the last two dimensions: x [B, R, C] -> y [B, C, R] (fp32) -----------------------------------
  * Replaces the `.permute(0, 1, 3, 4, 2)` / `.permute(0, 1, 4, 2, 3)` copies around the DCNv3 sampling core

@@ -405,6 +405,63 @@ def tta_finish(acc, n_views, threshold=0.3):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ evaluation
+SEG_HIST_MAX_CLASSES = 2048          # include/s2f.h S2F_SEG_HIST_MAX_CLASSES
+_SEG_PRED_CODES = {torch.int64: 0, torch.float32: 1}
+_SEG_LABEL_CODES = {torch.uint8: 0, torch.int64: 1}
+
+
+def _seg_hist_torch(pred, label, totals, ignore_index, reduce_zero_label):
+    """the semantics of s2f_seg_hist in exact integer torch arithmetic (CPU tensors; CUDA tensors the kernel does not take)"""
+    K = totals.shape[1]
+    lab = label.to(torch.int64)
+    if reduce_zero_label:
+        lab = torch.where((lab == 0) | (lab == 255), torch.full_like(lab, 255), lab - 1)
+    none = torch.full_like(lab, -1)
+    if pred.is_floating_point():
+        ok = (pred >= 0) & (pred < K) & (pred == pred.trunc())
+        pc = torch.where(ok, torch.where(ok, pred, torch.zeros_like(pred)).to(torch.int64), none)
+    else:
+        pred = pred.to(torch.int64)
+        pc = torch.where((pred >= 0) & (pred < K), pred, none)
+    lc = torch.where((lab >= 0) & (lab < K), lab, none)
+    part = lab != ignore_index
+    pc, lc = pc[part], lc[part]
+    totals[0] += torch.bincount(pc[(pc == lc) & (pc >= 0)], minlength=K)
+    totals[1] += torch.bincount(pc[pc >= 0], minlength=K)
+    totals[2] += torch.bincount(lc[lc >= 0], minlength=K)
+    return totals
+
+
+def seg_hist(pred, label, totals, ignore_index=255, reduce_zero_label=False):
+    """totals int64 [3, K] += {intersection, prediction areas, label areas} of ONE image over the pixels with label != ignore_index
+    (s2f_seg_hist; IoUMetric.intersect_and_union, mmseg iou_metric.py:164-205, as integer class histograms).  pred [H, W] or [1, H, W],
+    int64 or float32 0 / 1; label of the same shape -- or stored transposed ([W, H], iou_metric.py:187-190: read by strides, not
+    copied) -- uint8 or int64; `reduce_zero_label` maps a raw annotation on the fly (0 -> 255, 255 -> 255, else - 1).  CUDA tensors
+    run the kernel; CPU tensors the same arithmetic in torch (the package's CPU implementation of this op)."""
+    pred = pred[0] if pred.dim() == 3 and pred.shape[0] == 1 else pred
+    label = label[0] if label.dim() == 3 and label.shape[0] == 1 else label
+    assert pred.dim() == 2 and label.dim() == 2, "one [H, W] (or [1, H, W]) prediction and label map"
+    if label.shape[0] != pred.shape[0] and label.shape[0] == pred.shape[1]:
+        label = label.t()
+    assert label.shape == pred.shape, f"label {tuple(label.shape)} does not fit the prediction {tuple(pred.shape)}"
+    assert totals.dtype == torch.int64 and totals.dim() == 2 and totals.shape[0] == 3 and totals.is_contiguous()
+    assert pred.device == label.device == totals.device, "pred, label and totals on one device"
+    H, W = pred.shape
+    K = totals.shape[1]
+    if not pred.is_cuda:
+        return _seg_hist_torch(pred, label, totals, int(ignore_index), bool(reduce_zero_label))
+    if (pred.dtype not in _SEG_PRED_CODES or label.dtype not in _SEG_LABEL_CODES or not 0 < K <= SEG_HIST_MAX_CLASSES
+            or not 0 < H * W < 2 ** 31 - 8 or abs(int(ignore_index)) >= 2 ** 31):
+        fallback("seg_hist", f"pred {pred.dtype}, label {label.dtype}, K {K}, {H} x {W}")
+        return _seg_hist_torch(pred, label, totals, int(ignore_index), bool(reduce_zero_label))
+    pred = pred.contiguous()
+    check(lib.s2f_seg_hist(_ptr(pred), _SEG_PRED_CODES[pred.dtype], _ptr(label), _SEG_LABEL_CODES[label.dtype], label.stride(0),
+                           label.stride(1), W, H * W, K, int(ignore_index), int(bool(reduce_zero_label)), _ptr(totals), _stream()),
+          "s2f_seg_hist")
+    return totals
+
+
 # ------------------------------------------------------------------------------------------------ mask losses (row f1)
 class _MaskLossSums(torch.autograd.Function):
     """sums[p] = {sum s t, sum s, sum t, sum focal} over the 2x up-sampled logits of matched prediction p against its binary

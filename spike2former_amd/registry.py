@@ -74,6 +74,7 @@ class Registry:
 
 MODELS = Registry("spike2former_amd.MODELS")
 HOOKS = Registry("spike2former_amd.HOOKS")
+METRICS = Registry("spike2former_amd.METRICS")
 
 
 def register_upstream():
@@ -91,4 +92,13 @@ def register_upstream():
             if cls is not None:
                 mod.MODELS.register_module(name=n, module=cls, force=True)
                 done.append(f"{pkg}:{n}")
+    # the evaluator of every shipped config (val_evaluator = dict(type='IoUMetric', ...)): offered where mmseg has a METRICS registry
+    try:
+        mod = __import__("mmseg.registry", fromlist=["METRICS"])
+    except Exception:
+        return done
+    cls = METRICS.get("IoUMetric")
+    if cls is not None and hasattr(mod, "METRICS"):
+        mod.METRICS.register_module(name="IoUMetric", module=cls, force=True)
+        done.append("mmseg.registry:IoUMetric")
     return done
