@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 35
+#define S2F_ABI_VERSION 36
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -594,6 +594,34 @@ int s2f_mask_loss_seg_fwd(const float* pred, const uint8_t* seg, const int32_t* 
                           int h, int w, float alpha, float gamma, void* stream);
 int s2f_mask_loss_seg_bwd(const float* pred, const uint8_t* seg, const int32_t* row_class, const float* g_sums, float* gpred, int B,
                           int R, int h, int w, float alpha, float gamma, void* stream);
+
+/* ---- assignment: the Hungarian matching of that loss on the device (csrc/lsa.hip, ABI 36) ------------------------------------------
+ * What loss.MaskFormerLoss.match_tables does on the host (HungarianAssigner: scipy.optimize.linear_sum_assignment per decoder layer
+ * and image, mmdet task_modules/assigners/hungarian_assigner.py:126-135), without leaving the stream:
+ *   cost [L, B, Q, K] fp32 and count_full [B, 256] fp32 as MaskFormerLoss.costs_all_classes returns them; per image the classes
+ *   present are the k < K with count_full[b][k] != 0; per (l, b) the rectangular linear sum assignment of cost[l][b][:, present]
+ *   (shortest augmenting paths, Crouse 2016, in fp64 on the fp32 costs; rows <= columns after orientation);
+ *   tgt_labels [L, B, Q] int64: class id of the matched column, K = no object;  row_class [B, L*Q] int32: the same, -1 = unmatched;
+ *   num_masks [L] fp32 = sum over the images of max(min(Q, n_present), 1);
+ *   status [1] int32: 0, or bit 0 = a label in K..254 is present (every num_masks is NaN), bit 1 = a non-finite cost (NaN, +Inf,
+ *   -Inf) in a present column (that problem's rows are unmatched, num_masks[l] is NaN).  A non-finite cost in an ABSENT column
+ *   is never read.
+ * EVERY element of the four outputs is written by every call (two launches, the first writes the status word): no fill precedes a
+ * replay inside a hipGraph.  Every loop of the solver has a structural bound; it cannot spin on any input.  Among equal minima
+ * the scan takes the column the textbook's list of unscanned columns yields (its first, or its last unassigned one): the tables are
+ * those of the host route bit for bit, on matrices with exactly tied totals too.
+ * Bounds: L, B, Q >= 1, L * B <= 2^20, Q <= S2F_LSA_MAX_QUERIES, 1 <= K <= S2F_LSA_MAX_CLASSES (255 is the ignored label).  One
+ * wave64 per problem, columns striped 4 per lane; the fp64 cost tile sits in LDS while Q * n_present <= 15 000 (Q = 100, K = 150)
+ * and is re-read as fp32 from L2 above that. */
+#define S2F_LSA_MAX_QUERIES 256
+#define S2F_LSA_MAX_CLASSES 254
+int s2f_lsa_tables(const float* cost, const float* count_full, int64_t* tgt_labels, int32_t* row_class, float* num_masks,
+                   int32_t* status, int L, int B, int Q, int K, void* stream);
+/* The same with flags (measurement only, tools/probe_lsa.py): S2F_LSA_TILE_L2 re-reads the fp32 costs from L2 for every problem
+ * instead of keeping the fp64 tile in LDS; the tables are the same. */
+#define S2F_LSA_TILE_L2 1
+int s2f_lsa_tables_ex(const float* cost, const float* count_full, int64_t* tgt_labels, int32_t* row_class, float* num_masks,
+                      int32_t* status, int L, int B, int Q, int K, int flags, void* stream);
 
 /* ---- a5 / a10: spike-driven (softmax-free) attention core --------------------------------------------
  * Replaces  kv = k^T @ v ; o = (q @ kv) * scale ; o.transpose(3,4).reshape(T,B,C,N)

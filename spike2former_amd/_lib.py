@@ -116,6 +116,8 @@ SIGNATURES = {
     "s2f_mask_loss_seg_partials": (_i64, [_i] * 4),
     "s2f_mask_loss_seg_fwd": (_i, [_p] * 5 + [_i] * 4 + [_f, _f, _p]),
     "s2f_mask_loss_seg_bwd": (_i, [_p] * 5 + [_i] * 4 + [_f, _f, _p]),
+    "s2f_lsa_tables": (_i, [_p] * 6 + [_i] * 4 + [_p]),
+    "s2f_lsa_tables_ex": (_i, [_p] * 6 + [_i] * 5 + [_p]),
     "s2f_spike_gemm_dw_bf16_split": (_i, [_p, _i64, _p, _p] + [_i] * 5 + [_p]),
     "s2f_spike_gemm_dw_grouped_split": (_i, [_p, _i, _i, _p]),
     "s2f_pgemm_dx_split": (_i, [_p, _p, _i64, _p] + [_i] * 5 + [_p]),

@@ -174,9 +174,28 @@ class GraphedHungarianStep:
         graph B : the losses from the tables (loss_from_tables: every shape is independent of the matching) + backward of the
                   whole model + packing of the gradients into the flat buffer
     Between the graphs the GPU idles for the copy, the assignment and one upload -- not for ~450 eager launches of the loss and
-    its backward as with GraphedSplitStep.  `__call__` returns the loss dictionary (static tensors, valid until the next call)."""
+    its backward as with GraphedSplitStep.  `__call__` returns the loss dictionary (static tensors, valid until the next call).
 
-    def __init__(self, model, example_input, example_seg, grad_buffer, warmup=3, ignore_index=None, optimizer=None):
+    assign="device": the assignment is a kernel of the step (ops.lsa_tables, csrc/lsa.hip: the same solver, fp64, one wave per
+    (layer, image)) and the host stop disappears --
+        single process : ONE hipGraph  reset + clear + forward + costs + assignment + losses + backward + packing (+ update);
+        process group  : graph A (... + assignment), at world size > 1 the `num_masks` all-reduce queued on the step's stream,
+                         graph B (losses ...) -- as the host route, without its synchronisation, copies and uploads.
+    `__call__` then never waits for the GPU.  What the host route raises for (a label >= num_classes in the map, non-finite costs)
+    arrives as a status word: every replay ORs the kernel's word into a STICKY device word and copies that to pinned memory at the
+    end of the last graph, so a later replay on clean inputs cannot erase it.  `check()` synchronises and raises; `__call__` raises,
+    before it touches the static inputs, when the word an earlier replay left has landed (a copy still in flight is seen on a
+    later call or by `check()`).  Raising clears the word (the error path waits for the stream).  A step with a set status has NaN
+    losses (the kernel writes num_masks = NaN), never quietly wrong ones -- and, with a captured optimizer, has already applied
+    them: validate label maps before training on them."""
+
+    def __init__(self, model, example_input, example_seg, grad_buffer, warmup=3, ignore_index=None, optimizer=None, assign="host"):
+        if assign not in ("host", "device"):
+            raise ValueError(f"assign must be 'host' or 'device', got {assign!r}")
+        if assign == "device" and not (example_input.is_cuda and example_seg.is_cuda):
+            raise RuntimeError("GraphedHungarianStep(assign='device') needs CUDA tensors: the device assignment is a HIP kernel and "
+                               "has no host fall-back")
+        self.assign = assign
         head = model.decode_head
         self.optimizer = optimizer          # train.FlatAdamW: captured at the end of graph B (single process; see GraphedStep)
         if optimizer is not None:
@@ -195,6 +214,10 @@ class GraphedHungarianStep:
         self.tgt_labels = torch.full((L, B, Q), self.crit.num_classes, dtype=torch.int64, device=dev)
         self.row_class = torch.full((B, L * Q), -1, dtype=torch.int32, device=dev)
         self.num_masks = torch.ones(L, dtype=torch.float32, device=dev)
+        if assign == "device":
+            del cls, masks
+            self._capture_device(params, dev, warmup)
+            return
         self.host_cost = torch.empty(L, B, Q, self.crit.num_classes, dtype=torch.float32).pin_memory()
         self.host_count = torch.empty(B, 256, dtype=torch.float32).pin_memory()
         self.host_tgt, self.host_rows, self.host_avg = (torch.empty(t.shape, dtype=t.dtype).pin_memory()
@@ -235,6 +258,89 @@ class GraphedHungarianStep:
         self._converted = ops.conversion_state()
         self._settings = ops.cfg.snapshot()          # see GraphedStep
 
+    def _capture_device(self, params, dev, warmup):
+        """assign="device": one graph (single process) or graph A | all-reduce | graph B (process group); no pinned cost buffer"""
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.sticky = torch.zeros(1, dtype=torch.int32, device=dev)          # OR of the status words since the last raise
+        self.host_status = torch.zeros(1, dtype=torch.int32).pin_memory()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                outs = self._forward()
+                self._tables(outs)
+                self._reduce_num_masks()
+                total = sum(self._losses(outs).values())
+                torch.autograd.grad(total, params, allow_unused=True)
+                ops.wgrad_join()
+                del outs, total
+        torch.cuda.current_stream().wait_stream(side)
+        ops.wgrad_drop()                                 # warm-up gradients are not packed: drop their deferred launches
+        ops.resplit_all(dev)
+        torch.cuda.synchronize()
+        import torch.distributed as dist
+        self.two_graphs = dist.is_available() and dist.is_initialized()
+        mode = "thread_local" if self.two_graphs else "global"
+
+        def tail(outs):
+            losses = self._losses(outs)
+            grads = torch.autograd.grad(sum(losses.values()), params, allow_unused=True)
+            ops.wgrad_join()
+            self.red.pack(grads)
+            if self.optimizer is not None:
+                self.optimizer.step(sync_hyper=False)
+            self.losses = {k: v.detach() for k, v in losses.items()}
+            self.sticky.bitwise_or_(self.status)
+            self.host_status.copy_(self.sticky, non_blocking=True)
+
+        self.graph = torch.cuda.CUDAGraph()
+        if self.two_graphs:
+            self.graph_tail = torch.cuda.CUDAGraph()
+            pool = torch.cuda.graph_pool_handle()
+            with torch.cuda.graph(self.graph, pool=pool, capture_error_mode=mode):
+                self.outs = self._forward()
+                self._tables(self.outs)
+            with torch.cuda.graph(self.graph_tail, pool=pool, capture_error_mode=mode):
+                tail(self.outs)
+        else:
+            with torch.cuda.graph(self.graph, capture_error_mode=mode):
+                self.outs = self._forward()
+                self._tables(self.outs)
+                tail(self.outs)
+        torch.cuda.synchronize()
+        self.sticky.zero_()                              # (whatever the warm-up on the example inputs left is not a replay's)
+        torch.cuda.synchronize()
+        self.host_status.zero_()
+        self._converted = ops.conversion_state()
+        self._settings = ops.cfg.snapshot()          # see GraphedStep
+
+    def _tables(self, outs):
+        """costs + device assignment into the static tables (and the status word)"""
+        with torch.no_grad():
+            cost, count = self.crit.costs_all_classes(outs[0], outs[1], self.static_seg)
+            self.crit.match_tables_device(cost, count, out=(self.tgt_labels, self.row_class, self.num_masks, self.status))
+
+    def _reduce_num_masks(self):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(self.num_masks.div_(dist.get_world_size()))          # reduce_mean (maskformer_head.py:459)
+
+    def _raise_for(self, word):
+        if word:
+            torch.cuda.current_stream().synchronize()      # the error path may wait: replays already queued have copied by now
+            word |= int(self.host_status[0])
+            self.sticky.zero_()
+            torch.cuda.current_stream().synchronize()
+            self.host_status.zero_()
+            self.crit.raise_for_status(word)
+
+    def check(self):
+        """assign="device": wait for the last replay and raise what the host route would have raised for its inputs (a label
+        >= num_classes in the map; non-finite matching costs).  The host route has raised inside `__call__` already."""
+        if self.assign == "device":
+            torch.cuda.current_stream().synchronize()
+            self._raise_for(int(self.host_status[0]))
+
     def _forward(self):
         reset_net(self.model)
         self.red.zero()
@@ -264,12 +370,22 @@ class GraphedHungarianStep:
 
     def __call__(self, x=None, seg=None):
         _check_settings(self._settings)
+        if self.assign == "device":
+            self._raise_for(int(self.host_status[0]))          # the word of an earlier replay, if it has landed; no wait
         if x is not None:
             self.static_in.copy_(x, non_blocking=True)
         if seg is not None:
             self.static_seg.copy_(self.crit.seg_as_u8(seg, self.ignore_index), non_blocking=True)
         if self.optimizer is not None:
             self.optimizer.sync_hyper()
+        if self.assign == "device":
+            self.graph.replay()
+            if self.two_graphs:
+                self._reduce_num_masks()
+                self.graph_tail.replay()
+            if self.optimizer is not None:
+                self.optimizer.mark_updated()
+            return self.losses
         self.graph_a.replay()
         torch.cuda.current_stream().synchronize()
         self._match()

@@ -195,6 +195,25 @@ class MaskFormerLoss:
                     avg[l] += 1
         return tgt, row_class.reshape(B, L * Q), avg
 
+    STATUS_LABEL, STATUS_NONFINITE = 1, 2          # the bits of ops.lsa_tables' status word
+
+    def match_tables_device(self, cost, count_full, out=None):
+        """Device: `match_tables` without the host -- cost [L, B, Q, K], count_full [B, 256] (CUDA tensors) -> (tgt_labels, row_class,
+        num_masks, status) as device tensors, no copy and no synchronisation (ops.lsa_tables: the same shortest-augmenting-path
+        solver in fp64, one wave per (layer, image)).  `status` [1] int32 is what the host route raises for; hand it to
+        `raise_for_status` once it has been read."""
+        from . import ops
+        return ops.lsa_tables(cost, count_full, self.num_classes, out=out)
+
+    @classmethod
+    def raise_for_status(cls, status):
+        """status: the (host) value of the word `match_tables_device` wrote -> the ValueError of the host route, if any"""
+        status = int(status)
+        if status & cls.STATUS_LABEL:
+            raise ValueError("semantic map holds labels >= num_classes other than the ignored one")
+        if status & cls.STATUS_NONFINITE:
+            raise ValueError("matrix contains invalid numeric entries")
+
     def loss_from_tables(self, all_cls_scores, all_mask_preds, seg_u8, tgt_labels, row_class, num_masks):
         """Device: the loss dictionary from the three tables of `match_tables` (num_masks [L]: already averaged over the ranks).
         Same formulas as `loss_by_feat`, all layers at once."""
@@ -229,10 +248,26 @@ class MaskFormerLoss:
             cache[dev] = torch.tensor(self.cls.class_weight, dtype=torch.float32, device=dev)
         return cache[dev]
 
-    def loss_semantic(self, all_cls_scores, all_mask_preds, segs, ignore_index=255, reduce_fn=None):
+    def loss_semantic(self, all_cls_scores, all_mask_preds, segs, ignore_index=255, reduce_fn=None, assign="host"):
         """`loss_by_feat` for targets given as semantic maps [B, H, W] (what mmseg's head builds its instances from): same
-        dictionary, one device -> host copy (the costs), the assignment, one upload of the tables."""
+        dictionary, one device -> host copy (the costs), the assignment, one upload of the tables.
+        assign="device": the assignment runs on the GPU (`match_tables_device`); nothing but its status word crosses to the host,
+        after the loss has been queued (same ValueErrors as the host route; non-finite costs: scipy's text)."""
+        if assign not in ("host", "device"):
+            raise ValueError(f"assign must be 'host' or 'device', got {assign!r}")
         seg_u8 = self.seg_as_u8(segs, ignore_index)
+        if assign == "device":
+            if not (all_cls_scores.is_cuda and all_mask_preds.is_cuda and seg_u8.is_cuda):
+                raise RuntimeError("loss_semantic(assign='device') needs CUDA tensors: the device assignment is a HIP kernel and has "
+                                   "no host fall-back (use assign='host')")
+            with torch.no_grad():
+                cost, count = self.costs_all_classes(all_cls_scores, all_mask_preds, seg_u8)
+                tgt, row_class, num_masks, status = self.match_tables_device(cost, count)
+                if reduce_fn is not None:
+                    num_masks = reduce_fn(num_masks)
+            losses = self.loss_from_tables(all_cls_scores, all_mask_preds, seg_u8, tgt, row_class, num_masks)
+            self.raise_for_status(status.item())
+            return losses
         with torch.no_grad():
             cost, count = self.costs_all_classes(all_cls_scores, all_mask_preds, seg_u8)
             cost, count = cost.cpu().numpy(), count.cpu().numpy()

@@ -512,6 +512,44 @@ def mask_cost_bins(pred, seg_small, K, alpha, gamma, eps):
     return out
 
 
+LSA_MAX_QUERIES, LSA_MAX_CLASSES = 256, 254          # include/s2f.h S2F_LSA_MAX_QUERIES / S2F_LSA_MAX_CLASSES
+
+
+def lsa_tables(cost, count_full, K, out=None, tile_l2=False):
+    """The Hungarian assignment of the semantic-map loss on the device (s2f.h s2f_lsa_tables): cost [L, B, Q, K] fp32 and
+    count_full [B, 256] fp32 as MaskFormerLoss.costs_all_classes returns them -> (tgt_labels [L, B, Q] int64, row_class [B, L*Q]
+    int32, num_masks [L] fp32, status [1] int32) -- the three tables of MaskFormerLoss.match_tables plus a status word (bit 0: a
+    label in K..254 is present, bit 1: a non-finite cost in a present column; num_masks is NaN then).  `out`: those four tensors
+    to write into (static buffers of a captured step); every element is written.  No autograd; nothing synchronises.
+    `tile_l2` (measurement only, tools/probe_lsa.py): re-read the costs from L2 instead of keeping the fp64 tile in LDS."""
+    if not (cost.is_cuda and count_full.is_cuda):
+        raise RuntimeError("ops.lsa_tables runs on the GPU only (HIP kernel, no host fall-back); got a CPU tensor -- "
+                           "the host route is MaskFormerLoss.match_tables (assign='host')")
+    if cost.dtype != torch.float32 or count_full.dtype != torch.float32:
+        raise RuntimeError(f"ops.lsa_tables takes fp32 costs and counts; got {cost.dtype}, {count_full.dtype}")
+    if cost.dim() != 4 or cost.shape[3] != K:
+        raise ValueError(f"cost [L, B, Q, K = {K}], got {tuple(cost.shape)}")
+    L, B, Q = cost.shape[:3]
+    if tuple(count_full.shape) != (B, 256) or count_full.device != cost.device:
+        raise ValueError(f"count_full [B = {B}, 256] on {cost.device}, got {tuple(count_full.shape)} on {count_full.device}")
+    cost, count_full = cost.detach().contiguous(), count_full.detach().contiguous()
+    dev = cost.device
+    if out is None:
+        out = (torch.empty(L, B, Q, dtype=torch.int64, device=dev), torch.empty(B, L * Q, dtype=torch.int32, device=dev),
+               torch.empty(L, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+    tgt, rows, num_masks, status = out
+    for t, shape, dtype in ((tgt, (L, B, Q), torch.int64), (rows, (B, L * Q), torch.int32), (num_masks, (L,), torch.float32),
+                            (status, (1,), torch.int32)):
+        if not (t.device == dev and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous()):
+            raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    args = (_ptr(cost), _ptr(count_full), _ptr(tgt), _ptr(rows), _ptr(num_masks), _ptr(status), L, B, Q, int(K))
+    if tile_l2:
+        check(lib.s2f_lsa_tables_ex(*args, 1, _stream()), "s2f_lsa_tables_ex")          # S2F_LSA_TILE_L2
+    else:
+        check(lib.s2f_lsa_tables(*args, _stream()), "s2f_lsa_tables")
+    return tgt, rows, num_masks, status
+
+
 class _MaskLossSeg(torch.autograd.Function):
     """sums[(b, r)] = {sum s t, sum s, sum t, sum focal} of the 2x up-sampled logits pred[b, r] against  seg[b] == row_class[b, r]
     (rows with row_class < 0: zeros, zero gradient); s2f.h s2f_mask_loss_seg_fwd/bwd."""
