@@ -1710,6 +1710,46 @@ int check_shape(const char* who, int64_t N, int64_t C, int64_t L) {
   return S2F_OK;
 }
 
+// The neuron variants of every forward kernel that are built: 5 of the 8 (LIF, HAS_V, YB) combinations -- without a neuron
+// (no y) there is no membrane to read and no spike format to choose.
+struct FwdVariant {
+  bool lif, has_v, yb;
+};
+constexpr FwdVariant kFwdVariants[] = {
+    {false, false, false},  // BatchNorm only: u_out, no neuron
+    {true, false, false},   // neuron from rest (first time step), fp32 spikes
+    {true, false, true},    // neuron from rest, bf16 spikes
+    {true, true, false},    // neuron with a membrane input, fp32 spikes
+    {true, true, true},     // neuron with a membrane input, bf16 spikes
+};
+template <class F>
+void for_fwd_variant(const float* y, const float* v_in, int y_bf16, const F& launch) {
+  s2f_dispatch<kFwdVariants>(
+      [&](const FwdVariant& e) {
+        return y ? (e.lif && e.has_v == (v_in != nullptr) && e.yb == (y_bf16 != 0)) : !e.lif;
+      },
+      launch);
+}
+
+// The incoming-gradient combinations of every backward kernel: 7 of 8 -- the launcher refuses a call without any gradient.
+struct BwdGrads {
+  bool gu, gy, gv;
+};
+constexpr BwdGrads kBwdGrads[] = {
+    {false, false, true},  // membrane gradient only (last time step of a layer whose spikes are unused)
+    {false, true, false},  // spike gradient only
+    {false, true, true},   // spike + membrane gradient (a neuron layer inside the time loop)
+    {true, false, false},  // BatchNorm only
+    {true, false, true},   // u + membrane gradient
+    {true, true, false},   // u + spike gradient
+    {true, true, true},    // all three
+};
+template <class F>
+void for_bwd_grads(const float* g_u, const float* g_y, const float* g_v, const F& launch) {
+  s2f_dispatch<kBwdGrads>(
+      [&](const BwdGrads& e) { return e.gu == (g_u != nullptr) && e.gy == (g_y != nullptr) && e.gv == (g_v != nullptr); }, launch);
+}
+
 }  // namespace
 
 extern "C" int s2f_bn_single_pass(int64_t N, int64_t C, int64_t L) {
@@ -1764,7 +1804,6 @@ static int bn_act_fwd_impl(const float* z, const float* conv_bias, const double*
   S2F_REQUIRE(z && stat_out && gamma && beta, S2F_EINVAL, "s2f_bn_act_fwd: null z/stat/gamma/beta");
   S2F_REQUIRE(!bn2.gamma || (training && sums == nullptr && single_pass_ok(N, C, L) && bn2.beta), S2F_EINVAL,
               "s2f_bn2_act_fwd: the BatchNorm pair runs on the single-pass kernels only (training mode, s2f_bn2_fused_ok)");
-  constexpr bool first_launch = true;
   // sums given for a shape that could go single-pass: the caller already has the statistics (a producer's epilogue, or a probe) --
   // take the apply path, which is not tied to one workgroup per channel
   const bool single = training && sums == nullptr && single_pass_ok(N, C, L);
@@ -1789,119 +1828,56 @@ static int bn_act_fwd_impl(const float* z, const float* conv_bias, const double*
   const float unbias = count > 1 ? (float)(count / (count - 1.0)) : 1.0f;
   if (training && mid_rows_ok(N, C, L)) {
     // (always, given statistics or not: the mask layout of this shape is the per-channel one, which the backward reads)
-#define S2F_BN_MID(LIFV, HASV, YBV)                                                                                      \
-  S2F_LAUNCH(true, true, (bn_mid_fwd_kernel<LIFV, HASV, YBV>), dim3((unsigned)C), dim3(mid_rows_threads(N, L)), 0, s, z, conv_bias, \
-             stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, (int)N, (int)C,   \
-             (int)L, inv_count, unbias, momentum, eps, vth, (float)D)
-    if (y == nullptr)
-      S2F_BN_MID(false, false, false);
-    else if (v_in == nullptr) {
-      if (y_bf16)
-        S2F_BN_MID(true, false, true);
-      else
-        S2F_BN_MID(true, false, false);
-    } else {
-      if (y_bf16)
-        S2F_BN_MID(true, true, true);
-      else
-        S2F_BN_MID(true, true, false);
-    }
-#undef S2F_BN_MID
+    for_fwd_variant(y, v_in, y_bf16, [&](auto i) {
+      constexpr FwdVariant V = kFwdVariants[i];
+      S2F_LAUNCH(true, true, (bn_mid_fwd_kernel<V.lif, V.has_v, V.yb>), dim3((unsigned)C), dim3(mid_rows_threads(N, L)), 0, s, z,
+                 conv_bias, stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st,
+                 (int)N, (int)C, (int)L, inv_count, unbias, momentum, eps, vth, (float)D);
+    });
     return s2f_check_launch("s2f_bn_act_fwd");
   }
   if (training && small_rows_ok(N, C, L)) {
     // (always, given statistics or not: the mask layout of this shape is the short-row one, which the backward reads)
-#define S2F_BN_SMALL(LIFV, HASV, YBV)                                                                                    \
-  S2F_LAUNCH(true, true, (bn_small_fwd_kernel<LIFV, HASV, YBV>), dim3((unsigned)C), dim3(64), 0, s, z, conv_bias, stat_out, \
-             running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, (int)N, (int)C,      \
-             (int)L, inv_count, unbias, momentum, eps, vth, (float)D)
-    if (y == nullptr)
-      S2F_BN_SMALL(false, false, false);
-    else if (v_in == nullptr) {
-      if (y_bf16)
-        S2F_BN_SMALL(true, false, true);
-      else
-        S2F_BN_SMALL(true, false, false);
-    } else {
-      if (y_bf16)
-        S2F_BN_SMALL(true, true, true);
-      else
-        S2F_BN_SMALL(true, true, false);
-    }
-#undef S2F_BN_SMALL
+    for_fwd_variant(y, v_in, y_bf16, [&](auto i) {
+      constexpr FwdVariant V = kFwdVariants[i];
+      S2F_LAUNCH(true, true, (bn_small_fwd_kernel<V.lif, V.has_v, V.yb>), dim3((unsigned)C), dim3(64), 0, s, z, conv_bias,
+                 stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, (int)N,
+                 (int)C, (int)L, inv_count, unbias, momentum, eps, vth, (float)D);
+    });
     return s2f_check_launch("s2f_bn_act_fwd");
   }
   if (single) {
-    const dim3 fgrid((unsigned)C), fblock(single_pass_threads(N, L));
-#define S2F_BN_FUSED(LIFV, HASV, YBV)                                                                                    \
-  do {                                                                                                                   \
-    if (bn2.gamma)                                                                                                       \
-      S2F_LAUNCH(true, true, (bn_fused_fwd_kernel<LIFV, HASV, YBV, true>), fgrid, fblock, 0, s, z, conv_bias, stat_out,    \
-                 running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, (int)N, (int)C,  \
-                 (int)L, inv_count, unbias, momentum, eps, vth, (float)D, bn2);                                          \
-    else                                                                                                                 \
-      S2F_LAUNCH(true, true, (bn_fused_fwd_kernel<LIFV, HASV, YBV>), fgrid, fblock, 0, s, z, conv_bias, stat_out,          \
-                 running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, (int)N, (int)C,  \
-                 (int)L, inv_count, unbias, momentum, eps, vth, (float)D, bn2);                                          \
-  } while (0)
-    if (y == nullptr)
-      S2F_BN_FUSED(false, false, false);
-    else if (v_in == nullptr) {
-      if (y_bf16)
-        S2F_BN_FUSED(true, false, true);
-      else
-        S2F_BN_FUSED(true, false, false);
-    } else {
-      if (y_bf16)
-        S2F_BN_FUSED(true, true, true);
-      else
-        S2F_BN_FUSED(true, true, false);
-    }
-#undef S2F_BN_FUSED
+    for_fwd_variant(y, v_in, y_bf16, [&](auto i) {
+      constexpr FwdVariant V = kFwdVariants[i];
+      s2f_dispatch_bool(bn2.gamma != nullptr, [&](auto pair) {
+        S2F_LAUNCH(true, true, (bn_fused_fwd_kernel<V.lif, V.has_v, V.yb, pair.value>), dim3((unsigned)C),
+                   dim3(single_pass_threads(N, L)), 0, s, z, conv_bias, stat_out, running_mean, running_var, nbt, gamma, beta,
+                   residual, u_out, v_in, y, v_out, mask, st, (int)N, (int)C, (int)L, inv_count, unbias, momentum, eps, vth,
+                   (float)D, bn2);
+      });
+    });
     return s2f_check_launch("s2f_bn_act_fwd");
   }
-  const bool rows = rows_ok(N, C, L, D), aligned = rows_aligned(total, L);
   const size_t lds = 3 * C * sizeof(float) + 64;
-#define S2F_BN_ROWS_FWD(LIFV, HASV, YBV, AL)                                                                              \
-  do {                                                                                                                  \
-    uint32_t chunk;                                                                                                     \
-    const uint32_t ntiles = (uint32_t)((total + 255) >> 8);                                                             \
-    const int rgrid = grid_rows<bn_apply_rows_kernel<LIFV, HASV, YBV, AL>>(ntiles, lds, chunk, 8);                         \
-    S2F_LAUNCH(first_launch, true, (bn_apply_rows_kernel<LIFV, HASV, YBV, AL>), dim3(rgrid), block, lds, s, z, conv_bias, \
-               sums, stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st,   \
-               total, ntiles, (int)C, (uint32_t)L, chunk, inv_count, unbias, momentum, eps, training, vth, (float)D);    \
-  } while (0)
-#define S2F_BN_APPLY(LIFV, HASV, YBV)                                                                                   \
-  do {                                                                                                                  \
-    if (rows && aligned) {                                                                                              \
-      S2F_BN_ROWS_FWD(LIFV, HASV, YBV, true);                                                                           \
-    } else if (rows) {                                                                                                  \
-      S2F_BN_ROWS_FWD(LIFV, HASV, YBV, false);                                                                          \
-    } else if (anyl) {                                                                                                  \
-      S2F_LAUNCH(first_launch, true, (bn_apply_kernel<LIFV, HASV, YBV, true>), grid, block, lds, s, z, conv_bias, sums, \
-                 stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st,      \
-                 total, (int)C, (int)L, inv_count, unbias, momentum, eps, training, vth, (float)D);                     \
-    } else {                                                                                                            \
-      S2F_LAUNCH(first_launch, true, (bn_apply_kernel<LIFV, HASV, YBV>), grid, block, lds, s, z, conv_bias, sums,        \
-                 stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st,      \
-                 total, (int)C, (int)L, inv_count, unbias, momentum, eps, training, vth, (float)D);                     \
-    }                                                                                                                   \
-  } while (0)
-  if (y == nullptr)
-    S2F_BN_APPLY(false, false, false);
-  else if (v_in == nullptr) {
-    if (y_bf16)
-      S2F_BN_APPLY(true, false, true);
-    else
-      S2F_BN_APPLY(true, false, false);
-  } else {
-    if (y_bf16)
-      S2F_BN_APPLY(true, true, true);
-    else
-      S2F_BN_APPLY(true, true, false);
-  }
-#undef S2F_BN_APPLY
-#undef S2F_BN_ROWS_FWD
+  for_fwd_variant(y, v_in, y_bf16, [&](auto i) {
+    constexpr FwdVariant V = kFwdVariants[i];
+    if (rows_ok(N, C, L, D)) {
+      s2f_dispatch_bool(rows_aligned(total, L), [&](auto al) {
+        uint32_t chunk;
+        const uint32_t ntiles = (uint32_t)((total + 255) >> 8);
+        const int rgrid = grid_rows<bn_apply_rows_kernel<V.lif, V.has_v, V.yb, al.value>>(ntiles, lds, chunk, 8);
+        S2F_LAUNCH(true, true, (bn_apply_rows_kernel<V.lif, V.has_v, V.yb, al.value>), dim3(rgrid), block, lds, s, z, conv_bias,
+                   sums, stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, total,
+                   ntiles, (int)C, (uint32_t)L, chunk, inv_count, unbias, momentum, eps, training, vth, (float)D);
+      });
+    } else {
+      s2f_dispatch_bool(anyl, [&](auto al) {
+        S2F_LAUNCH(true, true, (bn_apply_kernel<V.lif, V.has_v, V.yb, al.value>), grid, block, lds, s, z, conv_bias, sums,
+                   stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, total,
+                   (int)C, (int)L, inv_count, unbias, momentum, eps, training, vth, (float)D);
+      });
+    }
+  });
   return s2f_check_launch("s2f_bn_act_fwd");
 }
 
@@ -1948,119 +1924,66 @@ static int bn_act_bwd_impl(const float* z, const float* conv_bias, const float* 
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t total = N * C * L;
+  const double inv_count = 1.0 / ((double)N * (double)L);
   if (training && mid_rows_ok(N, C, L)) {
     S2F_REQUIRE(gzs == nullptr && gz, S2F_EINVAL, "s2f_bn_act_bwd_split: rows that are not whole tiles have no bf16-plane form");
-#define S2F_BN_MB(A, B, Cc)                                                                                               \
-  S2F_LAUNCH(true, true, (bn_mid_bwd_kernel<A, B, Cc>), dim3((unsigned)C), dim3(mid_rows_threads(N, L)), 0, s, z, conv_bias, stat, \
-             gamma, g_u, g_y, g_v, mask, gz, g_residual, dgamma, dbeta, (int)N, (int)C, (int)L, 1.0 / ((double)N * (double)L), vth, \
-             (float)D)
-    switch ((g_u ? 4 : 0) | (g_y ? 2 : 0) | (g_v ? 1 : 0)) {
-      case 1: S2F_BN_MB(false, false, true); break;
-      case 2: S2F_BN_MB(false, true, false); break;
-      case 3: S2F_BN_MB(false, true, true); break;
-      case 4: S2F_BN_MB(true, false, false); break;
-      case 5: S2F_BN_MB(true, false, true); break;
-      case 6: S2F_BN_MB(true, true, false); break;
-      default: S2F_BN_MB(true, true, true); break;
-    }
-#undef S2F_BN_MB
+    for_bwd_grads(g_u, g_y, g_v, [&](auto i) {
+      constexpr BwdGrads G = kBwdGrads[i];
+      S2F_LAUNCH(true, true, (bn_mid_bwd_kernel<G.gu, G.gy, G.gv>), dim3((unsigned)C), dim3(mid_rows_threads(N, L)), 0, s, z,
+                 conv_bias, stat, gamma, g_u, g_y, g_v, mask, gz, g_residual, dgamma, dbeta, (int)N, (int)C, (int)L, inv_count,
+                 vth, (float)D);
+    });
     return s2f_check_launch("s2f_bn_act_bwd");
   }
   if (training && small_rows_ok(N, C, L)) {
     S2F_REQUIRE(gzs == nullptr && gz, S2F_EINVAL, "s2f_bn_act_bwd_split: short rows (N * L <= 2048) have no bf16-plane form");
-#define S2F_BN_SB(A, B, Cc)                                                                                               \
-  S2F_LAUNCH(true, true, (bn_small_bwd_kernel<A, B, Cc>), dim3((unsigned)C), dim3(64), 0, s, z, conv_bias, stat, gamma, g_u, \
-             g_y, g_v, mask, gz, g_residual, dgamma, dbeta, (int)N, (int)C, (int)L, 1.0 / ((double)N * (double)L), vth,    \
-             (float)D)
-    switch ((g_u ? 4 : 0) | (g_y ? 2 : 0) | (g_v ? 1 : 0)) {
-      case 1: S2F_BN_SB(false, false, true); break;
-      case 2: S2F_BN_SB(false, true, false); break;
-      case 3: S2F_BN_SB(false, true, true); break;
-      case 4: S2F_BN_SB(true, false, false); break;
-      case 5: S2F_BN_SB(true, false, true); break;
-      case 6: S2F_BN_SB(true, true, false); break;
-      default: S2F_BN_SB(true, true, true); break;
-    }
-#undef S2F_BN_SB
+    for_bwd_grads(g_u, g_y, g_v, [&](auto i) {
+      constexpr BwdGrads G = kBwdGrads[i];
+      S2F_LAUNCH(true, true, (bn_small_bwd_kernel<G.gu, G.gy, G.gv>), dim3((unsigned)C), dim3(64), 0, s, z, conv_bias, stat,
+                 gamma, g_u, g_y, g_v, mask, gz, g_residual, dgamma, dbeta, (int)N, (int)C, (int)L, inv_count, vth, (float)D);
+    });
     return s2f_check_launch("s2f_bn_act_bwd");
   }
   if (single) {
-#define S2F_BN_FB(A, B, Cc)                                                                                               \
-  do {                                                                                                                    \
-    if (bn2.gamma)                                                                                                        \
-      S2F_LAUNCH(true, true, (bn_fused_bwd_kernel<A, B, Cc, true>), dim3((unsigned)C), dim3(single_pass_threads(N, L)), 0,  \
-                 s, z, conv_bias, stat, gamma, g_u, g_y, g_v, mask, gz, g_residual, dgamma, dbeta, (int)N, (int)C,        \
-                 (int)L, 1.0 / ((double)N * (double)L), vth, (float)D, gzs, bn2, g_y2);                                   \
-    else                                                                                                                  \
-      S2F_LAUNCH(true, true, (bn_fused_bwd_kernel<A, B, Cc>), dim3((unsigned)C), dim3(single_pass_threads(N, L)), 0, s, z,  \
-                 conv_bias, stat, gamma, g_u, g_y, g_v, mask, gz, g_residual, dgamma, dbeta, (int)N, (int)C, (int)L,      \
-                 1.0 / ((double)N * (double)L), vth, (float)D, gzs, bn2, g_y2);                                           \
-  } while (0)
-    const int combo = (g_u ? 4 : 0) | (g_y ? 2 : 0) | (g_v ? 1 : 0);
-    switch (combo) {
-      case 1: S2F_BN_FB(false, false, true); break;
-      case 2: S2F_BN_FB(false, true, false); break;
-      case 3: S2F_BN_FB(false, true, true); break;
-      case 4: S2F_BN_FB(true, false, false); break;
-      case 5: S2F_BN_FB(true, false, true); break;
-      case 6: S2F_BN_FB(true, true, false); break;
-      default: S2F_BN_FB(true, true, true); break;
-    }
-#undef S2F_BN_FB
+    for_bwd_grads(g_u, g_y, g_v, [&](auto i) {
+      constexpr BwdGrads G = kBwdGrads[i];
+      s2f_dispatch_bool(bn2.gamma != nullptr, [&](auto pair) {
+        S2F_LAUNCH(true, true, (bn_fused_bwd_kernel<G.gu, G.gy, G.gv, pair.value>), dim3((unsigned)C),
+                   dim3(single_pass_threads(N, L)), 0, s, z, conv_bias, stat, gamma, g_u, g_y, g_v, mask, gz, g_residual, dgamma,
+                   dbeta, (int)N, (int)C, (int)L, inv_count, vth, (float)D, gzs, bn2, g_y2);
+      });
+    });
     return s2f_check_launch("s2f_bn_act_bwd");
   }
   if (rows_ok(N, C, L, D)) {
     int slice;
     const int S = pick_slices_rows((int)C, (int)L, slice);
     const uint32_t ntiles = (uint32_t)((total + 255) >> 8);
-    const double inv_count = 1.0 / ((double)N * (double)L);
-    const bool aligned = rows_aligned(total, L);
-#define S2F_BN_ROWS_APPLY(A, B, Cc, AL)                                                                                  \
-  do {                                                                                                                   \
-    uint32_t chunk;                                                                                                      \
-    const int rgrid = grid_rows<bn_bwd_apply_rows_kernel<A, B, Cc, AL>>(ntiles, 0, chunk, 4);                               \
-    S2F_LAUNCH(false, true, (bn_bwd_apply_rows_kernel<A, B, Cc, AL>), dim3(rgrid), dim3(kBlock), 0, s, z, conv_bias, stat, \
-               gamma, g_u, g_y, g_v, mask, sums_zeroed, gz, g_residual, dgamma, dbeta, total, ntiles, (int)C, (uint32_t)L, \
-               chunk, inv_count, training, vth, (float)D, gzs, g_y2);                                                    \
-  } while (0)
-#define S2F_BN_ROWS_BWD(A, B, Cc)                                                                                        \
-  do {                                                                                                                   \
-    S2F_LAUNCH(true, false, (bn_bwd_reduce_rows_kernel<A, B, Cc>), dim3((unsigned)C, S), dim3(kBlock), 0, s, z, conv_bias, \
-               stat, g_u, g_y, g_v, mask, sums_zeroed, (int)N, (int)C, (int)L, slice, vth, (float)D, g_y2);               \
-    if (aligned)                                                                                                         \
-      S2F_BN_ROWS_APPLY(A, B, Cc, true);                                                                                 \
-    else                                                                                                                 \
-      S2F_BN_ROWS_APPLY(A, B, Cc, false);                                                                                \
-  } while (0)
-    switch ((g_u ? 4 : 0) | (g_y ? 2 : 0) | (g_v ? 1 : 0)) {
-      case 1: S2F_BN_ROWS_BWD(false, false, true); break;
-      case 2: S2F_BN_ROWS_BWD(false, true, false); break;
-      case 3: S2F_BN_ROWS_BWD(false, true, true); break;
-      case 4: S2F_BN_ROWS_BWD(true, false, false); break;
-      case 5: S2F_BN_ROWS_BWD(true, false, true); break;
-      case 6: S2F_BN_ROWS_BWD(true, true, false); break;
-      default: S2F_BN_ROWS_BWD(true, true, true); break;
-    }
-#undef S2F_BN_ROWS_BWD
-#undef S2F_BN_ROWS_APPLY
+    for_bwd_grads(g_u, g_y, g_v, [&](auto i) {
+      constexpr BwdGrads G = kBwdGrads[i];
+      S2F_LAUNCH(true, false, (bn_bwd_reduce_rows_kernel<G.gu, G.gy, G.gv>), dim3((unsigned)C, S), dim3(kBlock), 0, s, z,
+                 conv_bias, stat, g_u, g_y, g_v, mask, sums_zeroed, (int)N, (int)C, (int)L, slice, vth, (float)D, g_y2);
+      s2f_dispatch_bool(rows_aligned(total, L), [&](auto al) {
+        uint32_t chunk;
+        const int rgrid = grid_rows<bn_bwd_apply_rows_kernel<G.gu, G.gy, G.gv, al.value>>(ntiles, 0, chunk, 4);
+        S2F_LAUNCH(false, true, (bn_bwd_apply_rows_kernel<G.gu, G.gy, G.gv, al.value>), dim3(rgrid), dim3(kBlock), 0, s, z,
+                   conv_bias, stat, gamma, g_u, g_y, g_v, mask, sums_zeroed, gz, g_residual, dgamma, dbeta, total, ntiles,
+                   (int)C, (uint32_t)L, chunk, inv_count, training, vth, (float)D, gzs, g_y2);
+      });
+    });
     return s2f_check_launch("s2f_bn_act_bwd");
   }
   int slice;
   const int S = pick_slices((int)C, (int)L, slice);
-  if (L & 3) {
-    S2F_REQUIRE(gzs == nullptr, S2F_EINVAL, "s2f_bn_act_bwd_split: rows of L %% 4 != 0 elements have no bf16-plane form");
-    S2F_LAUNCH(true, false, bn_bwd_reduce_any_kernel, dim3((unsigned)C, S), dim3(kBlock), 0, s, z, conv_bias, stat, g_u, g_y,
-               g_v, mask, sums_zeroed, (int)N, (int)C, (int)L, slice, vth, (float)D);
-    S2F_LAUNCH(false, true, bn_bwd_apply_kernel<true>, dim3(grid_flat(total)), dim3(kBlock), 2 * C * sizeof(float), s, z,
+  const bool anyl = (L & 3) != 0;
+  S2F_REQUIRE(!anyl || gzs == nullptr, S2F_EINVAL, "s2f_bn_act_bwd_split: rows of L %% 4 != 0 elements have no bf16-plane form");
+  S2F_LAUNCH(true, false, anyl ? bn_bwd_reduce_any_kernel : bn_bwd_reduce_kernel, dim3((unsigned)C, S), dim3(kBlock), 0, s, z,
+             conv_bias, stat, g_u, g_y, g_v, mask, sums_zeroed, (int)N, (int)C, (int)L, slice, vth, (float)D);
+  s2f_dispatch_bool(anyl, [&](auto al) {
+    S2F_LAUNCH(false, true, bn_bwd_apply_kernel<al.value>, dim3(grid_flat(total)), dim3(kBlock), 2 * C * sizeof(float), s, z,
                conv_bias, stat, gamma, g_u, g_y, g_v, mask, sums_zeroed, gz, g_residual, dgamma, dbeta, total, (int)C, (int)L,
-               1.0 / ((double)N * (double)L), training, vth, (float)D, gzs);
-    return s2f_check_launch("s2f_bn_act_bwd");
-  }
-  S2F_LAUNCH(true, false, bn_bwd_reduce_kernel, dim3((unsigned)C, S), dim3(kBlock), 0, s, z, conv_bias, stat, g_u, g_y, g_v,
-                     mask, sums_zeroed, (int)N, (int)C, (int)L, slice, vth, (float)D);
-  S2F_LAUNCH(false, true, bn_bwd_apply_kernel<false>, dim3(grid_flat(total)), dim3(kBlock), 2 * C * sizeof(float), s, z, conv_bias, stat, gamma, g_u, g_y,
-                     g_v, mask, sums_zeroed, gz, g_residual, dgamma, dbeta, total, (int)C, (int)L,
-                     1.0 / ((double)N * (double)L), training, vth, (float)D, gzs);
+               inv_count, training, vth, (float)D, gzs);
+  });
   return s2f_check_launch("s2f_bn_act_bwd");
 }
 

@@ -353,6 +353,13 @@ int check(const char* who, int N, int C, int H, int W, int K, int pad, int& Ho, 
   return S2F_OK;
 }
 
+// The stencil sizes every depthwise kernel is built for (check() admits no other K).
+constexpr int kStencilSizes[] = {3, 5, 7};
+template <class F>
+void for_stencil_size(int K, const F& launch) {
+  s2f_dispatch<kStencilSizes>([&](int k) { return k == K; }, launch);
+}
+
 template <typename TX>
 void launch_stencil_epi(int K, dim3 grid, hipStream_t s, const TX* x, const float* w, const float* border, int C, int H, int W, int Ho,
                         int Wo, int pad, int tiles_x, DwEpi ep) {
@@ -362,15 +369,10 @@ void launch_stencil_epi(int K, dim3 grid, hipStream_t s, const TX* x, const floa
                        (float*)nullptr, C, H, W, Ho, Wo, pad, wx, ep);
     return;
   }
-  if (K == 3)
-    hipLaunchKernelGGL((dw_stencil_kernel<3, false, TX, true>), grid, dim3(256), 0, s, x, w, border, (float*)nullptr, C, H, W, Ho, Wo,
-                       pad, tiles_x, ep);
-  else if (K == 5)
-    hipLaunchKernelGGL((dw_stencil_kernel<5, false, TX, true>), grid, dim3(256), 0, s, x, w, border, (float*)nullptr, C, H, W, Ho, Wo,
-                       pad, tiles_x, ep);
-  else
-    hipLaunchKernelGGL((dw_stencil_kernel<7, false, TX, true>), grid, dim3(256), 0, s, x, w, border, (float*)nullptr, C, H, W, Ho, Wo,
-                       pad, tiles_x, ep);
+  for_stencil_size(K, [&](auto i) {
+    hipLaunchKernelGGL((dw_stencil_kernel<kStencilSizes[i], false, TX, true>), grid, dim3(256), 0, s, x, w, border, (float*)nullptr,
+                       C, H, W, Ho, Wo, pad, tiles_x, ep);
+  });
 }
 
 template <bool FLIP, typename TX>
@@ -387,12 +389,10 @@ void launch_stencil(int K, dim3 grid, hipStream_t s, const TX* x, const float* w
                        Wo, pad, wx, DwEpi{});
     return;
   }
-  if (K == 3)
-    hipLaunchKernelGGL((dw_stencil_kernel<3, FLIP, TX>), grid, dim3(256), 0, s, x, w, border, y, C, H, W, Ho, Wo, pad, tiles_x, DwEpi{});
-  else if (K == 5)
-    hipLaunchKernelGGL((dw_stencil_kernel<5, FLIP, TX>), grid, dim3(256), 0, s, x, w, border, y, C, H, W, Ho, Wo, pad, tiles_x, DwEpi{});
-  else
-    hipLaunchKernelGGL((dw_stencil_kernel<7, FLIP, TX>), grid, dim3(256), 0, s, x, w, border, y, C, H, W, Ho, Wo, pad, tiles_x, DwEpi{});
+  for_stencil_size(K, [&](auto i) {
+    hipLaunchKernelGGL((dw_stencil_kernel<kStencilSizes[i], FLIP, TX>), grid, dim3(256), 0, s, x, w, border, y, C, H, W, Ho, Wo, pad,
+                       tiles_x, DwEpi{});
+  });
 }
 
 }  // namespace
@@ -450,9 +450,7 @@ extern "C" int s2f_dwconv_bwd_input(const float* gy, const float* w, float* gx, 
 
 extern "C" int s2f_dwconv_bwd_weight(const void* x_in, const float* border, const float* gy, float* gw, int N, int C, int H,
                                      int W, int K, int pad, int accumulate, int x_bf16, void* stream) {
-  const float* x = reinterpret_cast<const float*>(x_in);
-  const unsigned short* xh = reinterpret_cast<const unsigned short*>(x_in);
-  S2F_REQUIRE(x && gy && gw, S2F_EINVAL, "s2f_dwconv_bwd_weight: null pointer");
+  S2F_REQUIRE(x_in && gy && gw, S2F_EINVAL, "s2f_dwconv_bwd_weight: null pointer");
   int Ho, Wo;
   int rc = check("s2f_dwconv_bwd_weight", N, C, H, W, K, pad, Ho, Wo);
   if (rc) return rc;
@@ -468,21 +466,12 @@ extern "C" int s2f_dwconv_bwd_weight(const void* x_in, const float* border, cons
   if (per_plane > ntiles) per_plane = ntiles;
   if (per_plane < 1) per_plane = 1;
   const dim3 grid(per_plane, N * C);
-#define S2F_WG(KV)                                                                                                          \
-  do {                                                                                                                      \
-    if (x_bf16)                                                                                                             \
-      hipLaunchKernelGGL((dw_wgrad_kernel<KV, unsigned short>), grid, dim3(256), 0, s, xh, border, gy, gw, C, H, W, Ho, Wo, \
-                         pad, tiles_x, ntiles);                                                                             \
-    else                                                                                                                    \
-      hipLaunchKernelGGL((dw_wgrad_kernel<KV, float>), grid, dim3(256), 0, s, x, border, gy, gw, C, H, W, Ho, Wo, pad,      \
-                         tiles_x, ntiles);                                                                                  \
-  } while (0)
-  if (K == 3)
-    S2F_WG(3);
-  else if (K == 5)
-    S2F_WG(5);
-  else
-    S2F_WG(7);
-#undef S2F_WG
+  for_stencil_size(K, [&](auto i) {
+    s2f_dispatch_bool(x_bf16 != 0, [&](auto bf) {
+      using TX = std::conditional_t<bf.value, unsigned short, float>;
+      hipLaunchKernelGGL((dw_wgrad_kernel<kStencilSizes[i], TX>), grid, dim3(256), 0, s, reinterpret_cast<const TX*>(x_in), border,
+                         gy, gw, C, H, W, Ho, Wo, pad, tiles_x, ntiles);
+    });
+  });
   return s2f_check_launch("s2f_dwconv_bwd_weight");
 }

@@ -493,6 +493,16 @@ bool dwp_shape_ok(int batch, int M, int K, int L) {
   return (int64_t)M * L < (1ll << 30) && (int64_t)K * L < (1ll << 31);
 }
 
+// The schedules of dwp_grouped_kernel that are built: the symmetric one takes whole 32-column steps only.
+struct DwpSchedule {
+  bool symmetric, ragged;
+};
+constexpr DwpSchedule kDwpSchedules[] = {
+    {true, false},   // cfg 1: symmetric schedule
+    {false, true},   // cfg 0, some L % 32 != 0: two-halves schedule with a masked last step
+    {false, false},  // cfg 0: two-halves schedule
+};
+
 }  // namespace
 
 // 1 when the pipelined kernel takes this shape (the host's dispatch asks before choosing it)
@@ -515,20 +525,23 @@ static int dwp_launch_table(DwpJobTable& tab, int cfg, int target_wgs, void* str
   tab.work = (int)work, tab.quota = quota;
   hipStream_t s = (hipStream_t)stream;
 #ifdef S2F_DWP_PROBE
-#define S2F_KO(N) if (cfg == 2 * N + 1) { S2F_LAUNCH(true, true, (dwp_grouped_kernel<true, N>), dim3((unsigned)wgs), dim3(512), 0, s, tab); return s2f_check_launch("ko"); } \
-                  if (cfg == 2 * N) { S2F_LAUNCH(true, true, (dwp_grouped_kernel<false, N>), dim3((unsigned)wgs), dim3(512), 0, s, tab); return s2f_check_launch("ko"); }
-  S2F_KO(1) S2F_KO(3) S2F_KO(4) S2F_KO(12) S2F_KO(15) S2F_KO(20) S2F_KO(36) S2F_KO(52) S2F_KO(48)
-#undef S2F_KO
+  // probe builds: cfg = 2 N (+ 1: the symmetric schedule) runs the instance that stops after N pipeline steps
+  static constexpr int kProbeCuts[] = {1, 3, 4, 12, 15, 20, 36, 52, 48};
+  if (s2f_dispatch<kProbeCuts>([&](int n) { return (cfg >> 1) == n; }, [&](auto i) {
+        s2f_dispatch_bool((cfg & 1) != 0, [&](auto sym) {
+          S2F_LAUNCH(true, true, (dwp_grouped_kernel<sym.value, kProbeCuts[i]>), dim3((unsigned)wgs), dim3(512), 0, s, tab);
+        });
+      }))
+    return s2f_check_launch("ko");
 #endif
   bool ragged = false;
   for (int i = 0; i < tab.njobs; ++i) ragged = ragged || (tab.job[i].L & 31) != 0;
   S2F_REQUIRE(!ragged || cfg == 0, S2F_EINVAL, "%s: L %% 32 != 0 runs on the two-halves schedule only (cfg 0)", who);
-  if (cfg == 1)
-    S2F_LAUNCH(true, true, (dwp_grouped_kernel<true>), dim3((unsigned)wgs), dim3(512), 0, s, tab);
-  else if (ragged)
-    S2F_LAUNCH(true, true, (dwp_grouped_kernel<false, 0, true>), dim3((unsigned)wgs), dim3(512), 0, s, tab);
-  else
-    S2F_LAUNCH(true, true, (dwp_grouped_kernel<false>), dim3((unsigned)wgs), dim3(512), 0, s, tab);
+  const bool symmetric = cfg == 1;
+  s2f_dispatch<kDwpSchedules>([&](const DwpSchedule& e) { return e.symmetric == symmetric && (symmetric || e.ragged == ragged); }, [&](auto i) {
+    constexpr DwpSchedule V = kDwpSchedules[i];
+    S2F_LAUNCH(true, true, (dwp_grouped_kernel<V.symmetric, 0, V.ragged>), dim3((unsigned)wgs), dim3(512), 0, s, tab);
+  });
   return s2f_check_launch(who);
 }
 
@@ -622,9 +635,8 @@ extern "C" int s2f_spike_conv3x3_dw_pipe(const int64_t* jobs, int njobs, int cfg
   const int wgs = (int)((work + quota - 1) / quota);
   tab.work = (int)work, tab.quota = quota;
   hipStream_t s = (hipStream_t)stream;
-  if (cfg & 1)
-    S2F_LAUNCH(true, true, (dwp_conv_kernel<true>), dim3((unsigned)wgs), dim3(512), 0, s, tab);
-  else
-    S2F_LAUNCH(true, true, (dwp_conv_kernel<false>), dim3((unsigned)wgs), dim3(512), 0, s, tab);
+  s2f_dispatch_bool((cfg & 1) != 0, [&](auto sym) {
+    S2F_LAUNCH(true, true, (dwp_conv_kernel<sym.value>), dim3((unsigned)wgs), dim3(512), 0, s, tab);
+  });
   return s2f_check_launch("s2f_spike_conv3x3_dw_pipe");
 }

@@ -701,6 +701,46 @@ __global__ __launch_bounds__(256) void gemm_dw_general_grouped_kernel(const GDwJ
                                      j.x_bs, local % j.tiles, local / j.tiles);
 }
 
+// spike_gemm_kernel workgroup shapes: WM 64-row slabs side by side, or KG intra-workgroup contraction groups on the one-slab tile.
+struct SpikeGemmTile {
+  int wm, kg;
+};
+constexpr SpikeGemmTile kSpikeGemmTiles[] = {
+    {4, 1},  // 256-row tile
+    {2, 1},  // 128-row tile
+    {1, 4},  // 64-row tile, four contraction groups (never chosen: measured slower than two; built for A/B)
+    {1, 2},  // 64-row tile, two contraction groups: grids that leave the chip under-filled
+    {1, 1},  // 64-row tile
+};
+// bf16 terms of the weight split, for the forward GEMMs
+constexpr int kWeightTerms[] = {3, 2, 1};
+
+// split_gemm_kernel operand forms: bf16 terms of A and of X, and the implicit 3x3 addressing of X.
+struct SplitGemmForm {
+  int at, bt;
+  bool conv;
+};
+constexpr SplitGemmForm kSplitGemmForms[] = {
+    {3, 3, true},   // implicit 3x3 convolution: two general operands
+    {1, 3, false},  // A exact in bf16
+    {3, 1, false},  // X exact in bf16
+    {3, 3, false},  // two general operands
+};
+
+// spike_gemm_dw_kernel instances: contraction step, bf16 terms of X, implicit 3x3 addressing, rows of dY per tile.
+struct SpikeDwForm {
+  int bk, xt;
+  bool conv;
+  int tm;
+};
+constexpr SpikeDwForm kSpikeDwForms[] = {
+    {64, 1, true, 32},  {64, 1, true, 64},  {64, 1, true, 128},   // 3x3, 64-wide step (never chosen: 257 registers; built for A/B)
+    {32, 1, true, 32},  {32, 1, true, 64},  {32, 1, true, 128},   // 3x3
+    {32, 3, false, 128},                                          // general fp32 X: six LDS operand tiles, 128-row tiles only
+    {64, 1, false, 32}, {64, 1, false, 64}, {64, 1, false, 128},  // spike X, long or 64-aligned rows
+    {32, 1, false, 32}, {32, 1, false, 64}, {32, 1, false, 128},  // spike X, short ragged rows
+};
+
 }  // namespace
 
 extern "C" int s2f_split_bf16x3(const float* w, uint16_t* out, int M, int K, int Mpad, int Kpad, void* stream) {
@@ -751,33 +791,15 @@ static int spike_gemm_launch(const char* who, const uint16_t* w_split, const flo
   // intra-workgroup split-K for the narrowest tile when even that leaves the chip under-filled (see spike_gemm_kernel)
   const bool thin = wm == 1 && (int64_t)n_tiles * m_tiles * batch < 512;
   const int kg = (thin && Kpad >= 4 * BK) ? 2 : 1;          // KG = 4 measured slightly slower than 2 (58.7 vs 58.5 ms/step)
-#define S2F_GEMM_GO(WMV, TV, CV, KGV)                                                                                   \
-  S2F_LAUNCH(true, true, (spike_gemm_kernel<WMV, TV, CV, KGV>), grid, dim3(128 * WMV * KGV), 0, s, w_split, X, bias, Y, M, N, \
-             K, Mpad, Kpad, n_tiles, m_tiles, geo)
-#define S2F_GEMM_T(WMV, CV, KGV)                    \
-  if (terms == 3) S2F_GEMM_GO(WMV, 3, CV, KGV);      \
-  else if (terms == 2) S2F_GEMM_GO(WMV, 2, CV, KGV); \
-  else S2F_GEMM_GO(WMV, 1, CV, KGV)
-#define S2F_GEMM_W(CV)        \
-  if (wm == 4) {              \
-    S2F_GEMM_T(4, CV, 1);     \
-  } else if (wm == 2) {       \
-    S2F_GEMM_T(2, CV, 1);     \
-  } else if (kg == 4) {       \
-    S2F_GEMM_T(1, CV, 4);     \
-  } else if (kg == 2) {       \
-    S2F_GEMM_T(1, CV, 2);     \
-  } else {                    \
-    S2F_GEMM_T(1, CV, 1);     \
-  }
-  if (conv) {
-    S2F_GEMM_W(true)
-  } else {
-    S2F_GEMM_W(false)
-  }
-#undef S2F_GEMM_W
-#undef S2F_GEMM_T
-#undef S2F_GEMM_GO
+  s2f_dispatch<kSpikeGemmTiles>([&](const SpikeGemmTile& e) { return e.wm == wm && (wm != 1 || e.kg == kg); }, [&](auto i) {
+    constexpr SpikeGemmTile T = kSpikeGemmTiles[i];
+    s2f_dispatch<kWeightTerms>([&](int t) { return t == terms; }, [&](auto j) {
+      s2f_dispatch_bool(conv, [&](auto cv) {
+        S2F_LAUNCH(true, true, (spike_gemm_kernel<T.wm, kWeightTerms[j], cv.value, T.kg>), grid, dim3(128 * T.wm * T.kg), 0, s,
+                   w_split, X, bias, Y, M, N, K, Mpad, Kpad, n_tiles, m_tiles, geo);
+      });
+    });
+  });
   return s2f_check_launch(who);
 }
 
@@ -816,28 +838,17 @@ static int split_gemm_launch(const char* who, const uint16_t* a_split, int64_t a
   const bool narrow = M <= 64;
   const int n_tiles = (N + BN - 1) / BN, m_tiles = narrow ? 1 : Mpad / 128;
   const dim3 grid(n_tiles * m_tiles, batch);
-#define S2F_SG(AT, BT, CV)                                                                                              \
-  do {                                                                                                                  \
-    if (narrow)                                                                                                         \
-      S2F_LAUNCH(true, true, (split_gemm_kernel<1, AT, BT, CV>), grid, dim3(128), 0, s, a_split, a_batch_stride,           \
-                 a_term_stride, X, x_batch_stride, k_inner, x_outer_stride, Y, y_batch_stride, out_scale, M, N, K, Mpad,   \
-                 Kpad, n_tiles, m_tiles, geo);                                                                            \
-    else                                                                                                                \
-      S2F_LAUNCH(true, true, (split_gemm_kernel<2, AT, BT, CV>), grid, dim3(256), 0, s, a_split, a_batch_stride,           \
-                 a_term_stride, X, x_batch_stride, k_inner, x_outer_stride, Y, y_batch_stride, out_scale, M, N, K, Mpad,   \
-                 Kpad, n_tiles, m_tiles, geo);                                                                            \
-  } while (0)
-  if (conv) {
-    S2F_REQUIRE(a_terms == 3 && x_terms == 3, S2F_EINVAL, "%s: the convolution form takes two general operands", who);
-    S2F_SG(3, 3, true);
-  } else if (a_terms == 1) {
-    S2F_SG(1, 3, false);
-  } else if (x_terms == 1) {
-    S2F_SG(3, 1, false);
-  } else {
-    S2F_SG(3, 3, false);
-  }
-#undef S2F_SG
+  S2F_REQUIRE(!conv || (a_terms == 3 && x_terms == 3), S2F_EINVAL, "%s: the convolution form takes two general operands", who);
+  s2f_dispatch<kSplitGemmForms>(
+      [&](const SplitGemmForm& e) { return e.at == a_terms && e.bt == x_terms && e.conv == conv; }, [&](auto i) {
+        constexpr SplitGemmForm V = kSplitGemmForms[i];
+        s2f_dispatch_bool(narrow, [&](auto nr) {
+          constexpr int WM = nr.value ? 1 : 2;
+          S2F_LAUNCH(true, true, (split_gemm_kernel<WM, V.at, V.bt, V.conv>), grid, dim3(128 * WM), 0, s, a_split, a_batch_stride,
+                     a_term_stride, X, x_batch_stride, k_inner, x_outer_stride, Y, y_batch_stride, out_scale, M, N, K, Mpad, Kpad,
+                     n_tiles, m_tiles, geo);
+        });
+      });
   return s2f_check_launch(who);
 }
 
@@ -910,32 +921,13 @@ static int spike_dw_launch(const float* dY, const float* X, float* dW, int batch
   if (splits > 65535) splits = 65535;
   const int steps_per_split = (total_steps + splits - 1) / splits;
   splits = (total_steps + steps_per_split - 1) / steps_per_split;
-#define S2F_DW_GO1(BKV, XTV, CV, TMV)                                                                                   \
-  S2F_LAUNCH(true, true, (spike_gemm_dw_kernel<BKV, XTV, CV, TMV>), dim3(m_tiles * k_tiles, splits), dim3(256), 0, s, dY, X, \
-             dW, batch, M, K, L, steps_per_split, k_tiles, geo, log_w, dy_bs, x_bs)
-#define S2F_DW_GO(BKV, XTV, CV)                                                                                         \
-  do {                                                                                                                  \
-    if (tm == 32)                                                                                                       \
-      S2F_DW_GO1(BKV, XTV, CV, 32);                                                                                     \
-    else if (tm == 64)                                                                                                  \
-      S2F_DW_GO1(BKV, XTV, CV, 64);                                                                                     \
-    else                                                                                                                \
-      S2F_DW_GO1(BKV, XTV, CV, 128);                                                                                    \
-  } while (0)
-  if (conv) {
-    if (bkv == 64)
-      S2F_DW_GO(64, 1, true);
-    else
-      S2F_DW_GO(32, 1, true);
-  } else if (x_terms == 3) {
-    S2F_DW_GO1(32, 3, false, 128);
-  } else if (bkv == 64) {
-    S2F_DW_GO(64, 1, false);
-  } else {
-    S2F_DW_GO(32, 1, false);
-  }
-#undef S2F_DW_GO1
-#undef S2F_DW_GO
+  const int xt = conv ? 1 : x_terms, tmv = xt == 3 ? 128 : tm == 32 ? 32 : tm == 64 ? 64 : 128;
+  s2f_dispatch<kSpikeDwForms>(
+      [&](const SpikeDwForm& e) { return e.bk == bkv && e.xt == xt && e.conv == conv && e.tm == tmv; }, [&](auto i) {
+        constexpr SpikeDwForm V = kSpikeDwForms[i];
+        S2F_LAUNCH(true, true, (spike_gemm_dw_kernel<V.bk, V.xt, V.conv, V.tm>), dim3(m_tiles * k_tiles, splits), dim3(256), 0, s,
+                   dY, X, dW, batch, M, K, L, steps_per_split, k_tiles, geo, log_w, dy_bs, x_bs);
+      });
   return s2f_check_launch("s2f_spike_gemm_dw");
 }
 

@@ -538,6 +538,39 @@ __global__ void to_bf16_exact_kernel(const float* __restrict__ x, unsigned short
   }
 }
 
+// sgemm_bf16_kernel workgroup shapes: WM 64-row slabs side by side, or KG intra-workgroup contraction groups on the one-slab tile.
+struct FwdTile {
+  int wm, kg;
+};
+constexpr FwdTile kFwdTiles[] = {
+    {4, 1},  // 256-row tile
+    {2, 1},  // 128-row tile
+    {1, 4},  // 64-row tile, thin launch with a long contraction: four groups
+    {1, 2},  // 64-row tile, thin launch: two groups
+    {1, 1},  // 64-row tile
+};
+// bf16 terms of the weight split
+constexpr int kWeightTerms[] = {3, 2, 1};
+// How the spike operand is staged: elements per chunk, and the implicit 3x3 addressing.
+struct FwdOperand {
+  int chunk;
+  bool conv;
+};
+constexpr FwdOperand kFwdOperands[] = {
+    {4, true},   // implicit 3x3 convolution: 8-byte chunks
+    {8, false},  // N % 8 == 0: 16-byte chunks
+    {4, false},  // 8-byte chunks
+};
+
+// sgemm_dw_bf16_kernel: contraction step and implicit 3x3 addressing (the 64-wide step does not fit the 3x3 loader's registers) ...
+struct DwStep {
+  int bk;
+  bool conv;
+};
+constexpr DwStep kDwSteps[] = {{32, true}, {64, false}, {32, false}};
+// ... and rows of dY per output tile
+constexpr int kDwTileRows[] = {32, 64, 128};
+
 int fwd_launch(const char* who, const uint16_t* w_split, const uint16_t* X, const float* bias, float* Y, int batch, int M, int N,
                int K, int Mpad, int Kpad, int terms, bool conv, Conv3 geo, void* stream, GemmEx ex = GemmEx{0, 1, 0, 0, 0, 0, 1.f}) {
   S2F_REQUIRE(w_split && X && Y, S2F_EINVAL, "%s: null pointer", who);
@@ -574,35 +607,17 @@ int fwd_launch(const char* who, const uint16_t* w_split, const uint16_t* X, cons
   // (A 64 x 128 wavefront tile -- WNW = 1, half the wavefronts, 37 % less LDS read traffic per MFMA -- measured SLOWER:
   // [512x1152]@[8x1152x4096] 119 -> 149 us, [256x256]@[8x256x16384] 67 -> 89 us (tools/micro/gemm_fwd_probe.hip): the loop
   // is bound by the latency of its LDS reads and barriers at two wavefronts per SIMD, not by LDS bandwidth.)
-#define S2F_GO(WMV, TV, CHV, CV, KGV)                                                                                    \
-  S2F_LAUNCH(true, true, (sgemm_bf16_kernel<WMV, TV, CHV, CV, KGV>), grid, dim3(128 * WMV * KGV), 0, s, w_split, X, bias, Y, \
-             M, N, K, Mpad, Kpad, n_tiles, m_tiles, geo, ex)
-#define S2F_T(WMV, CHV, CV, KGV)                    \
-  if (terms == 3) S2F_GO(WMV, 3, CHV, CV, KGV);      \
-  else if (terms == 2) S2F_GO(WMV, 2, CHV, CV, KGV); \
-  else S2F_GO(WMV, 1, CHV, CV, KGV)
-#define S2F_W(CHV, CV)        \
-  if (wm == 4) {              \
-    S2F_T(4, CHV, CV, 1);     \
-  } else if (wm == 2) {       \
-    S2F_T(2, CHV, CV, 1);     \
-  } else if (kg == 4) {       \
-    S2F_T(1, CHV, CV, 4);     \
-  } else if (kg == 2) {       \
-    S2F_T(1, CHV, CV, 2);     \
-  } else {                    \
-    S2F_T(1, CHV, CV, 1);     \
-  }
-  if (conv) {
-    S2F_W(4, true)
-  } else if (wide) {
-    S2F_W(8, false)
-  } else {
-    S2F_W(4, false)
-  }
-#undef S2F_W
-#undef S2F_T
-#undef S2F_GO
+  s2f_dispatch<kFwdTiles>(
+      [&](const FwdTile& e) { return (wm == 4 || wm == 2) ? e.wm == wm : (e.wm == 1 && e.kg == kg); }, [&](auto i) {
+        constexpr FwdTile T = kFwdTiles[i];
+        s2f_dispatch<kWeightTerms>([&](int t) { return t == terms; }, [&](auto j) {
+          s2f_dispatch<kFwdOperands>([&](const FwdOperand& e) { return e.conv == conv && (conv || (e.chunk == 8) == wide); }, [&](auto o) {
+            constexpr FwdOperand O = kFwdOperands[o];
+            S2F_LAUNCH(true, true, (sgemm_bf16_kernel<T.wm, kWeightTerms[j], O.chunk, O.conv, T.kg>), grid,
+                       dim3(128 * T.wm * T.kg), 0, s, w_split, X, bias, Y, M, N, K, Mpad, Kpad, n_tiles, m_tiles, geo, ex);
+          });
+        });
+      });
   return s2f_check_launch(who);
 }
 
@@ -641,32 +656,15 @@ int dw_launch(const float* dY, const uint16_t* X, float* dW, int batch, int M, i
   if (splits > 65535) splits = 65535;
   const int steps_per_split = (total_steps + splits - 1) / splits;
   splits = (total_steps + steps_per_split - 1) / steps_per_split;
-#define S2F_DW1(BKV, CV, TMV)                                                                                            \
-  do {                                                                                                                   \
-    if (plane > 0)                                                                                                       \
-      S2F_LAUNCH(true, true, (sgemm_dw_bf16_kernel<BKV, CV, TMV, true>), dim3(m_tiles * k_tiles, splits), dim3(256), 0, s, dY, \
-                 X, dW, batch, M, K, L, steps_per_split, k_tiles, geo, log_w, plane);                                     \
-    else                                                                                                                 \
-      S2F_LAUNCH(true, true, (sgemm_dw_bf16_kernel<BKV, CV, TMV, false>), dim3(m_tiles * k_tiles, splits), dim3(256), 0, s, dY, \
-                 X, dW, batch, M, K, L, steps_per_split, k_tiles, geo, log_w, plane);                                     \
-  } while (0)
-#define S2F_DW(BKV, CV)             \
-  do {                              \
-    if (tm == 32)                   \
-      S2F_DW1(BKV, CV, 32);         \
-    else if (tm == 64)              \
-      S2F_DW1(BKV, CV, 64);         \
-    else                            \
-      S2F_DW1(BKV, CV, 128);        \
-  } while (0)
-  if (conv)
-    S2F_DW(32, true);
-  else if (bkv == 64)
-    S2F_DW(64, false);
-  else
-    S2F_DW(32, false);
-#undef S2F_DW
-#undef S2F_DW1
+  s2f_dispatch<kDwSteps>([&](const DwStep& e) { return e.bk == bkv && e.conv == conv; }, [&](auto i) {
+    constexpr DwStep V = kDwSteps[i];
+    s2f_dispatch<kDwTileRows>([&](int t) { return t == tm; }, [&](auto j) {
+      s2f_dispatch_bool(plane > 0, [&](auto pl) {
+        S2F_LAUNCH(true, true, (sgemm_dw_bf16_kernel<V.bk, V.conv, kDwTileRows[j], pl.value>), dim3(m_tiles * k_tiles, splits),
+                   dim3(256), 0, s, dY, X, dW, batch, M, K, L, steps_per_split, k_tiles, geo, log_w, plane);
+      });
+    });
+  });
   return s2f_check_launch("s2f_spike_gemm_dw_bf16");
 }
 
@@ -768,14 +766,11 @@ static int dw_grouped_launch(const int64_t* jobs, int njobs, int bkv, void* stre
   }
   S2F_REQUIRE(first < (1ll << 31), S2F_EINVAL, "s2f_spike_gemm_dw_grouped: grid too large");
   hipStream_t s = (hipStream_t)stream;
-  if (bkv == 64 && split)
-    S2F_LAUNCH(true, true, (sgemm_dw_grouped_kernel<64, 64, true>), dim3((unsigned)first), dim3(256), 0, s, tab);
-  else if (bkv == 64)
-    S2F_LAUNCH(true, true, (sgemm_dw_grouped_kernel<64, 64, false>), dim3((unsigned)first), dim3(256), 0, s, tab);
-  else if (split)
-    S2F_LAUNCH(true, true, (sgemm_dw_grouped_kernel<32, 64, true>), dim3((unsigned)first), dim3(256), 0, s, tab);
-  else
-    S2F_LAUNCH(true, true, (sgemm_dw_grouped_kernel<32, 64, false>), dim3((unsigned)first), dim3(256), 0, s, tab);
+  s2f_dispatch_bool(bkv == 64, [&](auto wide) {
+    s2f_dispatch_bool(split, [&](auto sp) {
+      S2F_LAUNCH(true, true, (sgemm_dw_grouped_kernel<wide.value ? 64 : 32, 64, sp.value>), dim3((unsigned)first), dim3(256), 0, s, tab);
+    });
+  });
   return s2f_check_launch("s2f_spike_gemm_dw_grouped");
 }
 

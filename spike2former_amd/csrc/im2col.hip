@@ -103,6 +103,13 @@ int geometry(const char* who, int N, int C, int H, int W, int kh, int kw, int st
   return S2F_OK;
 }
 
+// Strides with an instance of their own; 0 = the generic form that reads the stride at run time.
+constexpr int kStrides[] = {1, 2, 0};
+template <class F>
+void for_stride(int stride, const F& launch) {
+  s2f_dispatch<kStrides>([&](int sv) { return sv == stride || sv == 0; }, launch);
+}
+
 }  // namespace
 
 extern "C" int s2f_im2col(const void* x, void* cols, int N, int C, int H, int W, int kh, int kw, int stride, int pad, int x_bf16,
@@ -115,19 +122,13 @@ extern "C" int s2f_im2col(const void* x, void* cols, int N, int C, int H, int W,
               "s2f_im2col: cols must be 8-byte (bf16) / 16-byte (fp32) aligned");
   const dim3 grid((unsigned)((((int64_t)Ho * Wo + 3) / 4 + 255) / 256), (unsigned)(C * kh * kw), (unsigned)N);
   hipStream_t s = (hipStream_t)stream;
-#define S2F_IM2COL(T, SV)                                                                                                        \
-  hipLaunchKernelGGL((im2col_kernel<T, SV>), grid, dim3(256), 0, s, reinterpret_cast<const T*>(x), reinterpret_cast<T*>(cols), C, H, \
-                     W, kh, kw, stride, pad, Ho, Wo)
-  if (x_bf16) {
-    if (stride == 1) S2F_IM2COL(unsigned short, 1);
-    else if (stride == 2) S2F_IM2COL(unsigned short, 2);
-    else S2F_IM2COL(unsigned short, 0);
-  } else {
-    if (stride == 1) S2F_IM2COL(float, 1);
-    else if (stride == 2) S2F_IM2COL(float, 2);
-    else S2F_IM2COL(float, 0);
-  }
-#undef S2F_IM2COL
+  for_stride(stride, [&](auto i) {
+    s2f_dispatch_bool(x_bf16 != 0, [&](auto bf) {
+      using T = std::conditional_t<bf.value, unsigned short, float>;
+      hipLaunchKernelGGL((im2col_kernel<T, kStrides[i]>), grid, dim3(256), 0, s, reinterpret_cast<const T*>(x),
+                         reinterpret_cast<T*>(cols), C, H, W, kh, kw, stride, pad, Ho, Wo);
+    });
+  });
   return s2f_check_launch("s2f_im2col");
 }
 
@@ -142,11 +143,8 @@ extern "C" int s2f_col2im(const float* cols, float* gx, int N, int C, int H, int
   const unsigned gy = (unsigned)(planes < 32768 ? planes : 32768);
   const dim3 grid((unsigned)(((int64_t)H * ((W + 3) / 4) + 255) / 256), gy, (unsigned)((planes + gy - 1) / gy));
   hipStream_t s = (hipStream_t)stream;
-  if (stride == 1)
-    hipLaunchKernelGGL(col2im_kernel<1>, grid, dim3(256), 0, s, cols, gx, planes, H, W, kh, kw, stride, pad, Ho, Wo);
-  else if (stride == 2)
-    hipLaunchKernelGGL(col2im_kernel<2>, grid, dim3(256), 0, s, cols, gx, planes, H, W, kh, kw, stride, pad, Ho, Wo);
-  else
-    hipLaunchKernelGGL(col2im_kernel<0>, grid, dim3(256), 0, s, cols, gx, planes, H, W, kh, kw, stride, pad, Ho, Wo);
+  for_stride(stride, [&](auto i) {
+    hipLaunchKernelGGL(col2im_kernel<kStrides[i]>, grid, dim3(256), 0, s, cols, gx, planes, H, W, kh, kw, stride, pad, Ho, Wo);
+  });
   return s2f_check_launch("s2f_col2im");
 }

@@ -551,21 +551,12 @@ extern "C" int s2f_lif_fwd(const float* x, const float* v_in, void* y_out, float
               "s2f_lif_fwd: count_u8 must be 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   auto* st = reinterpret_cast<unsigned long long*>(stats);
-#define S2F_LIF_GO(HV, YBV)                                                                                            \
-  S2F_LAUNCH(true, true, (lif_fwd_kernel<HV, YBV>), dim3(grid_for(n)), dim3(kBlock), 0, s, x, v_in, y, v_out, mask,     \
-             count_u8, st, n, vth, (float)D)
-  if (v_in != nullptr) {
-    if (y_bf16)
-      S2F_LIF_GO(true, true);
-    else
-      S2F_LIF_GO(true, false);
-  } else {
-    if (y_bf16)
-      S2F_LIF_GO(false, true);
-    else
-      S2F_LIF_GO(false, false);
-  }
-#undef S2F_LIF_GO
+  s2f_dispatch_bool(v_in != nullptr, [&](auto hv) {
+    s2f_dispatch_bool(y_bf16 != 0, [&](auto yb) {
+      S2F_LAUNCH(true, true, (lif_fwd_kernel<hv.value, yb.value>), dim3(grid_for(n)), dim3(kBlock), 0, s, x, v_in, y, v_out,
+                 mask, count_u8, st, n, vth, (float)D);
+    });
+  });
   return s2f_check_launch("s2f_lif_fwd");
 }
 
@@ -578,12 +569,10 @@ extern "C" int s2f_lif_bwd_ports(const float* gy, const float* gy2, const float*
   S2F_REQUIRE(s2f_aligned16(gy) && s2f_aligned16(gx) && s2f_aligned16(gv_out) && s2f_aligned16(gy2) && s2f_aligned16(skip), S2F_EALIGN,
               "s2f_lif_bwd: gy/gx/gv must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if (gv_out != nullptr)
-    S2F_LAUNCH(true, true, lif_bwd_kernel<true>, dim3(grid_for(n)), dim3(kBlock), 0, s, gy, gv_out, mask, gx, n, vth,
-                       (float)D, gy2, skip);
-  else
-    S2F_LAUNCH(true, true, lif_bwd_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, s, gy, gv_out, mask, gx, n, vth,
-                       (float)D, gy2, skip);
+  s2f_dispatch_bool(gv_out != nullptr, [&](auto hg) {
+    S2F_LAUNCH(true, true, lif_bwd_kernel<hg.value>, dim3(grid_for(n)), dim3(kBlock), 0, s, gy, gv_out, mask, gx, n, vth,
+               (float)D, gy2, skip);
+  });
   return s2f_check_launch("s2f_lif_bwd");
 }
 
@@ -605,23 +594,14 @@ extern "C" int s2f_lif_leaky_fwd(const float* x, const float* v_in, void* y_out,
   hipStream_t s = (hipStream_t)stream;
   auto* st = reinterpret_cast<unsigned long long*>(stats);
   const float keep = (float)(1.0 - 1.0 / (double)tau);          // Python forms 1. - 1. / tau in double; the scalar multiply rounds it to fp32
-#define S2F_LEAKY_GO(HV, YBV, DI)                                                                                                   \
-  S2F_LAUNCH(true, true, (lif_leaky_fwd_kernel<HV, YBV, DI>), dim3(grid_for(n)), dim3(kBlock), 0, s, x, v_in, y, v_out, mask, st, n, \
-             vth, (float)D, tau, keep)
-#define S2F_LEAKY_YB(HV, DI) \
-  do {                       \
-    if (y_bf16)              \
-      S2F_LEAKY_GO(HV, true, DI); \
-    else                     \
-      S2F_LEAKY_GO(HV, false, DI); \
-  } while (0)
-  if (v_in != nullptr) {
-    if (decay_input) S2F_LEAKY_YB(true, true); else S2F_LEAKY_YB(true, false);
-  } else {
-    if (decay_input) S2F_LEAKY_YB(false, true); else S2F_LEAKY_YB(false, false);
-  }
-#undef S2F_LEAKY_YB
-#undef S2F_LEAKY_GO
+  s2f_dispatch_bool(v_in != nullptr, [&](auto hv) {
+    s2f_dispatch_bool(y_bf16 != 0, [&](auto yb) {
+      s2f_dispatch_bool(decay_input != 0, [&](auto di) {
+        S2F_LAUNCH(true, true, (lif_leaky_fwd_kernel<hv.value, yb.value, di.value>), dim3(grid_for(n)), dim3(kBlock), 0, s, x,
+                   v_in, y, v_out, mask, st, n, vth, (float)D, tau, keep);
+      });
+    });
+  });
   return s2f_check_launch("s2f_lif_leaky_fwd");
 }
 
@@ -634,15 +614,12 @@ extern "C" int s2f_lif_leaky_bwd(const float* gy, const float* gv_out, const uin
               "s2f_lif_leaky_bwd: gy/gx/gv must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const float keep = (float)(1.0 - 1.0 / (double)tau);
-#define S2F_LEAKY_BGO(HG, DI)                                                                                                    \
-  S2F_LAUNCH(true, true, (lif_leaky_bwd_kernel<HG, DI>), dim3(grid_for(n)), dim3(kBlock), 0, s, gy, gv_out, mask, gx, gv_in, n, vth, \
-             (float)D, tau, keep)
-  if (gv_out != nullptr) {
-    if (decay_input) S2F_LEAKY_BGO(true, true); else S2F_LEAKY_BGO(true, false);
-  } else {
-    if (decay_input) S2F_LEAKY_BGO(false, true); else S2F_LEAKY_BGO(false, false);
-  }
-#undef S2F_LEAKY_BGO
+  s2f_dispatch_bool(gv_out != nullptr, [&](auto hg) {
+    s2f_dispatch_bool(decay_input != 0, [&](auto di) {
+      S2F_LAUNCH(true, true, (lif_leaky_bwd_kernel<hg.value, di.value>), dim3(grid_for(n)), dim3(kBlock), 0, s, gy, gv_out, mask,
+                 gx, gv_in, n, vth, (float)D, tau, keep);
+    });
+  });
   return s2f_check_launch("s2f_lif_leaky_bwd");
 }
 
@@ -658,12 +635,10 @@ extern "C" int s2f_sum2_lif_fwd(const float* x, const float* e, const float* pos
               "s2f_sum2_lif_fwd: tensors must be 16-byte aligned");
   S2F_REQUIRE(!y_bf16 || s2f_bf16_spikes_exact(D), S2F_EINVAL, "s2f_sum2_lif_fwd: bf16 spikes need D a power of two <= 128 (D=%d)", D);
   const int64_t n = TB * C * L;
-  if (y_bf16)
-    S2F_LAUNCH(true, true, sum2_lif_fwd_kernel<true>, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, x, e, pos,
+  s2f_dispatch_bool(y_bf16 != 0, [&](auto yb) {
+    S2F_LAUNCH(true, true, sum2_lif_fwd_kernel<yb.value>, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, x, e, pos,
                y_key, y_value, mask_key, mask_value, n, (int)C, (int)L, (int)B, vth, (float)D);
-  else
-    S2F_LAUNCH(true, true, sum2_lif_fwd_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, x, e, pos,
-               y_key, y_value, mask_key, mask_value, n, (int)C, (int)L, (int)B, vth, (float)D);
+  });
   return s2f_check_launch("s2f_sum2_lif_fwd");
 }
 
@@ -722,12 +697,10 @@ extern "C" int s2f_lif_seq_fwd(const float* x_seq, const float* v0, float* y_seq
               "s2f_lif_seq_fwd: pointers must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   auto* st = reinterpret_cast<unsigned long long*>(stats);
-  if (v0 != nullptr)
-    hipLaunchKernelGGL(lif_seq_fwd_kernel<true>, dim3(grid_for(n)), dim3(kBlock), 0, s, x_seq, v0, y_seq, vT, mask, st,
-                       T, n, vth, (float)D);
-  else
-    hipLaunchKernelGGL(lif_seq_fwd_kernel<false>, dim3(grid_for(n)), dim3(kBlock), 0, s, x_seq, v0, y_seq, vT, mask, st,
-                       T, n, vth, (float)D);
+  s2f_dispatch_bool(v0 != nullptr, [&](auto hv) {
+    hipLaunchKernelGGL(lif_seq_fwd_kernel<hv.value>, dim3(grid_for(n)), dim3(kBlock), 0, s, x_seq, v0, y_seq, vT, mask, st, T, n,
+                       vth, (float)D);
+  });
   return s2f_check_launch("s2f_lif_seq_fwd");
 }
 

@@ -1249,6 +1249,173 @@ int pick_cfg_nn(int M, int N, int K, int batch, int force) {
   return (M > 64 && tiles128 >= t7) ? 7 : ((N >= 128 || M >= 64) ? 8 : 6);
 }
 
+
+// ---- kernel variants (host side): every instance the launchers build is listed here, once ----------------------------------------
+// A workgroup tile: MI x NJ 32 x 32 MFMA blocks per wavefront on WMW x WNW wavefronts.  `extra` is the family's own compile-time
+// knob (named in each table).  Every form below lists the tile configurations it is built for: the tables are not a cross product.
+struct PgTile {
+  int cfg, MI, NJ, WMW, WNW, extra;
+  constexpr int rows() const { return 32 * MI * WMW; }
+  constexpr int threads() const { return 64 * WMW * WNW; }
+};
+template <class... I>
+constexpr unsigned cfg_set(I... cfg) { return ((1u << cfg) | ...); }
+
+// pg_nn_kernel (all-DMA product).  extra = LDS stages.
+constexpr PgTile kNnTiles[] = {
+    {1, 2, 2, 2, 2, 2},  // 128 x 128, 4 wavefronts, 2 stages (64 KiB: two workgroups per CU)
+    {2, 1, 2, 2, 2, 3},  // 64 x 128, 4 wavefronts of 32 x 64, 3 stages (60 KiB)
+    {3, 2, 2, 2, 2, 3},  // 128 x 128, 3 stages (96 KiB: one workgroup per CU)
+    {4, 1, 2, 2, 2, 2},  // 64 x 128, 2 stages (40 KiB: three workgroups per CU)
+    {5, 2, 2, 4, 2, 2},  // 256 x 128, 8 wavefronts, 2 stages (112 KiB)
+};
+struct NnForm {
+  int terms, epi;  // bf16 terms of the weight; 1: the BatchNorm -> neuron epilogue
+  bool stats, ex;  // BatchNorm partial sums of the product; the general form (NnEx)
+  unsigned cfgs;
+};
+constexpr NnForm kNnForms[] = {
+    {3, 0, false, false, cfg_set(1, 2, 3, 4, 5)},  // plain product, general weight
+    {2, 0, false, false, cfg_set(1, 2, 3, 4, 5)},  // weight exact in two terms
+    {1, 0, false, false, cfg_set(1, 2, 3, 4, 5)},  // weight exact in bf16
+    {3, 0, true, false, cfg_set(1, 2, 3, 4, 5)},   // + statistics (always all three weight terms)
+    {3, 1, false, false, cfg_set(2, 4)},           // inference epilogue: the 64 x 128 tiles pick_cfg_nn returns
+    {3, 0, false, true, cfg_set(2, 4)},            // general form: the 64 x 128 tile, two or three stages
+};
+
+// pg_conv_kernel: the implicit 3x3 convolution (cfg 1 .. 4) and the 1x1 product with register-staged activation rows (cfg 6 .. 8).
+// extra = CONV.
+constexpr PgTile kConvTiles[] = {
+    {1, 2, 2, 2, 2, 1},  // 128 x 128, wavefront tiles 64 x 64
+    {2, 1, 2, 2, 2, 1},  // 64 x 128, wavefront tiles 32 x 64
+    {3, 1, 1, 1, 4, 1},  // 32 x 128, wavefront tiles 32 x 32 (the 32-channel gradients of the 256 x 256 maps)
+    {4, 1, 2, 4, 2, 1},  // 128 x 128 on EIGHT wavefronts of 32 x 64: two per SIMD, staging under the MFMAs
+    {6, 1, 2, 2, 2, 0},  // rows: 64 x 128 on four wavefronts (outputs of fewer than 64 rows)
+    {7, 1, 2, 4, 2, 0},  // rows: 128 x 128 on eight wavefronts
+    {8, 1, 1, 2, 4, 0},  // rows: 64 x 128 on eight wavefronts of 32 x 32
+};
+struct ConvForm {
+  int bt, epi;  // bf16 terms of the activation (3: fp32 input); 1: the BatchNorm -> neuron epilogue
+  bool stats;
+  int g;        // K steps per barrier
+  unsigned cfgs;
+};
+constexpr ConvForm kConvForms[] = {
+    {3, 0, false, 1, cfg_set(1, 2, 3, 4)},           // fp32 activation (3x3 only)
+    {1, 0, false, 1, cfg_set(1, 2, 3, 4, 6, 7, 8)},  // plain
+    {1, 0, true, 1, cfg_set(1, 2, 3, 4, 6, 7, 8)},   // + statistics
+    {1, 0, false, 2, cfg_set(1, 2, 3, 4, 7, 8)},     // two steps per barrier (not on the four-wavefront rows tile)
+    {1, 0, true, 2, cfg_set(1, 2, 3, 4, 7, 8)},
+    {1, 1, false, 1, cfg_set(2, 3, 4, 6, 7, 8)},     // inference epilogue
+    {1, 1, false, 2, cfg_set(2, 3, 4, 7, 8)},
+};
+
+constexpr bool conv_g2_built(int cfg) {
+  for (const ConvForm& f : kConvForms)
+    if (f.g == 2 && (f.cfgs >> cfg & 1)) return true;
+  return false;
+}
+
+// pg_tn_split_kernel.  extra = LDS stages.
+constexpr PgTile kTnSplitTiles[] = {
+    {1, 2, 2, 2, 2, 3},  // 128 x 128, 3 stages (72 KiB)
+    {2, 1, 2, 2, 2, 3},  // 64 x 128, 3 stages (54 KiB)
+    {3, 2, 2, 2, 2, 2},  // 128 x 128, 2 stages
+    {4, 1, 2, 2, 2, 2},  // 64 x 128, 2 stages (36 KiB)
+};
+
+// pg_tn_f32_kernel.  extra = KS, 16-row contraction steps per barrier.
+constexpr PgTile kTnTiles[] = {
+    {1, 2, 2, 2, 2, 1},   // 128 x 128
+    {2, 1, 2, 2, 2, 1},   // 64 x 128
+    {3, 1, 2, 4, 2, 1},   // 128 x 128 on eight wavefronts (two per SIMD)
+    {4, 1, 1, 2, 4, 1},   // 64 x 128 on eight wavefronts of 32 x 32
+    {5, 1, 1, 1, 4, 1},   // 32 x 128 on four wavefronts of 32 x 32: twice the workgroups of cfg 2
+    {7, 1, 1, 2, 4, 2},   // cfg 4 with 32-row steps (half the barriers per MFMA)
+    {8, 1, 2, 2, 2, 2},   // cfg 2 with 32-row steps
+    {9, 1, 2, 4, 2, 2},   // cfg 3 with 32-row steps
+    {10, 1, 1, 2, 4, 4},  // cfg 4 with 64-row steps (144 KB of LDS: one workgroup per CU)
+};
+struct TnForm {
+  int epi;  // 0: store, 1: DX = beta DX + product, 2: atomics of a contraction split, 3: the BatchNorm -> neuron epilogue
+  bool stats, grouped;
+  unsigned cfgs;
+};
+constexpr TnForm kTnForms[] = {
+    {2, false, false, cfg_set(1, 2, 3, 4, 5)},
+    {1, false, false, cfg_set(1, 2, 3, 4, 5)},
+    {0, true, false, cfg_set(1, 2, 3, 4, 5, 7, 8, 9, 10)},
+    {0, false, false, cfg_set(1, 2, 3, 4, 5, 7, 8, 9, 10)},
+    {0, true, true, cfg_set(3, 5, 7)},      // 1..4 weights on consecutive channel groups (gridDim.z)
+    {0, false, true, cfg_set(3, 5, 7)},
+    {3, false, true, cfg_set(5, 7, 9, 10)},  // dense inference product
+};
+
+// One launch of pg_nn_kernel; false when no instance is built for (form, cfg).
+bool launch_pg_nn(int cfg, int terms, int epi, bool ex_form, hipStream_t s, const uint16_t* a_pack, const uint16_t* X, const float* bias,
+                  float* Y, int batch, int M, int N, int K, int64_t xbs, const BnLifEpi& ep, float* part, const NnEx& ex) {
+  const int Kb = (K + PK - 1) / PK, n_tiles = (N + 127) / 128;
+  bool ok = false;
+  s2f_dispatch<kNnForms>(
+      [&](const NnForm& e) { return e.terms == terms && e.epi == epi && e.stats == (part != nullptr) && e.ex == ex_form; }, [&](auto f) {
+        constexpr NnForm F = kNnForms[f];
+        ok = s2f_dispatch<kNnTiles>([&](const PgTile& e) { return e.cfg == cfg && (F.cfgs >> e.cfg & 1); }, [&](auto i) {
+          constexpr PgTile T = kNnTiles[i];
+          if constexpr (F.cfgs >> T.cfg & 1) {
+            const int m_tiles = (M + T.rows() - 1) / T.rows();
+            S2F_LAUNCH(true, true, (pg_nn_kernel<T.MI, T.NJ, T.WMW, T.WNW, F.terms, T.extra, F.epi, F.stats, F.ex>),
+                       dim3(n_tiles * m_tiles, batch), dim3(T.threads()), 0, s, a_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, xbs,
+                       ep, part, ex);
+          }
+        });
+      });
+  return ok;
+}
+
+// One launch of pg_conv_kernel; two_steps(workgroups) says whether this launch wants two K steps per barrier where that is built.
+template <class TwoSteps>
+bool launch_pg_conv(int cfg, bool conv, int bt, int epi, const TwoSteps& two_steps, hipStream_t s, const uint16_t* a_pack, const void* X,
+                    const float* bias, float* Y, int batch, int M, int N, int K, int Kb, Conv3 geo, float* part, const BnLifEpi& ep) {
+  const int n_tiles = (N + 127) / 128;
+  bool ok = false;
+  s2f_dispatch<kConvTiles>([&](const PgTile& e) { return e.cfg == cfg && (e.extra != 0) == conv; }, [&](auto i) {
+    constexpr PgTile T = kConvTiles[i];
+    const int m_tiles = (M + T.rows() - 1) / T.rows();
+    const bool stats = part != nullptr && bt == 1;
+    const int g = (conv_g2_built(T.cfg) && two_steps((int64_t)n_tiles * m_tiles * batch)) ? 2 : 1;
+    ok = s2f_dispatch<kConvForms>(
+        [&](const ConvForm& e) { return e.bt == bt && e.epi == epi && e.stats == stats && e.g == g && (e.cfgs >> T.cfg & 1); }, [&](auto f) {
+          constexpr ConvForm F = kConvForms[f];
+          if constexpr (F.cfgs >> T.cfg & 1)
+            S2F_LAUNCH(true, true, (pg_conv_kernel<T.MI, T.NJ, T.WMW, T.WNW, F.bt, T.extra != 0, F.stats, F.epi, F.g>),
+                       dim3(n_tiles * m_tiles, batch), dim3(T.threads()), 0, s, a_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, geo,
+                       part, ep);
+        });
+  });
+  return ok;
+}
+
+// One launch of pg_tn_f32_kernel (gridDim.z = zdim: contraction splits or weight groups); false when no instance is built.
+bool launch_pg_tn(int cfg, int epi, bool grouped, hipStream_t s, const uint16_t* w_pack, const float* G, float* DX, int batch, int zdim,
+                  int Mo, int Ki, int N, float beta, int64_t g_batch_stride, int64_t dx_batch_stride, float* part, const TnGroups& grp,
+                  const BnLifEpi& ep) {
+  const int KbW = (Ki + PK - 1) / PK, n_tiles = (N + 127) / 128;
+  bool ok = false;
+  s2f_dispatch<kTnForms>([&](const TnForm& e) { return e.epi == epi && e.stats == (part != nullptr) && e.grouped == grouped; }, [&](auto f) {
+    constexpr TnForm F = kTnForms[f];
+    ok = s2f_dispatch<kTnTiles>([&](const PgTile& e) { return e.cfg == cfg && (F.cfgs >> e.cfg & 1); }, [&](auto i) {
+      constexpr PgTile T = kTnTiles[i];
+      if constexpr (F.cfgs >> T.cfg & 1) {
+        const int m_tiles = (Ki + T.rows() - 1) / T.rows();
+        S2F_LAUNCH(true, true, (pg_tn_f32_kernel<T.MI, T.NJ, T.WMW, T.WNW, F.epi, T.extra, F.stats, F.grouped>),
+                   dim3(n_tiles * m_tiles, batch, zdim), dim3(T.threads()), 0, s, w_pack, G, DX, Mo, Ki, N, KbW, n_tiles, m_tiles, beta,
+                   g_batch_stride, dx_batch_stride, part, grp, ep);
+      }
+    });
+  });
+  return ok;
+}
+
 }  // namespace
 
 extern "C" int64_t s2f_pack_elems(int M, int K) { return (int64_t)((M + PR - 1) / PR) * ((K + PK - 1) / PK) * PBLOCK; }
@@ -1274,86 +1441,20 @@ static int pgemm_nn_impl(const uint16_t* a_pack, const uint16_t* X, const float*
               "s2f_pgemm_nn_bf16: pointers must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int Kb = (K + PK - 1) / PK;
-  const int n_tiles = (N + 127) / 128;
   static const char* force = getenv("S2F_PG_CFG");
   const int c = terms == 3 ? pick_cfg_nn(M, N, K, batch, cfg > 0 ? cfg : (force ? atoi(force) : 0)) : (cfg > 0 ? cfg : 4);
   S2F_REQUIRE((N & 7) == 0 || cfg == 0 || cfg >= 6, S2F_EINVAL, "s2f_pgemm_nn_bf16: cfg %d needs N %% 8 == 0 (N=%d)", cfg, N);
   if (c == 6 || c == 7 || c == 8 || (N & 7) != 0) {
     // the activation rows through registers (pg_conv_kernel<.., CONV = false>): any N % 4 == 0
     S2F_REQUIRE(terms == 3, S2F_EINVAL, "s2f_pgemm_nn_bf16: the register-staged form takes all three weight terms");
-    const bool wide = c == 7;          // (an environment-forced DMA configuration does not apply to rows of N % 8 != 0)
-    if (c == 8) {
-      const int m_tiles = (M + 63) / 64;
-      const bool g2 = nn_super_steps(Kb, (int64_t)n_tiles * m_tiles * batch);
-      if (part && g2)
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 1, 2, 4, 1, false, true, 0, 2>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X,
-                   bias, Y, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-      else if (g2)
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 1, 2, 4, 1, false, false, 0, 2>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X, bias, Y,
-                   M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-      else if (part)
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 1, 2, 4, 1, false, true>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X,
-                   bias, Y, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-      else
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 1, 2, 4, 1, false>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X, bias, Y,
-                   M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-    } else if (wide) {
-      const int m_tiles = (M + 127) / 128;
-      const bool g2 = nn_super_steps(Kb, (int64_t)n_tiles * m_tiles * batch);
-      if (part && g2)
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 4, 2, 1, false, true, 0, 2>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X,
-                   bias, Y, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-      else if (g2)
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 4, 2, 1, false, false, 0, 2>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X, bias, Y,
-                   M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-      else if (part)
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 4, 2, 1, false, true>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X,
-                   bias, Y, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-      else
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 4, 2, 1, false>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X, bias, Y,
-                   M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-    } else {
-      const int m_tiles = (M + 63) / 64;
-      if (part)
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 2, 2, 1, false, true>), dim3(n_tiles * m_tiles, batch), dim3(256), 0, s, a_pack, X,
-                   bias, Y, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-      else
-        S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 2, 2, 1, false>), dim3(n_tiles * m_tiles, batch), dim3(256), 0, s, a_pack, X, bias, Y,
-                   M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, part, BnLifEpi{});
-    }
+    // (an environment-forced DMA configuration does not apply to rows of N % 8 != 0)
+    const bool ok = launch_pg_conv(c == 8 || c == 7 ? c : 6, false, 1, 0, [&](int64_t wgs) { return nn_super_steps(Kb, wgs); }, s,
+                                   a_pack, X, bias, Y, batch, M, N, K, Kb, Conv3{0, 0, 0}, part, BnLifEpi{});
+    S2F_REQUIRE(ok, S2F_EINVAL, "s2f_pgemm_nn_bf16: unknown cfg %d", c);
     return s2f_check_launch("s2f_pgemm_nn_bf16");
   }
-  const int64_t xbs = (int64_t)K * N;
-#define S2F_PG(MI, NJ, WMW, WNW, ATV, NSTV)                                                                            \
-  do {                                                                                                                 \
-    const int m_tiles = (M + 32 * MI * WMW - 1) / (32 * MI * WMW);                                                     \
-    if (part) {                                                                                                        \
-      if constexpr (ATV == 3)          /* (the statistics entry point always runs all three weight terms) */             \
-        S2F_LAUNCH(true, true, (pg_nn_kernel<MI, NJ, WMW, WNW, 3, NSTV, 0, true>), dim3(n_tiles * m_tiles, batch),      \
-                   dim3(64 * WMW * WNW), 0, s, a_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, xbs, BnLifEpi{}, part, NnEx{}); \
-    } else                                                                                                             \
-      S2F_LAUNCH(true, true, (pg_nn_kernel<MI, NJ, WMW, WNW, ATV, NSTV>), dim3(n_tiles * m_tiles, batch),               \
-                 dim3(64 * WMW * WNW), 0, s, a_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, xbs, BnLifEpi{}, part, NnEx{}); \
-  } while (0)
-#define S2F_PG_T(MI, NJ, WMW, WNW, NSTV)          \
-  do {                                           \
-    if (terms == 3)                              \
-      S2F_PG(MI, NJ, WMW, WNW, 3, NSTV);         \
-    else if (terms == 2)                         \
-      S2F_PG(MI, NJ, WMW, WNW, 2, NSTV);         \
-    else                                         \
-      S2F_PG(MI, NJ, WMW, WNW, 1, NSTV);         \
-  } while (0)
-  switch (c) {
-    case 1: S2F_PG_T(2, 2, 2, 2, 2); break;          // 128 x 128, 4 wavefronts, 2 stages (64 KiB: two workgroups per CU)
-    case 2: S2F_PG_T(1, 2, 2, 2, 3); break;          // 64 x 128, 4 wavefronts of 32 x 64, 3 stages (60 KiB)
-    case 3: S2F_PG_T(2, 2, 2, 2, 3); break;          // 128 x 128, 3 stages (96 KiB: one workgroup per CU)
-    case 4: S2F_PG_T(1, 2, 2, 2, 2); break;          // 64 x 128, 2 stages (40 KiB: three workgroups per CU)
-    case 5: S2F_PG_T(2, 2, 4, 2, 2); break;          // 256 x 128, 8 wavefronts, 2 stages (112 KiB)
-    default: S2F_REQUIRE(false, S2F_EINVAL, "s2f_pgemm_nn_bf16: unknown cfg %d", c);
-  }
-#undef S2F_PG_T
-#undef S2F_PG
+  const bool ok = launch_pg_nn(c, terms, 0, false, s, a_pack, X, bias, Y, batch, M, N, K, (int64_t)K * N, BnLifEpi{}, part, NnEx{});
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_pgemm_nn_bf16: unknown cfg %d", c);
   return s2f_check_launch("s2f_pgemm_nn_bf16");
 }
 
@@ -1370,18 +1471,12 @@ extern "C" int s2f_pgemm_nn_bf16_ex(const uint16_t* a_pack, int64_t a_batch_stri
   S2F_REQUIRE((a_batch_stride & 7) == 0 && (x_batch_stride & 7) == 0 && (x_outer_stride & 7) == 0, S2F_EALIGN,
               "s2f_pgemm_nn_bf16_ex: strides must keep 16-byte alignment");
   S2F_REQUIRE(s2f_aligned16(a_pack) && s2f_aligned16(X) && s2f_aligned16(Y), S2F_EALIGN, "s2f_pgemm_nn_bf16_ex: pointers must be 16-byte aligned");
-  const int Kb = (K + PK - 1) / PK, n_tiles = (N + 127) / 128, m_tiles = (M + 63) / 64;
   // 64 x 128 on four wavefronts, two LDS stages, three workgroups per CU (cfg 4 of s2f_pgemm_nn_bf16): 603 us on the C2 mask contraction
   // [700 x 1024] @ [2 x 1024 x 65536] against 834 for the round-2 kernel and 659 for the 256 x 128 eight-wavefront tile (tools/probe_mask_fwd.py)
-  static const char* nst_env = getenv("S2F_PG_EX_NST");          // A/B switch: LDS stages of this launch
-  if (nst_env && nst_env[0] == '3')
-    S2F_LAUNCH(true, true, (pg_nn_kernel<1, 2, 2, 2, 3, 3, 0, false, true>), dim3(n_tiles * m_tiles, batch), dim3(256), 0,
-               (hipStream_t)stream, a_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, x_batch_stride, BnLifEpi{}, nullptr,
-               NnEx{k_inner, a_batch_stride, x_outer_stride, bias_batch_stride, out_scale});
-  else
-    S2F_LAUNCH(true, true, (pg_nn_kernel<1, 2, 2, 2, 3, 2, 0, false, true>), dim3(n_tiles * m_tiles, batch), dim3(256), 0,
-               (hipStream_t)stream, a_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, x_batch_stride, BnLifEpi{}, nullptr,
-               NnEx{k_inner, a_batch_stride, x_outer_stride, bias_batch_stride, out_scale});
+  static const char* nst_env = getenv("S2F_PG_EX_NST");          // A/B switch: LDS stages of this launch (3: cfg 2)
+  const bool ok = launch_pg_nn(nst_env && nst_env[0] == '3' ? 2 : 4, 3, 0, true, (hipStream_t)stream, a_pack, X, bias, Y, batch, M, N, K, x_batch_stride,
+               BnLifEpi{}, nullptr, NnEx{k_inner, a_batch_stride, x_outer_stride, bias_batch_stride, out_scale});
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_pgemm_nn_bf16_ex: no kernel instance");
   return s2f_check_launch("s2f_pgemm_nn_bf16_ex");
 }
 
@@ -1408,7 +1503,7 @@ extern "C" int s2f_gemm_bn_lif_fwd(const uint16_t* a_pack, const uint16_t* X, co
               "s2f_gemm_bn_lif_fwd: bad sizes (N=%d must be a multiple of 4, >= 8)", N);
   S2F_REQUIRE(!y_bf16 || s2f_bf16_spikes_exact(D), S2F_EINVAL, "s2f_gemm_bn_lif_fwd: bf16 spikes need D a power of two <= 128");
   S2F_REQUIRE(s2f_aligned16(a_pack) && s2f_aligned16(X), S2F_EALIGN, "s2f_gemm_bn_lif_fwd: operands must be 16-byte aligned");
-  const int Kb = (K + PK - 1) / PK, n_tiles = (N + 127) / 128;
+  const int Kb = (K + PK - 1) / PK;
   BnLifEpi ep{conv_bias, running_mean, running_var, gamma, beta, residual, u_out, v_in, v_out,
               reinterpret_cast<unsigned short*>(y_bf16), reinterpret_cast<unsigned long long*>(stats), eps, vth, (float)D,
               1.0f / (float)D};
@@ -1416,35 +1511,11 @@ extern "C" int s2f_gemm_bn_lif_fwd(const uint16_t* a_pack, const uint16_t* X, co
   // the tile rule of the plain product (pick_cfg_nn): round 3 ran every fused launch on the four-wavefront DMA tile, 36 us on average
   // in the C2 inference step where the plain products of the same shapes take 14-21 us
   const int c = pick_cfg_nn(M, N, K, batch, 0);
-  if (c == 2) {
-    const int m_tiles = (M + 63) / 64;
-    S2F_LAUNCH(true, true, (pg_nn_kernel<1, 2, 2, 2, 3, 3, 1>), dim3(n_tiles * m_tiles, batch), dim3(256), 0, s, a_pack, X,
-               (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, (int64_t)K * N, ep, (float*)nullptr, NnEx{});
-  } else if (c == 4) {
-    const int m_tiles = (M + 63) / 64;
-    S2F_LAUNCH(true, true, (pg_nn_kernel<1, 2, 2, 2, 3, 2, 1>), dim3(n_tiles * m_tiles, batch), dim3(256), 0, s, a_pack, X,
-               (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, (int64_t)K * N, ep, (float*)nullptr, NnEx{});
-  } else if (c == 8) {
-    const int m_tiles = (M + 63) / 64;
-    if (nn_super_steps(Kb, (int64_t)n_tiles * m_tiles * batch))
-      S2F_LAUNCH(true, true, (pg_conv_kernel<1, 1, 2, 4, 1, false, false, 1, 2>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X,
-                 (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, (float*)nullptr, ep);
-    else
-      S2F_LAUNCH(true, true, (pg_conv_kernel<1, 1, 2, 4, 1, false, false, 1>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X,
-                 (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, (float*)nullptr, ep);
-  } else if (c == 7) {
-    const int m_tiles = (M + 127) / 128;
-    if (nn_super_steps(Kb, (int64_t)n_tiles * m_tiles * batch))
-      S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 4, 2, 1, false, false, 1, 2>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X,
-                 (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, (float*)nullptr, ep);
-    else
-      S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 4, 2, 1, false, false, 1>), dim3(n_tiles * m_tiles, batch), dim3(512), 0, s, a_pack, X,
-                 (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, (float*)nullptr, ep);
-  } else {
-    const int m_tiles = (M + 63) / 64;
-    S2F_LAUNCH(true, true, (pg_conv_kernel<1, 2, 2, 2, 1, false, false, 1>), dim3(n_tiles * m_tiles, batch), dim3(256), 0, s, a_pack, X,
-               (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, Conv3{0, 0, 0}, (float*)nullptr, ep);
-  }
+  const bool ok = (c == 2 || c == 4)
+                      ? launch_pg_nn(c, 3, 1, false, s, a_pack, X, nullptr, nullptr, batch, M, N, K, (int64_t)K * N, ep, nullptr, NnEx{})
+                      : launch_pg_conv(c == 8 || c == 7 ? c : 6, false, 1, 1, [&](int64_t wgs) { return nn_super_steps(Kb, wgs); }, s,
+                                       a_pack, X, nullptr, nullptr, batch, M, N, K, Kb, Conv3{0, 0, 0}, nullptr, ep);
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_gemm_bn_lif_fwd: no kernel instance for cfg %d", c);
   return s2f_check_launch("s2f_gemm_bn_lif_fwd");
 }
 
@@ -1465,31 +1536,14 @@ extern "C" int s2f_conv3x3_bn_lif_fwd(const uint16_t* w_pack, const uint16_t* X,
   BnLifEpi ep{conv_bias, running_mean, running_var, gamma, beta, residual, u_out, v_in, v_out,
               reinterpret_cast<unsigned short*>(y_bf16), reinterpret_cast<unsigned long long*>(stats), eps, vth, (float)D,
               1.0f / (float)D};
-  hipStream_t s = (hipStream_t)stream;
-  const Conv3 geo{H, W, C};
   // (the small-grid rule of the training forward, conv_launch: 64 x 128 tiles and two K steps per barrier when that is all the chip gets)
   static const char* small_env = getenv("S2F_PG_CONV_SMALL");
   const bool small_ok = !(small_env && small_env[0] == '0');
   const bool narrow = small_ok && M > 64 && (int64_t)n_tiles * batch * ((M + 127) / 128) <= 256;
-#define S2F_PGCE(MI, NJ, WMW, WNW)                                                                                        \
-  do {                                                                                                                   \
-    const int m_tiles = (M + 32 * MI * WMW - 1) / (32 * MI * WMW);                                                       \
-    if (small_ok && (Kb & 1) == 0 && Kb >= 4 && (int64_t)n_tiles * m_tiles * batch <= 512)                               \
-      S2F_LAUNCH(true, true, (pg_conv_kernel<MI, NJ, WMW, WNW, 1, true, false, 1, 2>), dim3(n_tiles * m_tiles, batch),    \
-                 dim3(64 * WMW * WNW), 0, s, w_pack, X, (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, \
-                 geo, (float*)nullptr, ep);                                                                              \
-    else                                                                                                                 \
-      S2F_LAUNCH(true, true, (pg_conv_kernel<MI, NJ, WMW, WNW, 1, true, false, 1>), dim3(n_tiles * m_tiles, batch),       \
-                 dim3(64 * WMW * WNW), 0, s, w_pack, X, (const float*)nullptr, (float*)nullptr, M, N, K, Kb, n_tiles, m_tiles, \
-                 geo, (float*)nullptr, ep);                                                                              \
-  } while (0)
-  if (M <= 32)
-    S2F_PGCE(1, 1, 1, 4);
-  else if (M <= 64 || narrow)
-    S2F_PGCE(1, 2, 2, 2);
-  else
-    S2F_PGCE(1, 2, 4, 2);
-#undef S2F_PGCE
+  const bool ok = launch_pg_conv(M <= 32 ? 3 : (M <= 64 || narrow) ? 2 : 4, true, 1, 1,
+                 [&](int64_t wgs) { return small_ok && (Kb & 1) == 0 && Kb >= 4 && wgs <= 512; }, (hipStream_t)stream, w_pack, X, nullptr,
+                 nullptr, batch, M, N, K, Kb, Conv3{H, W, C}, nullptr, ep);
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_conv3x3_bn_lif_fwd: no kernel instance");
   return s2f_check_launch("s2f_conv3x3_bn_lif_fwd");
 }
 
@@ -1506,20 +1560,13 @@ extern "C" int s2f_pgemm_dx_split(const uint16_t* w_pack, const uint16_t* G_spli
   static const char* force = getenv("S2F_PG_DXS_CFG");
   int c = cfg > 0 ? cfg : (force ? atoi(force) : 0);
   if (c <= 0) c = (Ki > 64 && (int64_t)n_tiles * batch * ((Ki + 127) / 128) >= 512) ? 1 : 2;
-#define S2F_PGS(MI, NJ, WMW, WNW, NSTV)                                                                                 \
-  do {                                                                                                                 \
-    const int m_tiles = (Ki + 32 * MI * WMW - 1) / (32 * MI * WMW);                                                    \
-    S2F_LAUNCH(true, true, (pg_tn_split_kernel<MI, NJ, WMW, WNW, NSTV>), dim3(n_tiles * m_tiles, batch),                \
-               dim3(64 * WMW * WNW), 0, s, w_pack, G_split, plane_stride, DX, Mo, Ki, N, KbW, n_tiles, m_tiles);        \
-  } while (0)
-  switch (c) {
-    case 1: S2F_PGS(2, 2, 2, 2, 3); break;          // 128 x 128, 3 stages (72 KiB)
-    case 2: S2F_PGS(1, 2, 2, 2, 3); break;          // 64 x 128, 3 stages (54 KiB)
-    case 3: S2F_PGS(2, 2, 2, 2, 2); break;          // 128 x 128, 2 stages
-    case 4: S2F_PGS(1, 2, 2, 2, 2); break;          // 64 x 128, 2 stages (36 KiB)
-    default: S2F_REQUIRE(false, S2F_EINVAL, "s2f_pgemm_dx_split: unknown cfg %d", c);
-  }
-#undef S2F_PGS
+  const bool ok = s2f_dispatch<kTnSplitTiles>([&](const PgTile& e) { return e.cfg == c; }, [&](auto i) {
+    constexpr PgTile T = kTnSplitTiles[i];
+    const int m_tiles = (Ki + T.rows() - 1) / T.rows();
+    S2F_LAUNCH(true, true, (pg_tn_split_kernel<T.MI, T.NJ, T.WMW, T.WNW, T.extra>), dim3(n_tiles * m_tiles, batch), dim3(T.threads()), 0,
+               s, w_pack, G_split, plane_stride, DX, Mo, Ki, N, KbW, n_tiles, m_tiles);
+  });
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_pgemm_dx_split: unknown cfg %d", c);
   return s2f_check_launch("s2f_pgemm_dx_split");
 }
 
@@ -1547,36 +1594,9 @@ static int conv_launch(const char* who, const uint16_t* w_pack, const void* X, b
   static const char* small_env = getenv("S2F_PG_CONV_SMALL");
   const bool small_ok = !(small_env && small_env[0] == '0');
   if (cfg <= 0 && !force && small_ok && c == 4 && (int64_t)n_tiles * batch * ((M + 127) / 128) <= 256) c = 2;
-  const bool g2 = small_ok && !x_fp32 &&
-                  nn_super_steps(Kb, (int64_t)n_tiles * batch * ((M + (c == 4 || c == 1 ? 127 : c == 2 ? 63 : 31)) / (c == 4 || c == 1 ? 128 : c == 2 ? 64 : 32)));
-  const Conv3 geo{H, W, C};
-#define S2F_PGC(MI, NJ, WMW, WNW)                                                                                         \
-  do {                                                                                                                   \
-    const int m_tiles = (M + 32 * MI * WMW - 1) / (32 * MI * WMW);                                                       \
-    if (x_fp32)                                                                                                          \
-      S2F_LAUNCH(true, true, (pg_conv_kernel<MI, NJ, WMW, WNW, 3>), dim3(n_tiles * m_tiles, batch), dim3(64 * WMW * WNW), 0, s, \
-                 w_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, geo, part, BnLifEpi{});                                           \
-    else if (part && g2)                                                                                                 \
-      S2F_LAUNCH(true, true, (pg_conv_kernel<MI, NJ, WMW, WNW, 1, true, true, 0, 2>), dim3(n_tiles * m_tiles, batch),     \
-                 dim3(64 * WMW * WNW), 0, s, w_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, geo, part, BnLifEpi{});               \
-    else if (g2)                                                                                                         \
-      S2F_LAUNCH(true, true, (pg_conv_kernel<MI, NJ, WMW, WNW, 1, true, false, 0, 2>), dim3(n_tiles * m_tiles, batch),    \
-                 dim3(64 * WMW * WNW), 0, s, w_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, geo, part, BnLifEpi{});               \
-    else if (part)                                                                                                       \
-      S2F_LAUNCH(true, true, (pg_conv_kernel<MI, NJ, WMW, WNW, 1, true, true>), dim3(n_tiles * m_tiles, batch),           \
-                 dim3(64 * WMW * WNW), 0, s, w_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, geo, part, BnLifEpi{});               \
-    else                                                                                                                 \
-      S2F_LAUNCH(true, true, (pg_conv_kernel<MI, NJ, WMW, WNW, 1>), dim3(n_tiles * m_tiles, batch), dim3(64 * WMW * WNW), 0, s, \
-                 w_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, geo, part, BnLifEpi{});                                           \
-  } while (0)
-  switch (c) {
-    case 1: S2F_PGC(2, 2, 2, 2); break;          // 128 x 128, wavefront tiles 64 x 64
-    case 2: S2F_PGC(1, 2, 2, 2); break;          // 64 x 128, wavefront tiles 32 x 64
-    case 3: S2F_PGC(1, 1, 1, 4); break;          // 32 x 128, wavefront tiles 32 x 32 (the 32-channel gradients of the 256 x 256 maps)
-    case 4: S2F_PGC(1, 2, 4, 2); break;          // 128 x 128 on EIGHT wavefronts of 32 x 64: two per SIMD, staging under the MFMAs
-    default: S2F_REQUIRE(false, S2F_EINVAL, "%s: unknown cfg %d", who, c);
-  }
-#undef S2F_PGC
+  const bool ok = launch_pg_conv(c, true, x_fp32 ? 3 : 1, 0, [&](int64_t wgs) { return small_ok && !x_fp32 && nn_super_steps(Kb, wgs); },
+                                 s, w_pack, X, bias, Y, batch, M, N, K, Kb, Conv3{H, W, C}, part, BnLifEpi{});
+  S2F_REQUIRE(ok, S2F_EINVAL, "%s: unknown cfg %d", who, c);
   return s2f_check_launch(who);
 }
 
@@ -1617,7 +1637,6 @@ static int pgemm_dx_impl(const uint16_t* w_pack, const float* G, int64_t g_batch
   S2F_REQUIRE(s2f_aligned16(w_pack) && s2f_aligned16(G) && s2f_aligned16(DX), S2F_EALIGN,
               "s2f_pgemm_dx_f32: pointers must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  const int KbW = (Ki + PK - 1) / PK;
   const int n_tiles = (N + 127) / 128;
   static const char* force = getenv("S2F_PG_DX_CFG");
   int c = cfg > 0 ? cfg : (force ? atoi(force) : 0);
@@ -1652,52 +1671,10 @@ static int pgemm_dx_impl(const uint16_t* w_pack, const float* G, int64_t g_batch
       return s2f_check_launch("s2f_pgemm_dx_f32 zero");
     c = 4;
   }
-#define S2F_PGD(MI, NJ, WMW, WNW)                                                                                       \
-  do {                                                                                                                 \
-    const int m_tiles = (Ki + 32 * MI * WMW - 1) / (32 * MI * WMW);                                                    \
-    const dim3 grid(n_tiles * m_tiles, batch, zsplit);                                                                 \
-    if (zsplit > 1)                                                                                                    \
-      S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 2>), grid, dim3(64 * WMW * WNW), 0, s, w_pack, G, DX,  \
-                 Mo, Ki, N, KbW, n_tiles, m_tiles, beta, g_batch_stride, dx_batch_stride, (float*)nullptr, TnGroups{}, BnLifEpi{});          \
-    else if (beta != 0.f)                                                                                              \
-      S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 1>), grid, dim3(64 * WMW * WNW), 0, s, w_pack, G, DX,   \
-                 Mo, Ki, N, KbW, n_tiles, m_tiles, beta, g_batch_stride, dx_batch_stride, (float*)nullptr, TnGroups{}, BnLifEpi{});          \
-    else if (part)                                                                                                     \
-      S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 0, 1, true>), grid, dim3(64 * WMW * WNW), 0, s, w_pack, \
-                 G, DX, Mo, Ki, N, KbW, n_tiles, m_tiles, beta, g_batch_stride, dx_batch_stride, part, TnGroups{}, BnLifEpi{});         \
-    else                                                                                                               \
-      S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 0>), grid, dim3(64 * WMW * WNW), 0, s, w_pack, G, DX,   \
-                 Mo, Ki, N, KbW, n_tiles, m_tiles, beta, g_batch_stride, dx_batch_stride, part, TnGroups{}, BnLifEpi{});                \
-  } while (0)
-  switch (c) {
-    case 1: S2F_PGD(2, 2, 2, 2); break;          // 128 x 128
-    case 2: S2F_PGD(1, 2, 2, 2); break;          // 64 x 128
-    case 3: S2F_PGD(1, 2, 4, 2); break;          // 128 x 128 on eight wavefronts (two per SIMD)
-    case 4: S2F_PGD(1, 1, 2, 4); break;          // 64 x 128 on eight wavefronts of 32 x 32
-    case 5: S2F_PGD(1, 1, 1, 4); break;          // 32 x 128 on four wavefronts of 32 x 32: twice the workgroups of cfg 2
-#define S2F_PGD2(MI, NJ, WMW, WNW) S2F_PGD3(MI, NJ, WMW, WNW, 2)
-#define S2F_PGD3(MI, NJ, WMW, WNW, KSV)                                                                                 \
-  do {                                                                                                                 \
-    S2F_REQUIRE(zsplit == 1 && beta == 0.f, S2F_EINVAL, "s2f_pgemm_dx_f32: cfg %d is the plain store form", c);           \
-    const int m_tiles = (Ki + 32 * MI * WMW - 1) / (32 * MI * WMW);                                                    \
-    if (part)                                                                                                          \
-      S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 0, KSV, true>), dim3(n_tiles * m_tiles, batch, 1),      \
-                 dim3(64 * WMW * WNW), 0, s, w_pack, G, DX, Mo, Ki, N, KbW, n_tiles, m_tiles, beta, g_batch_stride,      \
-                 dx_batch_stride, part, TnGroups{}, BnLifEpi{});                                                                       \
-    else                                                                                                               \
-      S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 0, KSV>), dim3(n_tiles * m_tiles, batch, 1),            \
-                 dim3(64 * WMW * WNW), 0, s, w_pack, G, DX, Mo, Ki, N, KbW, n_tiles, m_tiles, beta, g_batch_stride,      \
-                 dx_batch_stride, part, TnGroups{}, BnLifEpi{});                                                                       \
-  } while (0)
-    case 7: S2F_PGD2(1, 1, 2, 4); break;         // cfg 4 with 32-row steps (half the barriers per MFMA)
-    case 8: S2F_PGD2(1, 2, 2, 2); break;         // cfg 2 with 32-row steps
-    case 9: S2F_PGD2(1, 2, 4, 2); break;         // cfg 3 with 32-row steps
-    case 10: S2F_PGD3(1, 1, 2, 4, 4); break;     // cfg 4 with 64-row steps (144 KB of LDS: one workgroup per CU)
-#undef S2F_PGD3
-#undef S2F_PGD2
-    default: S2F_REQUIRE(false, S2F_EINVAL, "s2f_pgemm_dx_f32: unknown cfg %d", c);
-  }
-#undef S2F_PGD
+  S2F_REQUIRE(c < 7 || c > 10 || (zsplit == 1 && beta == 0.f), S2F_EINVAL, "s2f_pgemm_dx_f32: cfg %d is the plain store form", c);
+  const bool ok = launch_pg_tn(c, zsplit > 1 ? 2 : beta != 0.f ? 1 : 0, false, s, w_pack, G, DX, batch, zsplit, Mo, Ki, N, beta,
+                               g_batch_stride, dx_batch_stride, part, TnGroups{}, BnLifEpi{});
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_pgemm_dx_f32: unknown cfg %d", c);
   return s2f_check_launch("s2f_pgemm_dx_f32");
 }
 
@@ -1744,25 +1721,13 @@ extern "C" int s2f_dense_gemm_bn_lif_fwd(const uint16_t* const* w_packs, int gro
               reinterpret_cast<unsigned short*>(y_bf16), reinterpret_cast<unsigned long long*>(stats), eps, vth, (float)D,
               1.0f / (float)D};
   hipStream_t s = (hipStream_t)stream;
-  const int KbW = (M + PK - 1) / PK, n_tiles = (N + 127) / 128;
+  const int n_tiles = (N + 127) / 128;
   const int64_t out_bs = (int64_t)groups * M * N;
   const bool wide = M > 64 && (int64_t)n_tiles * batch * ((M + 127) / 128) >= 192;
-#define S2F_PGE(MI, NJ, WMW, WNW, KSV)                                                                                   \
-  do {                                                                                                                  \
-    const int m_tiles = (M + 32 * MI * WMW - 1) / (32 * MI * WMW);                                                      \
-    S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 3, KSV, false, true>), dim3(n_tiles * m_tiles, batch, groups),    \
-               dim3(64 * WMW * WNW), 0, s, grp.wp[0], X, (float*)nullptr, K, M, N, KbW, n_tiles, m_tiles, 0.f, x_batch_stride,  \
-               out_bs, (float*)nullptr, grp, ep);                                                                       \
-  } while (0)
-  if (M <= 32)
-    S2F_PGE(1, 1, 1, 4, 1);
-  else if (wide)
-    S2F_PGE(1, 2, 4, 2, 2);
-  else if (K >= 128 && (int64_t)n_tiles * batch * ((M + 63) / 64) * groups <= 512)
-    S2F_PGE(1, 1, 2, 4, 4);          // 64-row steps for the launches of one workgroup per CU or less (as s2f_pgemm_dx_f32's cfg 10)
-  else
-    S2F_PGE(1, 1, 2, 4, 2);
-#undef S2F_PGE
+  // 64-row steps (cfg 10) for the launches of one workgroup per CU or less (as s2f_pgemm_dx_f32)
+  const int c = M <= 32 ? 5 : wide ? 9 : (K >= 128 && (int64_t)n_tiles * batch * ((M + 63) / 64) * groups <= 512) ? 10 : 7;
+  const bool ok = launch_pg_tn(c, 3, true, s, grp.wp[0], X, nullptr, batch, groups, K, M, N, 0.f, x_batch_stride, out_bs, nullptr, grp, ep);
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_dense_gemm_bn_lif_fwd: no kernel instance for cfg %d", c);
   return s2f_check_launch("s2f_dense_gemm_bn_lif_fwd");
 }
 
@@ -1784,27 +1749,11 @@ extern "C" int s2f_pgemm_dx_f32_grouped(const uint16_t* const* w_packs, int grou
   grp.g_stride = g_group_stride;
   grp.dx_stride = dx_group_stride;
   grp.part_stride = partials_group_stride;
-  hipStream_t s = (hipStream_t)stream;
-  const int KbW = (Ki + PK - 1) / PK, n_tiles = (N + 127) / 128;
+  const int n_tiles = (N + 127) / 128;
   // the tile rule of the single product (s2f_pgemm_dx_f32), per group
   const bool wide = Ki > 64 && (int64_t)n_tiles * batch * ((Ki + 127) / 128) >= 192;
-#define S2F_PGG(MI, NJ, WMW, WNW, KSV)                                                                                   \
-  do {                                                                                                                  \
-    const int m_tiles = (Ki + 32 * MI * WMW - 1) / (32 * MI * WMW);                                                     \
-    const dim3 grid(n_tiles * m_tiles, batch, groups);                                                                  \
-    if (bn_partials)                                                                                                    \
-      S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 0, KSV, true, true>), grid, dim3(64 * WMW * WNW), 0, s,  \
-                 grp.wp[0], G, DX, Mo, Ki, N, KbW, n_tiles, m_tiles, 0.f, g_batch_stride, dx_batch_stride, bn_partials, grp, BnLifEpi{}); \
-    else                                                                                                                \
-      S2F_LAUNCH(true, true, (pg_tn_f32_kernel<MI, NJ, WMW, WNW, 0, KSV, false, true>), grid, dim3(64 * WMW * WNW), 0, s, \
-                 grp.wp[0], G, DX, Mo, Ki, N, KbW, n_tiles, m_tiles, 0.f, g_batch_stride, dx_batch_stride, bn_partials, grp, BnLifEpi{}); \
-  } while (0)
-  if (Ki <= 32)
-    S2F_PGG(1, 1, 1, 4, 1);
-  else if (wide)
-    S2F_PGG(1, 2, 4, 2, 1);
-  else
-    S2F_PGG(1, 1, 2, 4, 2);
-#undef S2F_PGG
+  const bool ok = launch_pg_tn(Ki <= 32 ? 5 : wide ? 3 : 7, 0, true, (hipStream_t)stream, grp.wp[0], G, DX, batch, groups, Mo, Ki, N, 0.f, g_batch_stride,
+               dx_batch_stride, bn_partials, grp, BnLifEpi{});
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_pgemm_dx_f32_grouped: no kernel instance");
   return s2f_check_launch("s2f_pgemm_dx_f32_grouped");
 }

@@ -295,13 +295,12 @@ extern "C" int s2f_resize_fwd(const float* x, float* y, int64_t planes, int64_t 
   const dim3 grid((unsigned)((W + kStrip - 1) / kStrip), (unsigned)((H + rows_per_wg - 1) / rows_per_wg), (unsigned)gz);
   const bool vec = (W % 4) == 0 && s2f_aligned16(y);
   hipStream_t s = (hipStream_t)stream;
-#define S2F_RESIZE_GO(V, S) \
-  hipLaunchKernelGGL((resize_fwd_kernel<V, S>), grid, dim3(256), 0, s, x, y, planes, wd, h, w, H, W, ax, ay, rows_per_wg)
-  if (vec && sig) S2F_RESIZE_GO(true, true);
-  else if (vec) S2F_RESIZE_GO(true, false);
-  else if (sig) S2F_RESIZE_GO(false, true);
-  else S2F_RESIZE_GO(false, false);
-#undef S2F_RESIZE_GO
+  s2f_dispatch_bool(vec, [&](auto v) {
+    s2f_dispatch_bool(sig, [&](auto sg) {
+      hipLaunchKernelGGL((resize_fwd_kernel<v.value, sg.value>), grid, dim3(256), 0, s, x, y, planes, wd, h, w, H, W, ax, ay,
+                         rows_per_wg);
+    });
+  });
   return s2f_check_launch("s2f_resize_fwd");
 }
 

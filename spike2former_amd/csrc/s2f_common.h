@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include "../../include/s2f.h"
+#include "s2f_dispatch.h"
 
 #define S2F_WAVE 64
 

@@ -302,6 +302,15 @@ __global__ __launch_bounds__(64 * NW) void apply_kernel(Operand<TX> OX, const fl
   }
 }
 
+// Workgroup shapes of apply_kernel: JC rows per wave (a multiple of 4 that covers d / NW) on NW waves.
+struct ApplyShape {
+  int jc, nw;
+};
+constexpr ApplyShape kApplyShapes[] = {
+    {4, 8}, {8, 8},                    // eight waves: d <= 32, d <= 64
+    {4, 4}, {8, 4}, {12, 4}, {16, 4},  // four waves: d <= 16, 32, 48, 64
+};
+
 template <bool TRANS, typename TX, bool LO = false>
 void launch_apply(Operand<TX> x, const float* m, float* y, int64_t y_batch_stride, int TB, int heads, int d, int N, float alpha,
                   hipStream_t s, LifOut lo = LifOut{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f}) {
@@ -310,22 +319,12 @@ void launch_apply(Operand<TX> x, const float* m, float* y, int64_t y_batch_strid
   const bool wide = (int64_t)grid.x * grid.y <= 1024 && d > 8;
   const int nw = wide ? 8 : 4;
   const int jc = ((d + nw - 1) / nw + 3) / 4 * 4;     // rows per wave, rounded up to a multiple of 4
-#define S2F_AP(JCV, NWV) \
-  hipLaunchKernelGGL((apply_kernel<TRANS, JCV, TX, NWV, LO>), grid, dim3(64 * NWV), 0, s, x, m, y, y_batch_stride, heads, d, N, alpha, lo)
-  if (wide) {
-    if (jc <= 4)
-      S2F_AP(4, 8);
-    else
-      S2F_AP(8, 8);
-  } else if (jc <= 4)
-    S2F_AP(4, 4);
-  else if (jc <= 8)
-    S2F_AP(8, 4);
-  else if (jc <= 12)
-    S2F_AP(12, 4);
-  else
-    S2F_AP(16, 4);
-#undef S2F_AP
+  // the last shape of a wave count takes every larger d as well (the callers bound d)
+  s2f_dispatch<kApplyShapes>([&](const ApplyShape& e) { return e.nw == nw && (jc <= e.jc || e.jc == (wide ? 8 : 16)); }, [&](auto i) {
+    constexpr ApplyShape A = kApplyShapes[i];
+    hipLaunchKernelGGL((apply_kernel<TRANS, A.jc, TX, A.nw, LO>), grid, dim3(64 * A.nw), 0, s, x, m, y, y_batch_stride, heads, d, N,
+                       alpha, lo);
+  });
 }
 
 

@@ -55,3 +55,23 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert b"null" in lib.s2f_last_error()
     assert lib.s2f_dcnv3_fwd(1, 1, 1, 1, 0, 4, 4, 1, 4, 3, 3, 1, 1, 1, 1, 1, 1, 1.0, None) == -1
     assert lib.s2f_sdsa_fwd(1, 1, 1, 1, 1, 1, 8, 65, 4, 4, 1.0, None) == -1     # head dim > 64
+
+
+def test_unknown_tile_cfg_is_an_error_before_any_launch():
+    """Every entry point whose `cfg` selects a tile from a table refuses a value that is not in the table: S2F_EINVAL and
+    "unknown cfg", after the pointer / size preconditions (aligned dummy pointers, valid sizes) and before any launch, so no GPU
+    is needed.  (The cfg of the s2f_spike_*_dw_pipe entry points is a schedule flag / bit set, not a table index: every value
+    of it runs.)"""
+    from spike2former_amd._lib import lib
+    P = 1 << 20          # a 16-byte aligned dummy address: never dereferenced on the host
+    calls = {
+        # (Mo = 64 keeps the contraction unsplit: a split would clear DX with a launch before the tile is chosen)
+        "s2f_pgemm_nn_bf16": lambda: lib.s2f_pgemm_nn_bf16(P, P, None, P, 1, 64, 128, 64, 3, 99, None),
+        "s2f_pgemm_dx_f32": lambda: lib.s2f_pgemm_dx_f32(P, P, 0, P, 0, 1, 64, 64, 128, 0.0, 99, None),
+        "s2f_pgemm_dx_split": lambda: lib.s2f_pgemm_dx_split(P, P, 64 * 128, P, 1, 64, 64, 128, 99, None),
+        "s2f_pgemm_conv3x3_bf16": lambda: lib.s2f_pgemm_conv3x3_bf16(P, P, None, P, 1, 64, 32, 16, 16, 99, None),
+        "s2f_pgemm_conv3x3_f32": lambda: lib.s2f_pgemm_conv3x3_f32(P, P, P, 1, 64, 32, 16, 16, 99, None),
+    }
+    for name, call in calls.items():
+        assert call() == -1, name          # S2F_EINVAL
+        assert b"unknown cfg" in lib.s2f_last_error(), (name, lib.s2f_last_error())
