@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 36
+#define S2F_ABI_VERSION 37
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -547,6 +547,58 @@ int s2f_tta_finish(float* acc, int64_t* label, float* label_f, int K, int64_t HW
 #define S2F_SEG_REDUCE_ZERO_LABEL 1
 int s2f_seg_hist(const void* pred, int pred_dtype, const void* label, int label_dtype, int64_t label_row_stride,
                  int64_t label_pixel_stride, int W, int64_t HW, int K, int ignore_index, int flags, int64_t* totals, void* stream);
+
+/* ---- training augmentation: the configs' train_pipeline + SegDataPreProcessor on the device (csrc/augment.hip, ABI 37) ------------
+ * RandomResize(keep_ratio) -> RandomCrop(cat_max_ratio) -> RandomFlip -> PhotoMetricDistortion (mmseg datasets/transforms/
+ * transforms.py:215-331, 575-737; the resize itself is mmcv's) and SegDataPreProcessor's training branch (channel swap,
+ * (x - mean) / std, pad right / bottom to the crop size) as two launches, from the batch's raw pictures to the step's static inputs.
+ * The random numbers are drawn by the caller and arrive in the table; the kernels are functions of their inputs, allocate nothing
+ * and synchronise nothing: capturable in a hipGraph (a single chain).
+ * data: `data_bytes` device bytes holding, per image and back to back with NO alignment, a uint8 HWC BGR picture [h0, w0, 3] and a
+ * uint8 annotation [h0, w0].  params: B table entries in device memory (8-byte aligned):
+ *   img_off, seg_off : byte offsets of the two into data          h0, w0 : source size          H, W : size after the resize
+ *   crop_y/x[11]     : candidate crop origins in the resized picture, each in [0, max(H - Hc, 0)] x [0, max(W - Wc, 0)]
+ *   flip             : horizontal flip of the cropped window
+ *   bright_on/_beta, mode, contrast_on/_alpha, sat_on/_alpha, hue_on/_delta : PhotoMetricDistortion's draws
+ * An entry that does not fit data (or has a non-positive size) yields an all-padding image and flags 0; origins outside their
+ * range are clamped into it: no load leaves data whatever the table holds.
+ *
+ * s2f_aug_crop_stats: flags [B, 11] int32 <- RandomCrop.crop_bbox's test of every candidate window (rows crop_y .. + min(Hc, H),
+ * columns crop_x .. + min(Wc, W)) of the NEAREST-resized annotation, source pixel ((y h0) / H, (x w0) / W) in exact integer
+ * arithmetic: over the labels != ignore_index at least two are present and max / sum < cat_max_ratio (an fp64 quotient of the
+ * integer counts, as numpy forms it).  reduce_zero_label maps each sample first (0 -> 255, 255 -> 255, l -> l - 1).
+ *
+ * s2f_aug_apply: writes EVERY element of inputs [B, 3, Hc, Wc] fp32 and seg [B, Hc, Wc] uint8 once (the outputs are never read).
+ * The candidate is the first of 0 .. 9 whose flag is set, else 10 (flags? NULL: candidate 0 -- cat_max_ratio >= 1 needs no first
+ * launch).  Output pixel (y, x) with y < hv = min(Hc, H), x < wv = min(Wc, W): resized pixel (crop_y + y, crop_x + (flip ? wv - 1 - x
+ * : x)); bilinear sample of the picture with half-pixel centres and no antialias (the arithmetic of s2f_resize_fwd, scale = in /
+ * out), rounded to nearest into uint8; PhotoMetricDistortion in the reference's order with its quantisation after every stage
+ * (convert = fp32(v) * alpha + beta, clipped to 0 .. 255, TRUNCATED; brightness, contrast here if mode == 1, saturation, hue, contrast
+ * here otherwise; saturation and hue each one BGR -> HSV -> BGR round trip on uint8 values); channel c of the output is channel
+ * (bgr_to_rgb ? 2 - c : c) of that, (v - mean_c) / std_c with an IEEE divide (mean 0, std 1: none).  The map takes the nearest sample
+ * with the label reduction.  Elsewhere: pad_val / seg_pad_val.
+ * The 8-bit HSV used here (the reference calls OpenCV): V = max, S = 255 (V - min) / V, hue by 60-degree sectors (V == R, then G, then
+ * B) halved into 0 .. 179 with 180 -> 0, each rounded to nearest; inverse: h / 30 -> sector i and fraction f, p = V (1 - s), q = V (1 -
+ * s f), t = V (1 - s (1 - f)) with s = S / 255, rounded to nearest.  Every step is one fp32 operation (tests/aug_ref.py restates them).
+ * Bounds: 0 < B <= 65535, 0 < Hc, Wc <= S2F_AUG_MAX_CROP.  16-byte stores when Wc % 4 == 0 and inputs is 16-byte (seg 4-byte)
+ * aligned, scalar stores otherwise. */
+#define S2F_AUG_CANDIDATES 11
+#define S2F_AUG_MAX_CROP 4096
+typedef struct S2fAugParams {
+  int64_t img_off, seg_off;
+  int32_t h0, w0, H, W;
+  int32_t crop_y[S2F_AUG_CANDIDATES], crop_x[S2F_AUG_CANDIDATES];
+  int32_t flip;
+  int32_t bright_on, mode, contrast_on, sat_on, hue_on, hue_delta;
+  float bright_beta, contrast_alpha, sat_alpha;
+} S2fAugParams;
+/* sizeof(S2fAugParams): what a binding checks its mirror of the layout against */
+int s2f_aug_param_bytes(void);
+int s2f_aug_crop_stats(const uint8_t* data, int64_t data_bytes, const S2fAugParams* params, int B, int Hc, int Wc, int ignore_index,
+                       int reduce_zero_label, double cat_max_ratio, int* flags, void* stream);
+int s2f_aug_apply(const uint8_t* data, int64_t data_bytes, const S2fAugParams* params, const int* flags, int B, int Hc, int Wc,
+                  float mean0, float mean1, float mean2, float std0, float std1, float std2, int bgr_to_rgb, float pad_val,
+                  int seg_pad_val, int reduce_zero_label, float* inputs, uint8_t* seg, void* stream);
 
 /* ---- batched transposition of the last two dimensions: x [B, R, C] -> y [B, C, R] (fp32) -----------------------------------
  * Replaces the `.permute(0, 1, 3, 4, 2)` / `.permute(0, 1, 4, 2, 3)` copies around the DCNv3 sampling core

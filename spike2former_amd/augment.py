@@ -1,0 +1,277 @@
+"""`TrainAugment`: the shipped configs' `train_pipeline` -- RandomResize(keep_ratio) -> RandomCrop(cat_max_ratio) -> RandomFlip ->
+PhotoMetricDistortion (mmseg/datasets/transforms/transforms.py:215-331, 575-737; the resize is mmcv's) -- and the training branch of
+`SegDataPreProcessor` as two HIP launches (csrc/augment.hip) from the decoded uint8 pictures of a batch to the [B, 3, Hc, Wc] fp32 /
+[B, Hc, Wc] uint8 tensors a training step replays on.  File loading is not here: the caller hands in decoded
+BGR pictures and raw annotations.
+
+    aug = TrainAugment.from_cfg(train_pipeline, data_preprocessor, batch_size=2, seed=0)
+    step = GraphedHungarianStep(model, example_in, example_seg, red, assign="device")
+    for images, segs in loader:                                   # lists of uint8 [h0, w0, 3] BGR / [h0, w0] arrays
+        aug(images, segs, out=(step.static_in, step.static_seg))  # one H2D copy + two launches, queued; nothing waits for the GPU
+        losses = step()
+
+The host draws the random numbers (`draw`), the kernels are functions of the parameter table.  Two deliberate differences from the
+reference's stream of random numbers, neither of which changes a distribution:
+  * `draw` always consumes the SAME number of variates per image (the ratio, eleven crop origins, the flip and every photometric
+    switch and value, used or not), where the reference draws a new crop origin only after a refused one and a photometric value
+    only behind its switch.  The eleven origins are independent and identically distributed and the chosen one is the first that
+    passes among the first ten, else the eleventh: the distribution of the chosen crop is the reference's.
+  * the generator is a `numpy.random.Generator` seeded from (seed, rank), not mmcv's use of the global `numpy.random` state: a run
+    here does not reproduce the reference's sequence of augmentations, only its distribution."""
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+
+CANDIDATES = ops.AUG_CANDIDATES
+# include/s2f.h S2fAugParams, field for field (ops.AUG_PARAM_BYTES is the library's sizeof)
+PARAM_DTYPE = np.dtype([
+    ("img_off", "<i8"), ("seg_off", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("H", "<i4"), ("W", "<i4"),
+    ("crop_y", "<i4", (CANDIDATES,)), ("crop_x", "<i4", (CANDIDATES,)), ("flip", "<i4"),
+    ("bright_on", "<i4"), ("mode", "<i4"), ("contrast_on", "<i4"), ("sat_on", "<i4"), ("hue_on", "<i4"), ("hue_delta", "<i4"),
+    ("bright_beta", "<f4"), ("contrast_alpha", "<f4"), ("sat_alpha", "<f4")])
+assert PARAM_DTYPE.itemsize == ops.AUG_PARAM_BYTES, "PARAM_DTYPE does not mirror S2fAugParams"
+VARIATES_PER_IMAGE = 2 * CANDIDATES + 11
+
+PHOTOMETRIC_DEFAULTS = dict(brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18)
+_PIPELINE_ORDER = ("LoadImageFromFile", "LoadAnnotations", "RandomResize", "RandomCrop", "RandomFlip", "PhotoMetricDistortion",
+                   "PackSegInputs")
+
+
+def resized_size(h0, w0, scale, ratio):
+    """mmcv RandomResize(scale, ratio_range, keep_ratio=True) at the drawn ratio -> (H, W): scale = (int(s0 r), int(s1 r)),
+    f = min(long / max(h0, w0), short / min(h0, w0)), (int(h0 f + 0.5), int(w0 f + 0.5)) (mmcv.image.geometric.rescale_size)"""
+    s = (int(scale[0] * ratio), int(scale[1] * ratio))
+    f = min(max(s) / max(h0, w0), min(s) / min(h0, w0))
+    return int(h0 * f + 0.5), int(w0 * f + 0.5)
+
+
+def _pick(u, n):
+    """a uniform variate u in [0, 1) -> an integer in [0, n)"""
+    return min(int(u * n), n - 1)
+
+
+def _default_rank():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank()
+    return int(os.environ.get("RANK", "0"))
+
+
+def _only(cfg, allowed, what):
+    extra = sorted(set(cfg) - set(allowed) - {"type"})
+    if extra:
+        raise NotImplementedError(f"TrainAugment: {what} option(s) {extra} are not implemented on the device")
+
+
+class TrainAugment:
+    def __init__(self, scale=(2048, 512), ratio_range=(0.5, 2.0), crop_size=(512, 512), cat_max_ratio=0.75, flip_prob=0.5,
+                 photometric=True, reduce_zero_label=False, ignore_index=255, mean=None, std=None, bgr_to_rgb=False, pad_val=0,
+                 seg_pad_val=255, batch_size=2, max_source_pixels=2048 * 1024, device="cuda", seed=0, rank=None):
+        """scale / ratio_range: RandomResize's (scale None: no resize; ratio_range None: ratio 1); crop_size (h, w), cat_max_ratio,
+        ignore_index: RandomCrop's; flip_prob: RandomFlip's (horizontal); photometric: True (PhotoMetricDistortion's defaults), a
+        dictionary of its arguments, or None / False; reduce_zero_label: LoadAnnotations'; mean, std, bgr_to_rgb, pad_val,
+        seg_pad_val: SegDataPreProcessor's (its `size` is crop_size).  batch_size images of at most max_source_pixels pixels each
+        fit the staging buffers (4 bytes per pixel: the picture and its annotation).  rank: the data-parallel rank the generator is
+        seeded with next to `seed` (default: the process group's, else $RANK, else 0)."""
+        self.scale = None if scale is None else (int(scale[0]), int(scale[1]))
+        self.ratio_range = None if ratio_range is None else (float(ratio_range[0]), float(ratio_range[1]))
+        self.crop_size = (int(crop_size), int(crop_size)) if isinstance(crop_size, int) else (int(crop_size[0]), int(crop_size[1]))
+        if not (0 < self.crop_size[0] <= ops.AUG_MAX_CROP and 0 < self.crop_size[1] <= ops.AUG_MAX_CROP):
+            raise ValueError(f"crop_size {self.crop_size} outside 1 .. {ops.AUG_MAX_CROP}")
+        self.cat_max_ratio, self.flip_prob = float(cat_max_ratio), float(flip_prob or 0.0)
+        if photometric is True:
+            photometric = {}
+        self.photometric = None if photometric in (None, False) else {**PHOTOMETRIC_DEFAULTS, **photometric}
+        if self.photometric is not None:
+            _only(self.photometric, PHOTOMETRIC_DEFAULTS, "PhotoMetricDistortion")
+        self.reduce_zero_label, self.ignore_index = bool(reduce_zero_label), int(ignore_index)
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std go together")
+        self.mean = None if mean is None else [float(v) for v in mean]
+        self.std = None if std is None else [float(v) for v in std]
+        self.bgr_to_rgb, self.pad_val, self.seg_pad_val = bool(bgr_to_rgb), float(pad_val), int(seg_pad_val)
+        self.batch_size, self.max_source_pixels = int(batch_size), int(max_source_pixels)
+        if self.batch_size <= 0 or self.max_source_pixels <= 0:
+            raise ValueError("batch_size and max_source_pixels are positive")
+        self.device = torch.device(device)
+        self.seed, self.rank = int(seed), int(_default_rank() if rank is None else rank)
+        self.rng = np.random.default_rng(np.random.SeedSequence([self.seed, self.rank]))
+        # the table first (its size is a multiple of 16: the packed bytes behind it start aligned), then the pixels
+        self._table_cap = (self.batch_size * PARAM_DTYPE.itemsize + 15) // 16 * 16
+        self._data_cap = self.batch_size * self.max_source_pixels * 4
+        self._pin = self._dev = self._flags = self._inputs = self._seg = self._copied = None
+        self._staged = 0
+
+    # ------------------------------------------------------------------------------------------------ configuration
+    @classmethod
+    def from_cfg(cls, train_pipeline, data_preprocessor, **kwargs):
+        """train_pipeline: the list of transform dictionaries of an mmseg config (LoadImageFromFile, LoadAnnotations, RandomResize,
+        RandomCrop, RandomFlip, PhotoMetricDistortion, PackSegInputs, in this order; LoadImageFromFile only marks where the caller's
+        decoded pictures enter); data_preprocessor: the model's SegDataPreProcessor dictionary.  Any other transform, order or option
+        raises NotImplementedError.  kwargs: batch_size, max_source_pixels, device, seed, rank."""
+        a = dict(scale=None, ratio_range=None, cat_max_ratio=1.0, flip_prob=0.0, photometric=None)
+        seen = []
+        for t in train_pipeline:
+            kind = t.get("type")
+            if kind not in _PIPELINE_ORDER:
+                raise NotImplementedError(f"TrainAugment: transform {kind!r} is not implemented on the device")
+            if seen and _PIPELINE_ORDER.index(kind) <= _PIPELINE_ORDER.index(seen[-1]):
+                raise NotImplementedError(f"TrainAugment: {kind} after {seen[-1]}: the kernels apply the transforms in the order "
+                                          f"{' -> '.join(_PIPELINE_ORDER)}")
+            seen.append(kind)
+            if kind in ("LoadImageFromFile", "PackSegInputs"):
+                _only(t, (), kind)
+            elif kind == "LoadAnnotations":
+                _only(t, ("reduce_zero_label",), kind)
+                a["reduce_zero_label"] = bool(t.get("reduce_zero_label", False))
+            elif kind == "RandomResize":
+                _only(t, ("scale", "ratio_range", "keep_ratio"), kind)
+                if not t.get("keep_ratio", False) or not isinstance(t.get("scale"), (tuple, list)) or len(t["scale"]) != 2 \
+                        or not all(isinstance(v, int) for v in t["scale"]):
+                    raise NotImplementedError("TrainAugment: RandomResize needs keep_ratio=True and one (long, short) scale")
+                a["scale"], a["ratio_range"] = tuple(t["scale"]), t.get("ratio_range")
+            elif kind == "RandomCrop":
+                _only(t, ("crop_size", "cat_max_ratio", "ignore_index"), kind)
+                a["crop_size"] = t["crop_size"]
+                a["cat_max_ratio"], a["ignore_index"] = t.get("cat_max_ratio", 1.0), t.get("ignore_index", 255)
+            elif kind == "RandomFlip":
+                _only(t, ("prob", "direction"), kind)
+                if t.get("direction", "horizontal") != "horizontal" or isinstance(t.get("prob"), (list, tuple)):
+                    raise NotImplementedError("TrainAugment: RandomFlip is implemented for one probability, horizontal")
+                a["flip_prob"] = t.get("prob") or 0.0
+            elif kind == "PhotoMetricDistortion":
+                _only(t, PHOTOMETRIC_DEFAULTS, kind)
+                a["photometric"] = {k: v for k, v in t.items() if k != "type"}
+        if "RandomCrop" not in seen:
+            raise NotImplementedError("TrainAugment: a train_pipeline without RandomCrop has no fixed output size")
+        p = dict(data_preprocessor)
+        if p.pop("type", "SegDataPreProcessor") != "SegDataPreProcessor":
+            raise NotImplementedError("TrainAugment: the data preprocessor is a SegDataPreProcessor")
+        _only(p, ("mean", "std", "bgr_to_rgb", "rgb_to_bgr", "pad_val", "seg_pad_val", "size", "test_cfg", "batch_augments",
+                  "size_divisor"), "SegDataPreProcessor")
+        if p.get("batch_augments") is not None or p.get("size_divisor") is not None:
+            raise NotImplementedError("TrainAugment: SegDataPreProcessor batch_augments / size_divisor are not implemented")
+        crop = a["crop_size"]
+        crop = (crop, crop) if isinstance(crop, int) else tuple(crop)
+        if p.get("size") is not None and tuple(p["size"]) != crop:
+            raise NotImplementedError(f"TrainAugment: SegDataPreProcessor size {tuple(p['size'])} is not the crop size {crop}")
+        if p.get("bgr_to_rgb") and p.get("rgb_to_bgr"):
+            raise ValueError("`bgr2rgb` and `rgb2bgr` cannot be set to True at the same time")
+        a.update(mean=p.get("mean"), std=p.get("std"), bgr_to_rgb=bool(p.get("bgr_to_rgb") or p.get("rgb_to_bgr")),
+                 pad_val=p.get("pad_val", 0), seg_pad_val=p.get("seg_pad_val", 255))
+        return cls(**a, **kwargs)
+
+    # ------------------------------------------------------------------------------------------------ random numbers
+    def draw(self, shapes):
+        """shapes: [(h0, w0)] of the batch's pictures -> their parameter table, a numpy array of PARAM_DTYPE (the offsets are filled
+        in by `stage`).  VARIATES_PER_IMAGE uniform variates per image, whatever the configuration uses of them."""
+        params = np.zeros(len(shapes), PARAM_DTYPE)
+        Hc, Wc = self.crop_size
+        ph = self.photometric
+        for p, (h0, w0) in zip(params, shapes):
+            u = self.rng.random(VARIATES_PER_IMAGE)
+            h0, w0 = int(h0), int(w0)
+            if self.scale is None:
+                H, W = h0, w0
+            else:
+                lo, hi = self.ratio_range or (1.0, 1.0)
+                H, W = resized_size(h0, w0, self.scale, u[0] * (hi - lo) + lo)          # RandomResize._random_scale
+            p["h0"], p["w0"], p["H"], p["W"] = h0, w0, H, W
+            my, mx = max(H - Hc, 0), max(W - Wc, 0)
+            for c in range(CANDIDATES):          # generate_crop_bbox: randint(0, margin + 1) for the row, then for the column
+                p["crop_y"][c], p["crop_x"][c] = _pick(u[1 + 2 * c], my + 1), _pick(u[2 + 2 * c], mx + 1)
+            v = u[1 + 2 * CANDIDATES:]
+            p["flip"] = int(v[0] < self.flip_prob)
+            if ph is not None:          # random.randint(2) switches, uniform values; hue: randint(-delta, delta), upper end open
+                p["bright_on"], p["bright_beta"] = _pick(v[1], 2), (2 * v[2] - 1) * ph["brightness_delta"]
+                p["mode"] = _pick(v[3], 2)
+                lo, hi = ph["contrast_range"]
+                p["contrast_on"], p["contrast_alpha"] = _pick(v[4], 2), lo + v[5] * (hi - lo)
+                lo, hi = ph["saturation_range"]
+                p["sat_on"], p["sat_alpha"] = _pick(v[6], 2), lo + v[7] * (hi - lo)
+                d = int(ph["hue_delta"])
+                p["hue_on"], p["hue_delta"] = _pick(v[8], 2), (-d + _pick(v[9], 2 * d)) if d > 0 else 0
+        return params
+
+    # ------------------------------------------------------------------------------------------------ device side
+    def _allocate(self):
+        if self.device.type != "cuda":
+            raise RuntimeError("TrainAugment runs on the GPU only (HIP kernels): there is no host route")
+        n = self._table_cap + self._data_cap
+        self._pin = torch.empty(n, dtype=torch.uint8).pin_memory()
+        self._dev = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self._flags = torch.zeros(self.batch_size, CANDIDATES, dtype=torch.int32, device=self.device)
+        self._copied = torch.cuda.Event()
+
+    def stage(self, images, segs, params=None):
+        """Packs the pictures, the annotations and the table into the pinned staging buffer and queues ONE host-to-device copy on the
+        current stream.  images: uint8 [h0, w0, 3] BGR arrays (numpy or CPU tensors); segs: uint8 [h0, w0].  -> params as staged."""
+        B = len(images)
+        if not 0 < B <= self.batch_size or len(segs) != B:
+            raise ValueError(f"{B} pictures, {len(segs)} annotations for a batch size of {self.batch_size}")
+        images = [np.ascontiguousarray(np.asarray(i)) for i in images]
+        segs = [np.ascontiguousarray(np.asarray(s)) for s in segs]
+        params = self.draw([i.shape[:2] for i in images]) if params is None else np.array(params, dtype=PARAM_DTYPE)
+        if params.shape != (B,):
+            raise ValueError(f"{params.shape} parameter entries for {B} pictures")
+        Hc, Wc = self.crop_size
+        off = 0
+        for i, s, p in zip(images, segs, params):
+            if i.dtype != np.uint8 or s.dtype != np.uint8 or i.ndim != 3 or i.shape[2] != 3 or s.shape != i.shape[:2]:
+                raise ValueError("pictures are uint8 [h0, w0, 3], annotations uint8 [h0, w0] of the same size")
+            h0, w0 = s.shape
+            if h0 * w0 > self.max_source_pixels or h0 * w0 == 0:
+                raise ValueError(f"a {h0} x {w0} picture does not fit max_source_pixels = {self.max_source_pixels}")
+            if (p["h0"], p["w0"]) != (h0, w0) or p["H"] <= 0 or p["W"] <= 0:
+                raise ValueError(f"parameter entry for a {p['h0']} x {p['w0']} picture resized to {p['H']} x {p['W']}, picture {h0} x {w0}")
+            my, mx = max(int(p["H"]) - Hc, 0), max(int(p["W"]) - Wc, 0)
+            if p["crop_y"].min() < 0 or p["crop_y"].max() > my or p["crop_x"].min() < 0 or p["crop_x"].max() > mx:
+                raise ValueError("a candidate crop origin lies outside [0, margin]")
+            p["img_off"], p["seg_off"] = off, off + 3 * h0 * w0
+            off += 4 * h0 * w0
+        if self._pin is None:
+            self._allocate()
+        self._copied.synchronize()          # the previous copy has left the staging buffer (a copy, not the step, is waited for)
+        pin = self._pin.numpy()
+        pin[:params.nbytes] = params.view(np.uint8)
+        d0 = self._table_cap
+        for i, s, p in zip(images, segs, params):
+            a, b = d0 + int(p["img_off"]), d0 + int(p["seg_off"])
+            pin[a:b] = i.reshape(-1)
+            pin[b:b + s.size] = s.reshape(-1)
+        n = d0 + off
+        self._dev[:n].copy_(self._pin[:n], non_blocking=True)
+        self._copied.record()
+        self._staged = B
+        return params
+
+    def launch(self, out=None, batch=None):
+        """The two launches on the current stream (one when cat_max_ratio >= 1) over what `stage` last copied; capturable in a
+        hipGraph (the table and the pixels are read from their static device buffers at replay time).  out = (inputs [B, 3, Hc, Wc]
+        fp32, seg [B, Hc, Wc] uint8) is written in place -- e.g. a step's (static_in, static_seg); None: persistent buffers of this
+        object.  -> (inputs, seg)."""
+        B = int(batch or self._staged)
+        if not 0 < B <= self.batch_size or self._dev is None:
+            raise RuntimeError("TrainAugment.launch before stage")
+        if out is None:
+            if self._inputs is None:
+                self._inputs = torch.empty(self.batch_size, 3, *self.crop_size, dtype=torch.float32, device=self.device)
+                self._seg = torch.empty(self.batch_size, *self.crop_size, dtype=torch.uint8, device=self.device)
+            out = (self._inputs[:B], self._seg[:B])
+        inputs, seg = out
+        if tuple(inputs.shape) != (B, 3, *self.crop_size) or tuple(seg.shape) != (B, *self.crop_size):
+            raise ValueError(f"out is {tuple(inputs.shape)} / {tuple(seg.shape)} for {B} pictures cropped to {self.crop_size}")
+        table, data = self._dev[:B * PARAM_DTYPE.itemsize], self._dev[self._table_cap:]
+        flags = None
+        if self.cat_max_ratio < 1.0:
+            flags = ops.aug_crop_stats(data, table, self._flags[:B], self.crop_size, self.ignore_index, self.reduce_zero_label,
+                                       self.cat_max_ratio)
+        return ops.aug_apply(data, table, flags, inputs, seg, self.mean, self.std, self.bgr_to_rgb, self.pad_val, self.seg_pad_val,
+                             self.reduce_zero_label)
+
+    def __call__(self, images, segs, params=None, out=None):
+        self.stage(images, segs, params)
+        return self.launch(out)

@@ -405,6 +405,62 @@ def tta_finish(acc, n_views, threshold=0.3):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ training augmentation
+AUG_CANDIDATES = 11                  # include/s2f.h S2F_AUG_CANDIDATES
+AUG_MAX_CROP = 4096                  # include/s2f.h S2F_AUG_MAX_CROP
+AUG_PARAM_BYTES = lib.s2f_aug_param_bytes()
+
+
+def _aug_cuda(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("spike2former_amd ops run on the GPU only (HIP kernels); got a CPU tensor")
+
+
+def _aug_buffers(data, params):
+    _aug_cuda(data, params)
+    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous(), "data: one contiguous uint8 byte buffer"
+    assert params.dtype == torch.uint8 and params.dim() == 1 and params.is_contiguous() and params.numel() % AUG_PARAM_BYTES == 0 \
+        and params.numel() > 0, f"params: B table entries of {AUG_PARAM_BYTES} bytes as one uint8 buffer"
+    return params.numel() // AUG_PARAM_BYTES
+
+
+def aug_crop_stats(data, params, flags, crop_size, ignore_index=255, reduce_zero_label=False, cat_max_ratio=0.75):
+    """flags int32 [B, 11] <- RandomCrop.crop_bbox's test of every candidate crop window of the nearest-resized annotations
+    (s2f_aug_crop_stats).  data: the batch's packed uint8 pictures and annotations; params: the B-entry table (S2fAugParams) as
+    bytes; both CUDA.  There is no other route: a CPU tensor raises."""
+    B = _aug_buffers(data, params)
+    _aug_cuda(flags)
+    assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B, AUG_CANDIDATES)
+    Hc, Wc = (int(v) for v in crop_size)
+    check(lib.s2f_aug_crop_stats(_ptr(data), data.numel(), _ptr(params), B, Hc, Wc, int(ignore_index), int(bool(reduce_zero_label)),
+                                 float(cat_max_ratio), _ptr(flags), _stream()), "s2f_aug_crop_stats")
+    return flags
+
+
+def aug_apply(data, params, flags, inputs, seg, mean=None, std=None, bgr_to_rgb=False, pad_val=0.0, seg_pad_val=255,
+              reduce_zero_label=False):
+    """inputs fp32 [B, 3, Hc, Wc] and seg uint8 [B, Hc, Wc] <- resize, chosen crop, flip, photometric distortion, channel swap,
+    normalisation and padding of every picture of the batch in one launch that writes every element once (s2f_aug_apply).
+    flags: what aug_crop_stats wrote, or None (candidate 0).  There is no other route: a CPU tensor raises."""
+    B = _aug_buffers(data, params)
+    _aug_cuda(inputs, seg)
+    assert inputs.dtype == torch.float32 and inputs.is_contiguous() and inputs.dim() == 4 and inputs.shape[:2] == (B, 3)
+    Hc, Wc = (int(v) for v in inputs.shape[-2:])
+    assert seg.dtype == torch.uint8 and seg.is_contiguous() and tuple(seg.shape) == (B, Hc, Wc)
+    if flags is not None:
+        _aug_cuda(flags)
+        assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B, AUG_CANDIDATES)
+    assert (mean is None) == (std is None), "mean and std go together"
+    m = [float(v) for v in mean] if mean is not None else [0.0] * 3
+    s = [float(v) for v in std] if std is not None else [1.0] * 3
+    assert len(m) == 3 and len(s) == 3
+    check(lib.s2f_aug_apply(_ptr(data), data.numel(), _ptr(params), _ptr(flags), B, Hc, Wc, *m, *s, int(bool(bgr_to_rgb)),
+                            float(pad_val), int(seg_pad_val), int(bool(reduce_zero_label)), _ptr(inputs), _ptr(seg), _stream()),
+          "s2f_aug_apply")
+    return inputs, seg
+
+
 # ------------------------------------------------------------------------------------------------ evaluation
 SEG_HIST_MAX_CLASSES = 2048          # include/s2f.h S2F_SEG_HIST_MAX_CLASSES
 _SEG_PRED_CODES = {torch.int64: 0, torch.float32: 1}
