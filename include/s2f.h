@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 37
+#define S2F_ABI_VERSION 38
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -171,6 +171,19 @@ int s2f_bn_act_bwd(const float* z, const float* conv_bias, const float* stat, co
                    const float* g_y, const float* g_v, const uint64_t* mask, double* sums_zeroed, float* gz,
                    float* g_residual, float* dgamma, float* dbeta, int64_t N, int64_t C, int64_t L, int training,
                    float vth, int D, void* stream);
+/* s2f_bn_act_fwd on [N, C, H * W] whose residual is the exact-2x bilinear up-sampling (s2f_upsample2x_fwd) of residual_lo
+ * [N * C, H/2, W/2] -- the top-down add of an FPN level: the apply kernel forms the up-sampled values from the low-resolution map
+ * itself (same expressions, same order, no contraction: u, spikes, mask, counters and statistics are bit-identical to the two
+ * launches) and the [N, C, H, W] fp32 map is neither written nor read.  Training mode with `sums` given, on the row-walking
+ * kernels: s2f_bn_up_ok(N, C, H, W, training, D) = 1 <=> H * W % 256 == 0, W % 4 == 0, 256 % W == 0 or W % 256 == 0, H even, D a
+ * power of two, not a single-pass shape; residual_lo 8-byte aligned.  Everything else: the two launches.  The backward is
+ * s2f_bn_act_bwd with g_residual, then s2f_upsample2x_bwd_add. */
+int s2f_bn_up_ok(int64_t N, int64_t C, int64_t H, int64_t W, int training, int D);
+int s2f_bn_act_up_fwd(const float* z, const float* conv_bias, const double* sums, float* stat_out, float* running_mean,
+                      float* running_var, int64_t* num_batches_tracked, const float* gamma, const float* beta,
+                      const float* residual_lo, float* u_out, const float* v_in, void* y, float* v_out, uint64_t* mask,
+                      uint64_t* stats, int64_t N, int64_t C, int64_t H, int64_t W, float momentum, float eps, int training,
+                      float vth, int D, int y_bf16, void* stream);
 
 /* Train-mode BatchNorm o BatchNorm as ONE kernel (every RepConv chain of the attention blocks ends in two: Sequential(RepConv(..,
  * BN), BN), mmseg/models/backbones/sdtv2.py:112-132, 280-296, 304-306).  With xhat = (z + b - mean) r the first BatchNorm gives
@@ -208,6 +221,14 @@ int s2f_col2im(const float* cols, float* gx, int N, int C, int H, int W, int kh,
  * output convolutions and DCNv3's dw_conv all read a neuron output); the arithmetic stays fp32. */
 int s2f_dwconv_fwd(const void* x, const float* w, const float* border, float* y, int N, int C, int H, int W, int K,
                    int pad, int x_bf16, void* stream);
+/* s2f_dwconv_fwd for K = 3, pad = 1, no border (the same y, bit for bit) that also stores the BatchNorm partials of y for the
+ * train-mode BatchNorm behind it: every workgroup reduces the outputs it stored to one fp32 (sum, sum of squares) pair -- wave
+ * shuffles and one LDS round in a fixed order, no atomics -- at partials[(c * P + n * tiles + tile) * 2 + {0, 1}],
+ * P = s2f_dwconv_stats_slots(N, H, W) = N * workgroups per plane (64 x 32 tiles for W % 4 == 0, W >= 128, H >= 32, else 32 x 32).
+ * s2f_bn_partials_finalize(partials, P, ...) turns them into the sums of s2f_bn_stats.  x aligned to four elements. */
+int64_t s2f_dwconv_stats_slots(int N, int H, int W);
+int s2f_dwconv_fwd_stats(const void* x, const float* w, float* y, float* partials, int64_t P, int N, int C, int H, int W,
+                         int x_bf16, void* stream);
 /* Eval mode (row f4): the stencil with the BatchNorm (running statistics) and the Q_IFNode that follow every depthwise convolution of
  * the path in its store -- u_out? = fp32 pre-activation, y_bf16? = bf16 spikes, stats? = firing counters; the fp32 convolution
  * output is never written.  Per-element expressions of s2f_bn_act_fwd in eval mode (bit-identical spikes). */

@@ -61,7 +61,8 @@ class Conv2d(nn.Conv2d):
             kh, kw = self.kernel_size
             if (self.groups == self.in_channels == self.out_channels and kh == kw and kh in (3, 5, 7) and bias is None
                     and self.stride == (1, 1) and self.dilation == (1, 1) and self.padding[0] == self.padding[1]):
-                return ops.dwconv(x, self.weight, self.padding[0], border)      # hand-written depthwise stencil
+                # hand-written depthwise stencil (a train-mode BatchNorm behind it takes its statistics from the stencil's epilogue)
+                return ops.dwconv(x, self.weight, self.padding[0], border, stats=self.training if stats is None else bool(stats))
             assert border is None
             ops.fallback("grouped Conv2d", f"groups={self.groups} k={self.kernel_size}")
             return F.conv2d(ops.spikes_float(x), self.weight, bias, self.stride, self.padding, self.dilation, self.groups)

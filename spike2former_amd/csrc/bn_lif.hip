@@ -638,14 +638,61 @@ __device__ __forceinline__ RowWalk walk_begin(uint32_t tile, uint32_t L, uint32_
   return w;
 }
 
-template <bool LIF, bool HAS_V, bool YB, bool ALIGNED>
+// UP (ALIGNED only): `res` is the LOW-resolution map [N * C, uh, uw] of a top-down FPN level and the residual is its exact-2x
+// bilinear up-sampling, formed here instead of being written by up2x_fwd_block_kernel (upsample.hip) and read back -- the same
+// expressions in the same order (horizontal taps, then vertical; clamped edges; no contraction), so the sum is bit-identical.
+// The plane is uh x uw -> H x W = 2uh x 2uw with H * W == L; W % 4 == 0 and (256 % W == 0 or W % 256 == 0): a tile is whole image
+// rows or a part of one.  The tile's first (image row, column) is wave-uniform and walked like (row, off); a lane's four outputs
+// 2c .. 2c+3 read source columns c-1 .. c+2 of two source rows: (c, c+1) is one aligned 8-byte load per row, c-1 / c+2 come from
+// the neighbouring lanes, and -- only where a row spans several tiles (W > 256) -- lanes 0 / 63 load theirs.
+struct UpWalk {
+  uint32_t row, oy, ox;          // plane n * C + c, image row and column of the tile's first element (wave-uniform)
+};
+struct UpSrc {
+  float2 a, b;                   // source columns (c, c+1) of the two source rows
+  float ea, eb;                  // lane 0: column c-1, lane 63: column c+2 of those rows (W > 256 only)
+};
+__device__ __forceinline__ UpWalk upwalk_begin(const RowWalk& w, uint32_t W) {
+  UpWalk u;
+  u.row = w.row;
+  u.oy = w.off / W;
+  u.ox = w.off - u.oy * W;
+  return u;
+}
+__device__ __forceinline__ void upwalk_next(UpWalk& u, uint32_t W, uint32_t H, uint32_t rstep) {
+  u.ox += 256u;
+  if (u.ox >= W) {
+    u.ox = 0;
+    u.oy += rstep;
+    if (u.oy >= H) {
+      u.oy = 0;
+      ++u.row;
+    }
+  }
+}
+// the four up-sampled values of one lane: s0 / s1 the two source rows' (c, c+1), l* / f* their columns c-1 / c+2 (f = c+1 at
+// the plane's last column), (wa, wb) the vertical weights; first: the plane's first column (out = 1 * in[0] + 0 * in[1])
+__device__ __forceinline__ void up2x_quad(const float2 s0, const float l0, const float f0, const float2 s1, const float l1,
+                                          const float f1, const bool first, const float wa, const float wb, float out[4]) {
+#pragma clang fp contract(off)
+  const float w0a = first ? 1.f : 0.25f, w0b = first ? 0.f : 0.75f;
+  const float a0 = first ? s0.x : l0, b0 = first ? s0.y : s0.x, a1 = first ? s1.x : l1, b1 = first ? s1.y : s1.x;
+  const float h0[4] = {w0a * a0 + w0b * b0, 0.75f * s0.x + 0.25f * s0.y, 0.25f * s0.x + 0.75f * s0.y, 0.75f * s0.y + 0.25f * f0};
+  const float h1[4] = {w0a * a1 + w0b * b1, 0.75f * s1.x + 0.25f * s1.y, 0.25f * s1.x + 0.75f * s1.y, 0.75f * s1.y + 0.25f * f1};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) out[j] = wa * h0[j] + wb * h1[j];
+}
+
+template <bool LIF, bool HAS_V, bool YB, bool ALIGNED, bool UP = false>
 __global__ __launch_bounds__(kBlock) void bn_apply_rows_kernel(
     const float* __restrict__ z, const float* __restrict__ bias, const double* __restrict__ sums, float* __restrict__ stat,
     float* __restrict__ running_mean, float* __restrict__ running_var, long long* __restrict__ num_batches,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ res, float* __restrict__ u_out,
     const float* __restrict__ v_in, float* __restrict__ y, float* __restrict__ v_out, uint64_t* __restrict__ mask,
     unsigned long long* __restrict__ stats, int64_t total, uint32_t ntiles, int C, uint32_t L, uint32_t chunk,
-    double inv_count, float unbias, float momentum, float eps, int training, float vth, float Df) {
+    double inv_count, float unbias, float momentum, float eps, int training, float vth, float Df, uint32_t uh = 0,
+    uint32_t uw = 0) {
+  static_assert(!UP || ALIGNED, "the up-sampling residual needs whole tiles");
   const int lane = threadIdx.x & 63;
   const uint32_t wave = blockIdx.x * kWaves + (uint32_t)wave_id_uniform();
   uint32_t t = wave * chunk;
@@ -653,13 +700,39 @@ __global__ __launch_bounds__(kBlock) void bn_apply_rows_kernel(
   const uint32_t tail = (uint32_t)(total - (int64_t)(ntiles - 1) * 256);      // valid elements of the last tile (1..256)
   extern __shared__ __attribute__((aligned(16))) float sstat[];      // [3][C]: mean, rstd, var
   Tile4 zn[kAhead], rn[kAhead], vn[kAhead];
+  // UP: image geometry (W a power of two when it is < 256) and the two walks -- `rq` for the tile being requested (requests are
+  // issued in tile order, one call per tile), `wk` for the tile being worked on
+  const uint32_t upW = 2u * uw, upH = 2u * uh;
+  const uint32_t uplg = upW >= 256u ? 8u : (uint32_t)__builtin_ctz(upW | 256u), upm = upW >= 256u ? 255u : upW - 1u;
+  UpSrc sn[kAhead];
+  UpWalk rq, wk;
+  if (UP) rq = wk = upwalk_begin(walk_begin(t, L, (uint32_t)C), upW);
   auto request = [&](int slot, uint32_t tile) __attribute__((always_inline)) {
     if (tile < t_end && (ALIGNED || tile + 1 < ntiles || (uint32_t)lane * 4 < tail)) {
       const int64_t base = (int64_t)tile * 256 + lane * 4;
       zn[slot] = (S2F_BN_NT & 1) ? ld4_nt(z + base) : ld4(z + base);
-      if (res) rn[slot] = (S2F_BN_NT & 32) ? ld4_nt(res + base) : ld4(res + base);
+      if (UP) {
+        const uint32_t oy = rq.oy + (((uint32_t)lane * 4u) >> uplg), ox = rq.ox + (((uint32_t)lane * 4u) & upm);
+        const uint32_t ra = oy == 0 ? 0u : (oy - 1u) >> 1, rb = min(ra + 1u, uh - 1u);      // out row 2i: i-1, i; 2i+1: i, i+1
+        const float* p = res + ((int64_t)rq.row * uh) * uw + (ox >> 1);
+        const float* pa = p + ra * uw;
+        const float* pb = p + rb * uw;
+        sn[slot].a = *reinterpret_cast<const float2*>(pa);
+        sn[slot].b = *reinterpret_cast<const float2*>(pb);
+        sn[slot].ea = sn[slot].eb = 0.f;
+        if (upW > 256u) {
+          const bool le = lane == 0 && ox > 0, re = lane == 63 && ox + 4u < upW;
+          if (le || re) {
+            sn[slot].ea = pa[le ? -1 : 2];
+            sn[slot].eb = pb[le ? -1 : 2];
+          }
+        }
+      } else if (res) {
+        rn[slot] = (S2F_BN_NT & 32) ? ld4_nt(res + base) : ld4(res + base);
+      }
       if (LIF && HAS_V) vn[slot] = ld4(v_in + base);
     }
+    if (UP) upwalk_next(rq, upW, upH, 256u >> uplg);
   };
 #pragma unroll
   for (int i = 0; i < kAhead; ++i) request(i, t + i);
@@ -704,8 +777,22 @@ __global__ __launch_bounds__(kBlock) void bn_apply_rows_kernel(
     if (training && c == 0 && num_batches != nullptr) *num_batches += 1;
   };
   // one tile: BN (+ residual) (+ neuron), stores, mask words; then the (row, channel) walk
-  auto work = [&](uint32_t tile, const Tile4& zv, const Tile4& rv, const Tile4& vv) __attribute__((always_inline)) {
+  auto work = [&](uint32_t tile, const Tile4& zv, const Tile4& rv_in, const Tile4& vv, const UpSrc& sv) __attribute__((always_inline)) {
     const int64_t base = (int64_t)tile * 256 + lane * 4;
+    Tile4 rv = rv_in;
+    if (UP) {
+      const uint32_t oy = wk.oy + (((uint32_t)lane * 4u) >> uplg), ox = wk.ox + (((uint32_t)lane * 4u) & upm);
+      float l0 = __shfl_up(sv.a.y, 1, 64), l1 = __shfl_up(sv.b.y, 1, 64);
+      float f0 = __shfl_down(sv.a.x, 1, 64), f1 = __shfl_down(sv.b.x, 1, 64);
+      if (upW > 256u) {
+        if (lane == 0) l0 = sv.ea, l1 = sv.eb;
+        if (lane == 63) f0 = sv.ea, f1 = sv.eb;
+      }
+      if (ox + 4u == upW) f0 = sv.a.y, f1 = sv.b.y;       // the plane's last column: the clamped tap
+      const float wa = oy == 0 ? 1.f : (oy & 1u) ? 0.75f : 0.25f, wb = oy == 0 ? 0.f : (oy & 1u) ? 0.25f : 0.75f;
+      up2x_quad(sv.a, l0, f0, sv.b, l1, f1, ox == 0, wa, wb, rv.a);
+      upwalk_next(wk, upW, upH, 256u >> uplg);
+    }
     const uint32_t bnd = L - w.off;                       // elements of this tile that still belong to `row`
     const bool split = !ALIGNED && bnd < 256u;
     const uint32_t c2 = w.c + 1 == (uint32_t)C ? 0u : w.c + 1;
@@ -763,17 +850,19 @@ __global__ __launch_bounds__(kBlock) void bn_apply_rows_kernel(
   };
   for (; t < t_end; t += kAhead) {
     Tile4 zv[kAhead], rv[kAhead], vv[kAhead];
+    UpSrc sv[kAhead];
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) {
       zv[i] = zn[i];
       rv[i] = rn[i];
       vv[i] = vn[i];
+      sv[i] = sn[i];
     }
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) request(i, t + kAhead + i);
 #pragma unroll
     for (int i = 0; i < kAhead; ++i)
-      if (t + i < t_end) work(t + i, zv[i], rv[i], vv[i]);
+      if (t + i < t_end) work(t + i, zv[i], rv[i], vv[i], sv[i]);
   }
   if (count) {
     for (int o = 32; o > 0; o >>= 1) {
@@ -1645,6 +1734,12 @@ inline bool rows_ok(int64_t N, int64_t C, int64_t L, int D) {
   return (L & 3) == 0 && L >= 256 && N * C * L < ((int64_t)1 << 39) && N * C < ((int64_t)1 << 31) && D >= 1 && (D & (D - 1)) == 0;
 }
 inline bool rows_aligned(int64_t total, int64_t L) { return (L & 255) == 0 && (total & 255) == 0; }
+// the apply kernel's up-sampling residual (bn_apply_rows_kernel<.., UP>): train mode on the two-pass row kernels, whole tiles, a
+// plane of H x W = L that doubles an [H/2, W/2] one, a tile = whole image rows or part of one
+inline bool up_ok(int64_t N, int64_t C, int64_t L, int64_t H, int64_t W, int training, int D) {
+  return training && rows_ok(N, C, L, D) && rows_aligned(N * C * L, L) && !single_pass_ok(N, C, L) && H > 0 && W > 0 && H * W == L &&
+         (H & 1) == 0 && (W & 3) == 0 && (W < 256 ? 256 % W == 0 : W % 256 == 0) && W < (1 << 24);
+}
 inline int pick_slices_rows(int C, int L, int& slice) {
   int S = 1;
   while ((int64_t)C * S < 2048 && L / (S * 2) >= 2048) S *= 2;       // >= 8 tiles per (row, slice): two per wave
@@ -1799,9 +1894,14 @@ static int bn_act_fwd_impl(const float* z, const float* conv_bias, const double*
                            float* running_var, int64_t* num_batches_tracked, const float* gamma, const float* beta,
                            const float* residual, float* u_out, const float* v_in, void* y_out, float* v_out, uint64_t* mask,
                            uint64_t* stats, int64_t N, int64_t C, int64_t L, float momentum, float eps, int training, float vth,
-                           int D, int y_bf16, void* stream, Bn2 bn2) {
+                           int D, int y_bf16, void* stream, Bn2 bn2, int64_t up_h = 0, int64_t up_w = 0) {
   float* y = reinterpret_cast<float*>(y_out);
   S2F_REQUIRE(z && stat_out && gamma && beta, S2F_EINVAL, "s2f_bn_act_fwd: null z/stat/gamma/beta");
+  // up_h > 0: `residual` is the low-resolution map [N * C, up_h, up_w], up-sampled 2x inside the row-walking apply kernel
+  const bool up = up_h > 0;
+  S2F_REQUIRE(!up || (residual && sums && !bn2.gamma && up_ok(N, C, L, 2 * up_h, 2 * up_w, training, D) &&
+                      (reinterpret_cast<uintptr_t>(residual) & 7u) == 0),
+              S2F_EINVAL, "s2f_bn_act_up_fwd: needs the statistics, an 8-byte aligned low-resolution map and a shape of s2f_bn_up_ok");
   S2F_REQUIRE(!bn2.gamma || (training && sums == nullptr && single_pass_ok(N, C, L) && bn2.beta), S2F_EINVAL,
               "s2f_bn2_act_fwd: the BatchNorm pair runs on the single-pass kernels only (training mode, s2f_bn2_fused_ok)");
   // sums given for a shape that could go single-pass: the caller already has the statistics (a producer's epilogue, or a probe) --
@@ -1861,14 +1961,22 @@ static int bn_act_fwd_impl(const float* z, const float* conv_bias, const double*
   const size_t lds = 3 * C * sizeof(float) + 64;
   for_fwd_variant(y, v_in, y_bf16, [&](auto i) {
     constexpr FwdVariant V = kFwdVariants[i];
-    if (rows_ok(N, C, L, D)) {
+    if (up) {
+      uint32_t chunk;
+      const uint32_t ntiles = (uint32_t)(total >> 8);
+      const int rgrid = grid_rows<bn_apply_rows_kernel<V.lif, V.has_v, V.yb, true, true>>(ntiles, lds, chunk, 8);
+      S2F_LAUNCH(true, true, (bn_apply_rows_kernel<V.lif, V.has_v, V.yb, true, true>), dim3(rgrid), block, lds, s, z, conv_bias, sums,
+                 stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, total, ntiles,
+                 (int)C, (uint32_t)L, chunk, inv_count, unbias, momentum, eps, training, vth, (float)D, (uint32_t)up_h,
+                 (uint32_t)up_w);
+    } else if (rows_ok(N, C, L, D)) {
       s2f_dispatch_bool(rows_aligned(total, L), [&](auto al) {
         uint32_t chunk;
         const uint32_t ntiles = (uint32_t)((total + 255) >> 8);
         const int rgrid = grid_rows<bn_apply_rows_kernel<V.lif, V.has_v, V.yb, al.value>>(ntiles, lds, chunk, 8);
         S2F_LAUNCH(true, true, (bn_apply_rows_kernel<V.lif, V.has_v, V.yb, al.value>), dim3(rgrid), block, lds, s, z, conv_bias,
                    sums, stat_out, running_mean, running_var, nbt, gamma, beta, residual, u_out, v_in, y, v_out, mask, st, total,
-                   ntiles, (int)C, (uint32_t)L, chunk, inv_count, unbias, momentum, eps, training, vth, (float)D);
+                   ntiles, (int)C, (uint32_t)L, chunk, inv_count, unbias, momentum, eps, training, vth, (float)D, 0u, 0u);
       });
     } else {
       s2f_dispatch_bool(anyl, [&](auto al) {
@@ -1888,6 +1996,24 @@ extern "C" int s2f_bn_act_fwd(const float* z, const float* conv_bias, const doub
                               float momentum, float eps, int training, float vth, int D, int y_bf16, void* stream) {
   return bn_act_fwd_impl(z, conv_bias, sums, stat_out, running_mean, running_var, num_batches_tracked, gamma, beta, residual, u_out,
                          v_in, y_out, v_out, mask, stats, N, C, L, momentum, eps, training, vth, D, y_bf16, stream, Bn2{});
+}
+
+// 1: s2f_bn_act_up_fwd takes [N, C, H * W] with the residual given as the [N * C, H/2, W/2] map
+extern "C" int s2f_bn_up_ok(int64_t N, int64_t C, int64_t H, int64_t W, int training, int D) {
+  return (H > 0 && W > 0 && up_ok(N, C, H * W, H, W, training, D)) ? 1 : 0;
+}
+
+// s2f_bn_act_fwd (train mode, statistics given) with residual = bilinear2x(residual_lo), residual_lo [N * C, H/2, W/2], L = H * W:
+// the up-sampled map of s2f_upsample2x_fwd is formed inside the apply kernel, bit-identical to the two launches (s2f_bn_up_ok)
+extern "C" int s2f_bn_act_up_fwd(const float* z, const float* conv_bias, const double* sums, float* stat_out,
+                                 float* running_mean, float* running_var, int64_t* num_batches_tracked, const float* gamma,
+                                 const float* beta, const float* residual_lo, float* u_out, const float* v_in, void* y_out,
+                                 float* v_out, uint64_t* mask, uint64_t* stats, int64_t N, int64_t C, int64_t H, int64_t W,
+                                 float momentum, float eps, int training, float vth, int D, int y_bf16, void* stream) {
+  S2F_REQUIRE(H > 0 && W > 0 && (H & 1) == 0 && (W & 1) == 0, S2F_EINVAL, "s2f_bn_act_up_fwd: even H, W");
+  return bn_act_fwd_impl(z, conv_bias, sums, stat_out, running_mean, running_var, num_batches_tracked, gamma, beta, residual_lo,
+                         u_out, v_in, y_out, v_out, mask, stats, N, C, H * W, momentum, eps, training, vth, D, y_bf16, stream, Bn2{},
+                         H / 2, W / 2);
 }
 
 extern "C" int s2f_bn2_fused_ok(int64_t N, int64_t C, int64_t L) { return single_pass_ok(N, C, L) ? 1 : 0; }

@@ -88,6 +88,8 @@ struct DwEpi {
   unsigned short* y;             // bf16 spikes or null (no neuron)
   unsigned long long* stats;     // firing counters or null
   float eps, vth, Df, inv_d;
+  float* part;                   // STATS kernels: BatchNorm partials [C][P][2] of the plain stencil's output (bn_lif.hip), else null
+  int P;                         // slots per channel = N * workgroups per plane
 };
 
 // four consecutive outputs of channel c at flat offset `off` (16-byte aligned when `vec`), `nvalid` of them inside the row
@@ -133,9 +135,31 @@ __device__ __forceinline__ void dw_epi_counters(const DwEpi& ep, uint32_t csum, 
   }
 }
 
+// STATS epilogue of the plain stencil (the train-mode BatchNorm that follows a depthwise convolution takes its statistics from
+// here instead of a pass over y, as from the GEMMs' epilogues in pgemm.hip): (s1, s2) = this thread's sum / sum of squares of the
+// outputs it STORED; the workgroup's pair -- wave shuffles, one LDS round, a fixed order -- is stored (no atomics, nothing shared
+// between workgroups) at part[c][n * gridDim.x + blockIdx.x]; s2f_bn_partials_finalize adds the P slots of a channel in fp64.
+__device__ __forceinline__ void dw_tile_stats(const DwEpi& ep, int c, int n, float s1, float s2) {
+  __shared__ float red[4][2];
+  for (int o = 32; o > 0; o >>= 1) {
+    s1 += __shfl_xor(s1, o, 64);
+    s2 += __shfl_xor(s2, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6][0] = s1;
+    red[threadIdx.x >> 6][1] = s2;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int64_t slot = (int64_t)c * ep.P + (int64_t)n * gridDim.x + blockIdx.x;
+    *reinterpret_cast<float2*>(ep.part + slot * 2) =
+        make_float2((red[0][0] + red[1][0]) + (red[2][0] + red[3][0]), (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]));
+  }
+}
+
 // FLIP = false: y[oy][ox] = sum_{i,j} w[i][j] * x[oy + i - pad][ox + j - pad]           (x: H x W, y: Ho x Wo)
 // FLIP = true : y[oy][ox] = sum_{i,j} w[i][j] * x[oy - i + pad][ox - j + pad]           (input gradient: x = gy)
-template <int K, bool FLIP, typename TX, bool EPI = false>
+template <int K, bool FLIP, typename TX, bool EPI = false, bool STATS = false>
 __global__ __launch_bounds__(256) void dw_stencil_kernel(const TX* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ border, float* __restrict__ y, int C,
                                                          int H, int W, int Ho, int Wo, int pad, int tiles_x, DwEpi ep = DwEpi{}) {
@@ -189,6 +213,16 @@ __global__ __launch_bounds__(256) void dw_stencil_kernel(const TX* __restrict__ 
         if (tx + q0 + o < Wo) yp[o] = acc[o];
     }
   }
+  if constexpr (STATS) {
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+      if (oy < Ho && tx + q0 + o < Wo) {
+        s1 += acc[o];
+        s2 += acc[o] * acc[o];
+      }
+    dw_tile_stats(ep, c, plane / C, s1, s2);
+  }
 }
 
 // Wide-map form of the same stencil (W % 4 == 0, W >= 64): a 64 x 32 output tile per workgroup, every thread a 2 x 4 output
@@ -199,7 +233,7 @@ __global__ __launch_bounds__(256) void dw_stencil_kernel(const TX* __restrict__ 
 // 1.5 LDS reads of 16 bytes instead of 17.5 of 4 bytes.  'Same' padding (pad == (K - 1) / 2) only.
 constexpr int WT = 64, HT = 32, WS = WT + 8;           // tile and staged row length (floats)
 
-template <int K, bool FLIP, typename TX, bool EPI = false>
+template <int K, bool FLIP, typename TX, bool EPI = false, bool STATS = false>
 __global__ __launch_bounds__(256) void dw_stencil_wide_kernel(const TX* __restrict__ x, const float* __restrict__ w,
                                                               const float* __restrict__ border, float* __restrict__ y,
                                                               int C, int H, int W, int Ho, int Wo, int pad, int tiles_x,
@@ -274,6 +308,18 @@ __global__ __launch_bounds__(256) void dw_stencil_wide_kernel(const TX* __restri
       for (int o = 0; o < 4; ++o)
         if (ox + o < Wo) yp[o] = acc[a][o];
     }
+  }
+  if constexpr (STATS) {
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+        if (ty + r2 + a < Ho && tx + q0 + o < Wo) {
+          s1 += acc[a][o];
+          s2 += acc[a][o] * acc[a][o];
+        }
+    dw_tile_stats(ep, c, plane / C, s1, s2);
   }
 }
 
@@ -375,6 +421,33 @@ void launch_stencil_epi(int K, dim3 grid, hipStream_t s, const TX* x, const floa
   });
 }
 
+// the plain 3x3 'same' stencil takes the wide form (see launch_stencil)
+inline bool wide_form(int K, int H, int W, int pad) {
+  static const bool wide_on = !getenv("S2F_DW_NO_WIDE");          // A/B switch for tools/probe_dw.py
+  return wide_on && K == 3 && (W & 3) == 0 && W >= 2 * WT && H >= HT && pad == 1;
+}
+
+// workgroups per plane of the STATS stencil (K = 3, pad = 1: Ho = H, Wo = W) = BatchNorm partial slots per (n, channel)
+inline int stats_tiles(int H, int W) {
+  return wide_form(3, H, W, 1) ? ((W + WT - 1) / WT) * ((H + HT - 1) / HT) : ((W + TS - 1) / TS) * ((H + TS - 1) / TS);
+}
+
+template <typename TX>
+void launch_stencil_stats(hipStream_t s, const TX* x, const float* w, float* y, float* part, int N, int C, int H, int W) {
+  DwEpi ep{};
+  ep.part = part;
+  ep.P = N * stats_tiles(H, W);
+  if (wide_form(3, H, W, 1)) {
+    const int wx = (W + WT - 1) / WT, wy = (H + HT - 1) / HT;
+    hipLaunchKernelGGL((dw_stencil_wide_kernel<3, false, TX, false, true>), dim3(wx * wy, N * C), dim3(256), 0, s, x, w,
+                       (const float*)nullptr, y, C, H, W, H, W, 1, wx, ep);
+    return;
+  }
+  const int tiles_x = (W + TS - 1) / TS, tiles_y = (H + TS - 1) / TS;
+  hipLaunchKernelGGL((dw_stencil_kernel<3, false, TX, false, true>), dim3(tiles_x * tiles_y, N * C), dim3(256), 0, s, x, w,
+                     (const float*)nullptr, y, C, H, W, H, W, 1, tiles_x, ep);
+}
+
 template <bool FLIP, typename TX>
 void launch_stencil(int K, dim3 grid, hipStream_t s, const TX* x, const float* w, const float* border, float* y, int C,
                     int H, int W, int Ho, int Wo, int pad, int tiles_x) {
@@ -382,8 +455,7 @@ void launch_stencil(int K, dim3 grid, hipStream_t s, const TX* x, const float* w
   // (tools/probe_dw.py, us, 32x32-tile form -> wide form): 3x3 [8,256,256,256] 267 -> 222, [8,256,128,128] 70 -> 53,
   // [8,256,64,64] 17 -> 18; 7x7 [8,64,256,256] 109 -> 139 (49 multiply-adds per output: that stencil is VALU-bound and the
   // 2 x 4 block only adds register pressure), so the wide form is used for K = 3, W >= 128 only.
-  static const bool wide_on = !getenv("S2F_DW_NO_WIDE");          // A/B switch for tools/probe_dw.py
-  if (wide_on && K == 3 && (W & 3) == 0 && W >= 2 * WT && H >= HT && pad == 1 && (reinterpret_cast<uintptr_t>(x) & (4 * sizeof(TX) - 1)) == 0) {
+  if (wide_form(K, H, W, pad) && (reinterpret_cast<uintptr_t>(x) & (4 * sizeof(TX) - 1)) == 0) {
     const int wx = (Wo + WT - 1) / WT, wy = (Ho + HT - 1) / HT;
     hipLaunchKernelGGL((dw_stencil_wide_kernel<3, FLIP, TX>), dim3(wx * wy, grid.y), dim3(256), 0, s, x, w, border, y, C, H, W, Ho,
                        Wo, pad, wx, DwEpi{});
@@ -411,6 +483,26 @@ extern "C" int s2f_dwconv_fwd(const void* x, const float* w, const float* border
     launch_stencil<false>(K, dim3(tiles_x * tiles_y, N * C), (hipStream_t)stream, reinterpret_cast<const float*>(x), w, border,
                           y, C, H, W, Ho, Wo, pad, tiles_x);
   return s2f_check_launch("s2f_dwconv_fwd");
+}
+
+extern "C" int64_t s2f_dwconv_stats_slots(int N, int H, int W) {
+  return (N > 0 && H > 0 && W > 0) ? (int64_t)N * stats_tiles(H, W) : 0;
+}
+
+extern "C" int s2f_dwconv_fwd_stats(const void* x, const float* w, float* y, float* partials, int64_t P, int N, int C, int H, int W,
+                                    int x_bf16, void* stream) {
+  S2F_REQUIRE(x && w && y && partials, S2F_EINVAL, "s2f_dwconv_fwd_stats: null pointer");
+  int Ho, Wo;
+  int rc = check("s2f_dwconv_fwd_stats", N, C, H, W, 3, 1, Ho, Wo);
+  if (rc) return rc;
+  S2F_REQUIRE(P == s2f_dwconv_stats_slots(N, H, W), S2F_EINVAL, "s2f_dwconv_fwd_stats: P must be s2f_dwconv_stats_slots(N, H, W)");
+  S2F_REQUIRE((reinterpret_cast<uintptr_t>(x) & (x_bf16 ? 7u : 15u)) == 0 && (reinterpret_cast<uintptr_t>(partials) & 7u) == 0,
+              S2F_EALIGN, "s2f_dwconv_fwd_stats: x must be aligned to four elements, partials to 8 bytes");
+  if (x_bf16)
+    launch_stencil_stats((hipStream_t)stream, reinterpret_cast<const unsigned short*>(x), w, y, partials, N, C, H, W);
+  else
+    launch_stencil_stats((hipStream_t)stream, reinterpret_cast<const float*>(x), w, y, partials, N, C, H, W);
+  return s2f_check_launch("s2f_dwconv_fwd_stats");
 }
 
 extern "C" int s2f_dwconv_bn_lif_fwd(const void* x, const float* w, const float* border, const float* running_mean,

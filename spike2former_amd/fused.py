@@ -8,7 +8,7 @@ from .neuron import Q_IFNode
 
 
 def bn_act(z, conv_bias, bn, residual=None, lif: Q_IFNode = None, want_pre=None, next_lif: Q_IFNode = None,
-           want_border=False, scale=None):
+           want_border=False, scale=None, residual_lo=None):
     """z: conv output WITHOUT its bias, [N, C, *].  Returns (u, y): u = BN(z + bias) [+ residual] (None unless wanted),
     y = lif(u) as an ops.Spikes pair (None without lif).  Shapes follow z.  want_border: also return BN(0) from the running statistics as
     updated by this call (BNAndPadLayer's padding value, sdtv2.py:68-78) -- written by the same kernel.
@@ -16,11 +16,18 @@ def bn_act(z, conv_bias, bn, residual=None, lif: Q_IFNode = None, want_pre=None,
     the residual stream).  Its update is done by this kernel as well and handed over with Q_IFNode.prefire: the reference's
     separate neuron pass over u (one more read of u forward; a neuron backward + a gradient add backward) disappears.
     scale: per-channel factor on the BatchNorm output, u = scale * BN(z + bias) [+ residual] (the layer-scale `gamma` of the
-    pixel decoder's encoder layers, detr_layers.py:331-337), folded into the affine pair: two [C] products, no pass over u."""
+    pixel decoder's encoder layers, detr_layers.py:331-337), folded into the affine pair: two [C] products, no pass over u.
+    residual_lo: the residual is the bilinear up-sampling of this [N, C, H/2, W/2] map to z's size (the FPN's top-down add) -- formed
+    inside the BatchNorm kernel where the shape allows (ops.bn_up_ok), else by ops.upsample_bilinear; the result then ends with the
+    pass-through of residual_lo for its second reader (as ops.upsample_bilinear(skip=True))."""
+    if residual_lo is not None and z.numel() == 0:
+        residual, through = ops.upsample_bilinear(residual_lo, z.shape[-2:], skip=True)
+        return bn_act(z, conv_bias, bn, residual=residual, lif=lif, want_pre=want_pre, next_lif=next_lif, want_border=want_border,
+                      scale=scale) + (through,)
     if next_lif is not None and lif is None:
-        u, y = bn_act(z, conv_bias, bn, residual=residual, lif=next_lif, want_pre=True, scale=scale)
+        u, y, *through = bn_act(z, conv_bias, bn, residual=residual, lif=next_lif, want_pre=True, scale=scale, residual_lo=residual_lo)
         next_lif.prefire(u, y)
-        return u, None
+        return (u, None, *through)
     if want_pre is None:
         want_pre = lif is None
     wanted_pre = want_pre
@@ -46,12 +53,13 @@ def bn_act(z, conv_bias, bn, residual=None, lif: Q_IFNode = None, want_pre=None,
     if lif is not None and lif.stats is not None:
         lif.stats_elems += z.numel()
     weight, bias = (bn.weight, bn.bias) if scale is None else ops.scale_affine(bn.weight, bn.bias, scale)
-    u, y, v_out, border = ops.bn_act(
+    u, y, v_out, border, *through = ops.bn_act(
         z, conv_bias, weight, bias, bn.running_mean, bn.running_var,
         bn.num_batches_tracked if training else None, training, bn.momentum, bn.eps,
         residual=residual, lif=lif is not None, want_pre=want_pre, v_in=v_in,
         keep_v=(lif is not None and lif.keep_membrane), D=(lif.D if lif is not None else 8),
-        vth=(lif.v_threshold if lif is not None else 1.0), stats=(lif.stats if lif is not None else None), want_border=True)
+        vth=(lif.v_threshold if lif is not None else 1.0), stats=(lif.stats if lif is not None else None), want_border=True,
+        residual_lo=residual_lo, lo_skip=residual_lo is not None)
     if lif is not None:
         lif.v = v_out if lif.keep_membrane else 0.0
         if lif._forward_hooks:
@@ -62,7 +70,7 @@ def bn_act(z, conv_bias, bn, residual=None, lif: Q_IFNode = None, want_pre=None,
                 hook(lif, (u,), yf)
     if not wanted_pre:
         u = None
-    return (u, y, border) if want_border else (u, y)
+    return ((u, y, border) if want_border else (u, y)) + tuple(through)
 
 
 class _EvalBN:

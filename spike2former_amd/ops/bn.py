@@ -8,12 +8,16 @@ from .core import *          # noqa: F401,F403  (the shared plumbing: _ptr, _str
 # ------------------------------------------------------------------------------------------------ BN (+bias, +residual, +LIF)
 class _BNAct(torch.autograd.Function):
     """t = z + conv_bias ; u = BatchNorm(t) [+ residual] ; y = Q_IFNode(u)   in two streaming kernels forward
-    (statistics, apply) and two backward (reduce, apply).  Returns (u, y, v_out); unrequested ones are empty."""
+    (statistics, apply) and two backward (reduce, apply).  Returns (u, y, v_out); unrequested ones are empty.
+    up_lo: the residual given as the low-resolution map [N, C, H/2, W/2] whose exact-2x bilinear up-sampling is added -- formed inside
+    the apply kernel (s2f_bn_act_up_fwd; the caller has asked s2f_bn_up_ok), its gradient returned through the up-sampling's adjoint.
+    up_skip: also hand up_lo back as a pass-through for a second reader, whose gradient that adjoint sums (as ops.upsample_bilinear)."""
 
     @staticmethod
     def forward(ctx, z, conv_bias, gamma, beta, residual, v_in, running_mean, running_var, nbt, training, momentum,
-                eps, lif_on, want_pre, keep_v, D, vth, stats, bf16, partials=None):
-        _need_cuda(z, conv_bias, gamma, beta, residual, v_in)
+                eps, lif_on, want_pre, keep_v, D, vth, stats, bf16, partials=None, up_lo=None, up_skip=False):
+        _need_cuda(z, conv_bias, gamma, beta, residual, v_in, up_lo)
+        up_in = up_lo
         z = z.contiguous()
         N, C = z.shape[0], z.shape[1]
         L = z.numel() // (N * C)
@@ -23,8 +27,8 @@ class _BNAct(torch.autograd.Function):
         ws = None
         single = bool(training) and bool(lib.s2f_bn_single_pass(N, C, L))    # small map: statistics inside s2f_bn_act_fwd
         if not (training and partials is not None and partials.dim() == 3 and partials.shape[0] == C and partials.shape[2] == 2
-                and partials.shape[1] == lib.s2f_bn_partials_count(N, L) and (cfg.BN_PARTIALS_SINGLE or not single)):
-            partials = None          # the statistics the producing GEMM stored with z (BN_PARTIALS), when they describe this view of it
+                and partials.shape[1] in _partial_slots(z) and (cfg.BN_PARTIALS_SINGLE or not single)):
+            partials = None          # the statistics z's producer stored with it (BN_PARTIALS), when they describe this view of it
         if partials is not None:
             # the producer's per-tile partials -> the sums of the statistics pass: one small launch over P * C * 8 bytes
             BN_PARTIALS_USED[0] += 1
@@ -39,28 +43,38 @@ class _BNAct(torch.autograd.Function):
             check(lib.s2f_bn_stats(_ptr(z), _ptr(conv_bias), _ptr(ws), N, C, L, s), "s2f_bn_stats")
         if residual is not None:
             residual = residual.contiguous()
+        if up_lo is not None:
+            assert residual is None and ws is not None and z.dim() == 4 and up_lo.shape == (N, C, z.shape[2] // 2, z.shape[3] // 2)
+            up_lo = up_lo.contiguous()
         if v_in is not None:
             v_in = v_in.contiguous()
         bf16 = bool(bf16) and lif_on
         u = torch.empty_like(z) if want_pre else None
         y = torch.empty(z.shape, dtype=torch.bfloat16 if bf16 else torch.float32, device=dev) if lif_on else None
         v_out = torch.empty_like(z) if (lif_on and keep_v) else None
-        need_grad = any(ctx.needs_input_grad[:5])
+        need_grad = any(ctx.needs_input_grad[:5]) or (up_lo is not None and ctx.needs_input_grad[20])
         # (training-mode short rows keep a per-channel mask layout of their own: s2f_bn_mask_words)
         nmask = int(lib.s2f_bn_mask_words(N, C, L)) if training else mask_words(z.numel())
         mask = torch.empty(nmask, dtype=torch.int64, device=dev) if (lif_on and need_grad) else None
         n = z.numel()
         # algorithmic bytes: read z, [read residual], [write u], [write y]  (SURVEY 8d per-element figures)
-        alg = 4 * n * (1 + (residual is not None) + bool(want_pre) + bool(lif_on))
+        alg = 4 * n * (1 + (residual is not None) + bool(want_pre) + bool(lif_on)) + (n if up_lo is not None else 0)
         _time_next("bn_lif_fwd" if lif_on else "bn_fwd", alg, moved=alg - (2 * n if bf16 else 0))
-        check(lib.s2f_bn_act_fwd(_ptr(z), _ptr(conv_bias), _ptr(ws), _ptr(stat), _ptr(running_mean), _ptr(running_var),
-                                 _ptr(nbt), _ptr(gamma), _ptr(beta), _ptr(residual), _ptr(u), _ptr(v_in), _ptr(y),
-                                 _ptr(v_out), _ptr(mask), _ptr(stats), N, C, L, momentum, eps, int(training), vth, D,
-                                 int(bf16), s), "s2f_bn_act_fwd")
+        if up_lo is not None:
+            check(lib.s2f_bn_act_up_fwd(_ptr(z), _ptr(conv_bias), _ptr(ws), _ptr(stat), _ptr(running_mean), _ptr(running_var),
+                                        _ptr(nbt), _ptr(gamma), _ptr(beta), _ptr(up_lo), _ptr(u), _ptr(v_in), _ptr(y),
+                                        _ptr(v_out), _ptr(mask), _ptr(stats), N, C, z.shape[2], z.shape[3], momentum, eps,
+                                        int(training), vth, D, int(bf16), s), "s2f_bn_act_up_fwd")
+        else:
+            check(lib.s2f_bn_act_fwd(_ptr(z), _ptr(conv_bias), _ptr(ws), _ptr(stat), _ptr(running_mean), _ptr(running_var),
+                                     _ptr(nbt), _ptr(gamma), _ptr(beta), _ptr(residual), _ptr(u), _ptr(v_in), _ptr(y),
+                                     _ptr(v_out), _ptr(mask), _ptr(stats), N, C, L, momentum, eps, int(training), vth, D,
+                                     int(bf16), s), "s2f_bn_act_fwd")
         buf = stat
         stat, border = buf[:2 * C], buf[2 * C:]
         ctx.save_for_backward(z, conv_bias, gamma, stat, mask)
         ctx.cfg = (N, C, L, bool(training), D, vth, residual is not None, conv_bias is not None)
+        ctx.up = None if up_lo is None else (z.shape[2] // 2, z.shape[3] // 2)
         ctx.set_materialize_grads(False)
         # bf16 spikes: slot 1 carries the autograd handle, slot 4 the (non-differentiable) bf16 tensor
         ydata = z.new_empty(0)
@@ -73,10 +87,13 @@ class _BNAct(torch.autograd.Function):
         ctx.mark_non_differentiable(border, ydata, *[o for o, t in zip(outs, (u, y, v_out)) if t is None])
         if tok2.numel() == 0:
             ctx.mark_non_differentiable(tok2)
-        return tuple(outs) + (border, ydata, tok2)
+        through = up_in if (up_in is not None and up_skip) else z.new_empty(0)
+        if through is not up_in:
+            ctx.mark_non_differentiable(through)
+        return tuple(outs) + (border, ydata, tok2, through)
 
     @staticmethod
-    def backward(ctx, g_u, g_y, g_v, g_border, _g_ydata, g_y2):
+    def backward(ctx, g_u, g_y, g_v, g_border, _g_ydata, g_y2, g_through=None):
         z, conv_bias, gamma, stat, mask = ctx.saved_tensors
         N, C, L, training, D, vth, has_res, has_bias = ctx.cfg
 
@@ -88,10 +105,10 @@ class _BNAct(torch.autograd.Function):
         if g_y2 is not None and not lib.s2f_bn_bwd_ports_ok(N, C, L, int(training), D):
             g_y, g_y2 = g_y + g_y2, None          # (a kernel form without the second port: the add the autograd engine would have made)
         if g_u is None and g_y is None and g_v is None:
-            return (None,) * 20
+            return (None,) * 20 + (g_through, None)
         dev = z.device
         gz = torch.empty_like(z)
-        g_res = torch.empty_like(z) if (has_res and ctx.needs_input_grad[4]) else None
+        g_res = torch.empty_like(z) if ((has_res and ctx.needs_input_grad[4]) or (ctx.up is not None and ctx.needs_input_grad[20])) else None
         dgamma = torch.empty(C, dtype=torch.float32, device=dev)
         dbeta = torch.empty(C, dtype=torch.float32, device=dev)
         ws = None if (training and lib.s2f_bn_single_pass(N, C, L)) else _take_zeroed(2 * C, dev)
@@ -108,24 +125,72 @@ class _BNAct(torch.autograd.Function):
             g_bias = None if training else gamma * stat[C:2 * C] * dbeta
         if ctx.needs_input_grad[5]:
             raise RuntimeError("gradient w.r.t. the incoming membrane is not supported by the fused BN+LIF op")
-        return (gz, g_bias, dgamma, dbeta, g_res) + (None,) * 15
+        if ctx.up is not None:
+            # the adjoint of the up-sampling the apply kernel formed, with the pass-through's gradient summed inside it
+            g_lo = g_through
+            if g_res is not None:
+                h, w = ctx.up
+                g_lo = torch.empty(N, C, h, w, dtype=torch.float32, device=dev)
+                check(lib.s2f_upsample2x_bwd_add(_ptr(g_res), _ptr(None if g_through is None else g_through.contiguous()), _ptr(g_lo),
+                                                 N * C, h, w, _stream()), "s2f_upsample2x_bwd_add")
+            return (gz, g_bias, dgamma, dbeta, None) + (None,) * 15 + (g_lo, None)
+        return (gz, g_bias, dgamma, dbeta, g_res) + (None,) * 17
+
+
+def _partial_slots(z):
+    """the slot counts per channel a producer of z may have stored its BatchNorm partials in: the GEMMs' column tiles, and for a
+    [N, C, H, W] map the depthwise stencil's workgroups (s2f_dwconv_fwd_stats)"""
+    N, C = z.shape[0], z.shape[1]
+    out = (int(lib.s2f_bn_partials_count(N, z.numel() // (N * C))),)
+    if z.dim() == 4:
+        out += (int(lib.s2f_dwconv_stats_slots(N, z.shape[2], z.shape[3])),)
+    return out
+
+
+def bn_up_ok(z, lo, training, D=8):
+    """the residual of bn_act can be given as the low-resolution map `lo` [N, C, H/2, W/2] (s2f_bn_act_up_fwd): fp32 CUDA maps of
+    exactly twice the size on the train-mode row-walking kernels (s2f_bn_up_ok)"""
+    if not (training and z.dim() == 4 and lo.dim() == 4 and z.is_cuda and lo.is_cuda and z.dtype == lo.dtype == torch.float32
+            and z.numel() and lo.shape[:2] == z.shape[:2] and (2 * lo.shape[2], 2 * lo.shape[3]) == tuple(z.shape[2:])):
+        return False
+    return bool(lib.s2f_bn_up_ok(z.shape[0], z.shape[1], z.shape[2], z.shape[3], 1, D))
 
 
 def bn_act(z, conv_bias, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, residual=None,
-           lif=False, want_pre=True, v_in=None, keep_v=False, D=8, vth=1.0, stats=None, want_border=False, partials=None):
+           lif=False, want_pre=True, v_in=None, keep_v=False, D=8, vth=1.0, stats=None, want_border=False, partials=None,
+           residual_lo=None, lo_skip=False):
     """-> (u or None, y or None, v_out or None [, border]); y is a Spikes pair (bf16 when cfg.SPIKES_BF16); border [C] = BN(0)
     from the updated running statistics (BNAndPadLayer's padding value), produced by the same kernel.
-    partials: the [C, P, 2] per-tile sums the producing GEMM stored for z (cfg.BN_PARTIALS; default: z's `_s2f_part` attribute)."""
+    partials: the [C, P, 2] per-tile sums the producing GEMM stored for z (cfg.BN_PARTIALS; default: z's `_s2f_part` attribute).
+    residual_lo: the residual is upsample_bilinear(residual_lo, z.shape[-2:]) -- formed inside the BatchNorm kernel where bn_up_ok
+    (the up-sampled map never exists), by ops.upsample_bilinear otherwise; the result then ends with the pass-through of residual_lo
+    (`lo_skip`: for a second reader, as upsample_bilinear(skip=True); else residual_lo itself)."""
     if partials is None:
         from .gemm import stats_of
         partials = stats_of(z)
     bf16 = bool(lif) and spikes_bf16_ok(D) and z.numel() % 4 == 0          # as ops.lif: consumers read bf16 spikes in 8-byte groups
-    u, y, v, border, ydata, tok2 = _BNAct.apply(z, conv_bias, gamma, beta, residual, v_in, running_mean, running_var, nbt, training,
-                                                momentum, eps, lif, want_pre, keep_v, D, vth, stats, bf16, partials)
+    up_lo, through = None, residual_lo
+    if residual_lo is not None:
+        assert residual is None
+        if bn_up_ok(z, residual_lo, training, D):
+            up_lo = residual_lo
+        else:
+            from .misc import upsample_bilinear
+            residual = upsample_bilinear(residual_lo, z.shape[-2:], skip=lo_skip)
+            if lo_skip:
+                residual, through = residual
+    port = bool(up_lo is not None and lo_skip and cfg.FANOUT_PORTS)
+    u, y, v, border, ydata, tok2, thr = _BNAct.apply(z, conv_bias, gamma, beta, residual, v_in, running_mean, running_var, nbt,
+                                                     training, momentum, eps, lif, want_pre, keep_v, D, vth, stats, bf16, partials,
+                                                     up_lo, port)
+    if port:
+        through = thr
     if lif:
         y = Spikes(ydata, y, tok2 if tok2.numel() else None) if bf16 else Spikes(y, None)
     out = (u if want_pre else None), (y if lif else None), (v if (lif and keep_v) else None)
-    return out + (border,) if want_border else out
+    if want_border:
+        out += (border,)
+    return out + (through,) if residual_lo is not None else out
 
 
 

@@ -12,7 +12,7 @@ class _DWConv(torch.autograd.Function):
     x: fp32, or a bf16 spike map with its autograd handle `tok`."""
 
     @staticmethod
-    def forward(ctx, x, tok, w, border, pad):
+    def forward(ctx, x, tok, w, border, pad, stats=False):
         _need_cuda(w, border, spikes=x)
         x, w = x.contiguous(), w.contiguous()
         N, C, H, W = x.shape
@@ -22,15 +22,30 @@ class _DWConv(torch.autograd.Function):
         if border is not None:
             border = border.contiguous()
         xb = int(x.dtype == torch.bfloat16)
-        check(lib.s2f_dwconv_fwd(_ptr(x), _ptr(w), _ptr(border), _ptr(y), N, C, H, W, K, pad, xb, _stream()),
-              "s2f_dwconv_fwd")
+        # a train-mode BatchNorm follows (3 x 3 'same', no border): the stencil stores its per-workgroup (sum, sum of squares) next to
+        # y and hands them over like the GEMMs do (cfg.BN_PARTIALS, gemm.stats_of) -- no statistics pass over y
+        P = 0
+        if stats and K == 3 and pad == 1 and border is None and _want_partials(True, N, C, H * W) and x.data_ptr() % 16 == 0:
+            P = int(lib.s2f_dwconv_stats_slots(N, H, W))
+        if P:
+            part = torch.empty(C, P, 2, dtype=torch.float32, device=x.device)
+            check(lib.s2f_dwconv_fwd_stats(_ptr(x), _ptr(w), _ptr(y), _ptr(part), P, N, C, H, W, xb, _stream()), "s2f_dwconv_fwd_stats")
+        else:
+            check(lib.s2f_dwconv_fwd(_ptr(x), _ptr(w), _ptr(border), _ptr(y), N, C, H, W, K, pad, xb, _stream()),
+                  "s2f_dwconv_fwd")
         ctx.save_for_backward(x, w, border)
         ctx.pad, ctx.has_tok = pad, tok is not None
-        return y
+        if not P:
+            part = y.new_empty(0)
+        ctx.mark_non_differentiable(part)
+        ctx.set_materialize_grads(False)          # (no zero-filled "gradient" of the partials)
+        return y, part
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, gy, _gpart=None):
         x, w, border = ctx.saved_tensors
+        if gy is None:
+            return (None,) * 6
         gy = gy.contiguous()
         N, C, H, W = x.shape
         K = w.shape[-1]
@@ -46,7 +61,7 @@ class _DWConv(torch.autograd.Function):
             check(lib.s2f_dwconv_bwd_weight(_ptr(x), _ptr(border), _ptr(gy), _ptr(gw if sink is None else sink), N, C, H, W,
                                             K, ctx.pad, int(sink is not None), int(x.dtype == torch.bfloat16),
                                             side.cuda_stream if side is not None else _stream()), "s2f_dwconv_bwd_weight")
-        return _grad_pair(ctx.has_tok, gx) + (gw, None, None)
+        return _grad_pair(ctx.has_tok, gx) + (gw, None, None, None)
 
 
 def dwconv_bn_lif_eval(x, w, pad, running_mean, running_var, gamma, beta, eps, border=None, want_pre=False, lif=False, D=8, vth=1.0,
@@ -69,10 +84,14 @@ def dwconv_bn_lif_eval(x, w, pad, running_mean, running_var, gamma, beta, eps, b
     return u, (Spikes(y, _new_tok(y)) if lif else None)
 
 
-def dwconv(x, w, pad, border=None):
-    """x: fp32 tensor or Spikes"""
+def dwconv(x, w, pad, border=None, stats=False):
+    """x: fp32 tensor or Spikes.  stats: the consumer is a train-mode BatchNorm -- where the stencil can (3 x 3, pad 1, no border,
+    cfg.BN_PARTIALS) it stores the BatchNorm partials with y and hands them over as y's `_s2f_part` (gemm.stats_of)"""
     data, tok = _unpack(x)
-    return _DWConv.apply(data, tok, w, border, pad)
+    y, part = _DWConv.apply(data, tok, w, border, pad, bool(stats))
+    if part.numel():
+        y._s2f_part = (part, y._version, y.data_ptr())
+    return y
 
 
 

@@ -103,20 +103,27 @@ class DCNTransformerEncoderPixelDecoder(nn.Module):
         # the pass-through the up-sampling hands back (ops.upsample_bilinear skip=True): its gradient is summed inside the up-sampling's
         # adjoint kernel instead of by an add launch of the autograd engine over the [T*B, C, H, W] map.
         def level(i, y, keep=None):
-            up, through = ops.upsample_bilinear(y, feats[i].shape[-2:], skip=True)
-            if keep is not None:
-                keep.append(through.reshape(t, bs, *through.shape[1:]))
             if lat_eval:
+                up, through = ops.upsample_bilinear(y, feats[i].shape[-2:], skip=True)
                 x = self.lateral_convs_spike[i].fire(feats[i]).flatten(0, 1)
                 _, s = conv_bn_act(self.lateral_convs[i][0], x, self.lateral_convs[i][1], residual=up, lif=self.output_convs_spike[i])
             else:
                 z, handle = lat[i]
                 ops.join(handle, (z,))
-                # cur + upsample(y), then the output neuron: residual add and neuron fused into the BatchNorm kernel
-                _, s = bn_act(z, self.lateral_convs[i][0].bias, self.lateral_convs[i][1], residual=up, lif=self.output_convs_spike[i])
-            # the last level feeds only mask_feature_spike: that neuron is applied by the same BatchNorm kernel (prefire)
-            # instead of a separate pass over the [T*B, C, H/2, W/2] map (537 MB at C2)
-            return conv_bn(self.output_convs[i], s, next_lif=self.mask_feature_spike if i == 0 else None)[0]
+                # cur + upsample(y), then the output neuron: up-sampling, residual add and neuron inside the BatchNorm kernel -- the
+                # up-sampled map (537 MB at the H/2 level of C2) is never written (ops.bn_up_ok; two launches on other shapes)
+                _, s, through = bn_act(z, self.lateral_convs[i][0].bias, self.lateral_convs[i][1], residual_lo=y,
+                                       lif=self.output_convs_spike[i])
+            if keep is not None:
+                keep.append(through.reshape(t, bs, *through.shape[1:]))
+            # the last level feeds only mask_feature_spike: that neuron is applied by the same BatchNorm kernel, which hands out its
+            # spikes (no separate pass over the [T*B, C, H/2, W/2] map, and no fp32 pre-activation of it: 537 MB at C2)
+            if i == 0:
+                mfs = self.mask_feature_spike
+                if mfs._forward_pre_hooks:          # (a pre-hook may replace the neuron's input: the module call, on the stored u)
+                    return mfs.fire(conv_bn(self.output_convs[i], s, next_lif=mfs)[0])
+                return conv_bn(self.output_convs[i], s, lif=mfs)[1]
+            return conv_bn(self.output_convs[i], s)[0]
 
         for i in range(self.num_inputs - 2, 0, -1):
             y = level(i, y, out)          # (appends the map that entered this level)
@@ -128,8 +135,7 @@ class DCNTransformerEncoderPixelDecoder(nn.Module):
                 and mfc.in_channels % 32 == 0 and not self.mask_feature_spike._forward_hooks)
 
         def finest(y=y):
-            y0 = level(0, y, out)          # (the pass-through is a view of y: nothing of it is computed on the side stream)
-            s0 = self.mask_feature_spike.fire(y0)
+            s0 = level(0, y, out)          # (the pass-through is a view of y: nothing of it is computed on the side stream)
             if fold and isinstance(s0, ops.Spikes) and s0.tok is not None and (s0.shape[-1] * s0.shape[-2]) % 8 == 0:
                 return s0
             return self.mask_feature(s0)
