@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 38
+#define S2F_ABI_VERSION 39
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -620,6 +620,47 @@ int s2f_aug_crop_stats(const uint8_t* data, int64_t data_bytes, const S2fAugPara
 int s2f_aug_apply(const uint8_t* data, int64_t data_bytes, const S2fAugParams* params, const int* flags, int B, int Hc, int Wc,
                   float mean0, float mean1, float mean2, float std0, float std1, float std2, int bgr_to_rgb, float pad_val,
                   int seg_pad_val, int reduce_zero_label, float* inputs, uint8_t* seg, void* stream);
+
+/* ---- test-time views: the configs' test_pipeline / tta_pipeline + SegDataPreProcessor's test branch (csrc/augment.hip, ABI 39) ----
+ * Resize(keep_ratio) -> RandomFlip(prob 0 | 1, horizontal) of every view of a test iteration (the data-set files under mmseg's configs/_base_/datasets:
+ * test_pipeline, tta_pipeline: TestTimeAug's scales x flips; the resize itself is mmcv's) and SegDataPreProcessor.forward(training =
+ * False) (channel swap, (x - mean) / std, pad right / bottom by test_cfg's size / size_divisor) as ONE launch from the decoded
+ * pictures to every view, each a [3, Hp, Wp] fp32 block of its own size inside one packed buffer.  The sizes are computed by the
+ * caller and arrive in the table; the kernel is a function of its inputs, allocates nothing and synchronises nothing: capturable
+ * in a hipGraph.
+ * data: `data_bytes` device bytes holding uint8 HWC BGR pictures [h0, w0, 3] with NO alignment.  params: V table entries in device
+ * memory (8-byte aligned), one per (view, image):
+ *   img_off : byte offset of the picture in data          out_off : ELEMENT offset of the entry's block in out, a multiple of 4
+ *   h0, w0  : source size      H, W : size after the resize      Hp, Wp : padded size, >= H, W      flip : horizontal flip of the
+ *   RESIZED picture (before the padding: the padding stays on the right)
+ * Entry v, output pixel (c, y, x) of its block:
+ *   y < H and x < W : resized pixel (y, flip ? W - 1 - x : x) -- the bilinear sample of the picture with half-pixel centres and no
+ *     antialias, scale = in / out, rounded to nearest into uint8: s2f_aug_apply's resize step, operation for operation (the same
+ *     device code), so H == h0 and W == w0 reproduces the source bytes; channel (bgr_to_rgb ? 2 - c : c) of that, (v - mean_c) /
+ *     std_c with an IEEE divide (mean 0, std 1: none).  Every step is one fp32 operation (tests/view_ref.py restates them).
+ *   elsewhere (up to Hp, Wp) : pad_val itself, un-normalised, as stack_batch pads after the normalisation.
+ * Every element of every entry's block is written once; elements of out between the blocks are not touched (the blocks are
+ * disjoint: the caller's business).  The table is untrusted: an entry whose block does not fit out (out_off < 0, not a multiple
+ * of 4 or out_off + 3 Hp Wp > out_elems; Hp, Wp outside 1 .. max_Hp, max_Wp) is SKIPPED; an entry whose picture does not fit data
+ * (or with a non-positive size, or H > Hp, W > Wp) yields an all-pad_val block; tap indices are clamped into the source.  No load
+ * leaves data and no store leaves out, whatever the table holds.
+ * max_Hp, max_Wp: the largest Hp and the largest Wp of the table (what the grid is sized by: an entry beyond them is skipped).
+ * Bounds: 0 < V <= 65535, 0 < max_Hp, max_Wp <= S2F_AUG_MAX_CROP.  16-byte stores for an entry with Wp % 4 == 0 when out is
+ * 16-byte aligned (out_off % 4 == 0 then aligns the block), scalar stores otherwise. */
+typedef struct S2fViewParams {
+  int64_t img_off;
+  int64_t out_off;
+  int32_t h0, w0;
+  int32_t H, W;
+  int32_t Hp, Wp;
+  int32_t flip;
+  int32_t reserved;
+} S2fViewParams;
+/* sizeof(S2fViewParams): what a binding checks its mirror of the layout against */
+int s2f_view_param_bytes(void);
+int s2f_test_views(const uint8_t* data, int64_t data_bytes, const S2fViewParams* params, int V, int max_Hp, int max_Wp, float mean0,
+                   float mean1, float mean2, float std0, float std1, float std2, int bgr_to_rgb, float pad_val, float* out,
+                   int64_t out_elems, void* stream);
 
 /* ---- batched transposition of the last two dimensions: x [B, R, C] -> y [B, C, R] (fp32) -----------------------------------
  * Replaces the `.permute(0, 1, 3, 4, 2)` / `.permute(0, 1, 4, 2, 3)` copies around the DCNv3 sampling core

@@ -18,7 +18,7 @@ from . import reparam  # noqa: F401
 from .segmentor import EncoderDecoder, ResetModelHook, headline_loss  # noqa: F401
 from .tta import SegTTAModel  # noqa: F401
 from .metrics import IoUMetric, evaluate  # noqa: F401
-from .augment import TrainAugment  # noqa: F401
+from .augment import TestAugment, TrainAugment  # noqa: F401
 from .train import LinearThenPoly, OptimWrapper, parse_losses, train_step  # noqa: F401
 
 __version__ = "0.1.0"

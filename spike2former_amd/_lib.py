@@ -74,6 +74,8 @@ SIGNATURES = {
     "s2f_aug_param_bytes": (_i, []),
     "s2f_aug_crop_stats": (_i, [_p, _i64, _p, _i, _i, _i, _i, _i, ctypes.c_double, _p, _p]),
     "s2f_aug_apply": (_i, [_p, _i64, _p, _p, _i, _i, _i] + [_f] * 6 + [_i, _f, _i, _i, _p, _p, _p]),
+    "s2f_view_param_bytes": (_i, []),
+    "s2f_test_views": (_i, [_p, _i64, _p, _i, _i, _i] + [_f] * 6 + [_i, _f, _p, _i64, _p]),
     "s2f_transpose_last2": (_i, [_p, _p, _i64, _i, _i, _p]),
     "s2f_transpose_last2_add": (_i, [_p, _p, _p, _i64, _i, _i, _p]),
     "s2f_sum_n": (_i, [_p, _i, _p, _i64, _p]),

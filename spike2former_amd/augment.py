@@ -17,7 +17,14 @@ reference's stream of random numbers, neither of which changes a distribution:
     only behind its switch.  The eleven origins are independent and identically distributed and the chosen one is the first that
     passes among the first ten, else the eleventh: the distribution of the chosen crop is the reference's.
   * the generator is a `numpy.random.Generator` seeded from (seed, rank), not mmcv's use of the global `numpy.random` state: a run
-    here does not reproduce the reference's sequence of augmentations, only its distribution."""
+    here does not reproduce the reference's sequence of augmentations, only its distribution.
+
+`TestAugment` (below) is the test-time counterpart: the configs' `test_pipeline` / `tta_pipeline` and the pre-processor's test branch
+as one H2D copy and ONE launch, from decoded pictures to the metric in three lines:
+
+    aug = TestAugment.from_cfg(cfg.tta_pipeline, cfg.model.data_preprocessor, reduce_zero_label=True)
+    metric = IoUMetric(label_reduce_zero=aug.reduce_zero_label); metric.dataset_meta = dict(classes=...)
+    evaluate(SegTTAModel(model), (aug([img], [seg], [path]) for img, seg, path in pictures), metric)"""
 import os
 
 import numpy as np
@@ -275,3 +282,335 @@ class TrainAugment:
     def __call__(self, images, segs, params=None, out=None):
         self.stage(images, segs, params)
         return self.launch(out)
+
+
+# ---------------------------------------------------------------------------------------------------- the test pipeline
+VIEW_PARAM_DTYPE = ops.VIEW_PARAM_DTYPE          # include/s2f.h S2fViewParams (ops.VIEW_PARAM_BYTES is the library's sizeof)
+_TEST_ORDER = ("LoadImageFromFile", "Resize", "LoadAnnotations", "PackSegInputs")
+_TTA_ORDER = ("Resize", "RandomFlip", "LoadAnnotations", "PackSegInputs")
+
+
+def _only_test(cfg, allowed, what):
+    extra = sorted(set(cfg) - set(allowed) - {"type"})
+    if extra:
+        raise NotImplementedError(f"TestAugment: {what} option(s) {extra} are not implemented on the device")
+
+
+def scale_factor_size(h0, w0, ratio):
+    """mmcv Resize(scale_factor=ratio, keep_ratio=True) -> (H, W): first scale = (int(w0 r + 0.5), int(h0 r + 0.5)) (_scale_size),
+    then the keep-ratio rescale TO that size: f = min(max(scale) / max(h0, w0), min(scale) / min(h0, w0)), (int(h0 f + 0.5),
+    int(w0 f + 0.5)) (rescale_size).  (512 x 683 at 1.5 -> 768 x 1025: the width is rounded twice.)"""
+    s = (int(w0 * ratio + 0.5), int(h0 * ratio + 0.5))
+    f = min(max(s) / max(h0, w0), min(s) / min(h0, w0))
+    return int(h0 * f + 0.5), int(w0 * f + 0.5)
+
+
+def _resize_args(t, what):
+    _only_test(t, ("scale", "scale_factor", "keep_ratio"), what)
+    if not t.get("keep_ratio", False):
+        raise NotImplementedError(f"TestAugment: {what} with keep_ratio=False is not implemented on the device")
+    if ("scale" in t) == ("scale_factor" in t):
+        raise NotImplementedError(f"TestAugment: {what} takes one of scale=(long, short) and scale_factor=r")
+    if "scale" in t:
+        s = t["scale"]
+        if not isinstance(s, (tuple, list)) or len(s) != 2 or not all(isinstance(v, int) for v in s):
+            raise NotImplementedError(f"TestAugment: {what} needs one (long, short) scale, got {s!r}")
+        return tuple(s), None
+    r = t["scale_factor"]
+    if isinstance(r, (tuple, list)) or not r > 0:
+        raise NotImplementedError(f"TestAugment: {what} needs one positive scale_factor, got {r!r}")
+    return None, float(r)
+
+
+class TestAugment:
+    """The shipped configs' `test_pipeline` / `tta_pipeline` -- Resize(keep_ratio=True) [x RandomFlip(prob 0 | 1)] -- and the test
+    branch of `SegDataPreProcessor` (channel swap, (x - mean) / std, padding by test_cfg's size / size_divisor) as ONE H2D copy and
+    ONE HIP launch (s2f_test_views, csrc/augment.hip) from the decoded uint8 pictures of an iteration to every view of it: the
+    test-time counterpart of `TrainAugment`, with the bilinear arithmetic the training pictures were resized by (the kernel shares
+    the sampling code with s2f_aug_apply).  File loading is not here: the caller hands in decoded BGR pictures.
+
+        aug = TestAugment.from_cfg(cfg.tta_pipeline, cfg.model.data_preprocessor, reduce_zero_label=True)
+        metric = IoUMetric(label_reduce_zero=aug.reduce_zero_label); metric.dataset_meta = dict(classes=...)
+        evaluate(SegTTAModel(model), (aug([img], [seg], [path]) for img, seg, path in pictures), metric)
+
+    (`cfg.test_pipeline` and the plain model alike.)  The annotations are NOT transformed: as in the reference, where LoadAnnotations
+    comes after the resize and the flips, `gt_sem_seg` is the raw map at the picture's own size, and the label reduction is the
+    metric's (`IoUMetric(label_reduce_zero=aug.reduce_zero_label)`).
+
+    The sizes follow mmcv 2.x (Resize.transform, _scale_size, rescale_size: `view_sizes`) and mmseg's stack_batch; mmcv is not
+    available to this project, the rule is restated from its source.  The resize itself is OpenCV's in the reference; here it is
+    the fp32 bilinear kernel of the training path (the distance between the two has not been measured).
+
+    What a call returns -- the views and the annotations -- lives in persistent device buffers of this object and is valid until
+    the next call."""
+    __test__ = False          # (pytest: a class named Test* imported into a test module is not a test)
+
+    def __init__(self, scale=(2048, 512), scale_factors=None, flips=(False,), reduce_zero_label=False, mean=None, std=None,
+                 bgr_to_rgb=False, pad_val=0, size=None, size_divisor=None, batch_size=1, max_source_pixels=2048 * 1024, device="cuda",
+                 tta=None):
+        """scale: Resize's (long, short), or None; scale_factors: the ratios of TestTimeAug's Resize(scale_factor=r) list, or None
+        (at most one of the two; neither: no resize); flips: the horizontal flips of every size, in order; reduce_zero_label:
+        LoadAnnotations' (recorded in the metainfo and for the metric: the kernel does not touch annotations); mean, std,
+        bgr_to_rgb, pad_val: SegDataPreProcessor's; size (h, w) / size_divisor: its test_cfg's (at most one).  batch_size pictures of
+        at most max_source_pixels pixels fit the staging buffers (4 bytes per pixel: the picture and its annotation).  tta: whether a
+        call returns the dict-of-per-view-lists SegTTAModel takes or the one batch a model's test_step takes (one view only);
+        default: the TTA form iff scale_factors or more than one flip is given."""
+        if scale is not None and scale_factors is not None:
+            raise ValueError("one Resize: scale or scale_factors, not both")
+        self.scale = None if scale is None else (int(scale[0]), int(scale[1]))
+        self.scale_factors = None if scale_factors is None else tuple(float(r) for r in scale_factors)
+        self.flips = tuple(bool(f) for f in flips)
+        if not self.flips or (self.scale_factors is not None and not self.scale_factors):
+            raise ValueError("at least one view")
+        self.tta = bool(self.scale_factors is not None or len(self.flips) > 1) if tta is None else bool(tta)
+        self.n_views = len(self.scale_factors or (None,)) * len(self.flips)
+        if not self.tta and self.n_views != 1:
+            raise ValueError(f"{self.n_views} views need the TTA form")
+        self.reduce_zero_label = bool(reduce_zero_label)
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std go together")
+        self.mean = None if mean is None else [float(v) for v in mean]
+        self.std = None if std is None else [float(v) for v in std]
+        self.bgr_to_rgb, self.pad_val = bool(bgr_to_rgb), float(pad_val)
+        if size is not None and size_divisor is not None:
+            raise ValueError("only one of size and size_divisor should be valid")
+        self.size = None if size is None else (int(size[0]), int(size[1]))
+        self.size_divisor = None if size_divisor is None else int(size_divisor)
+        self.batch_size, self.max_source_pixels = int(batch_size), int(max_source_pixels)
+        if self.batch_size <= 0 or self.max_source_pixels <= 0:
+            raise ValueError("batch_size and max_source_pixels are positive")
+        self.device = torch.device(device)
+        # the table first (its size is a multiple of 16: the packed bytes behind it start aligned), then the pixels
+        self._table_cap = (self.n_views * self.batch_size * VIEW_PARAM_DTYPE.itemsize + 15) // 16 * 16
+        self._data_cap = self.batch_size * self.max_source_pixels * 4
+        self._pin = self._dev = self._out = self._copied = None
+        self._staged = None
+
+    # ------------------------------------------------------------------------------------------------ configuration
+    @classmethod
+    def from_cfg(cls, pipeline, data_preprocessor, reduce_zero_label=False, **kwargs):
+        """pipeline: an mmseg config's `test_pipeline` (LoadImageFromFile, Resize(scale=(long, short), keep_ratio=True),
+        LoadAnnotations, PackSegInputs) or `tta_pipeline` (LoadImageFromFile, TestTimeAug(transforms=[[Resize(scale_factor=r,
+        keep_ratio=True) ...], [RandomFlip(prob=0. | 1., direction='horizontal') ...], [LoadAnnotations], [PackSegInputs]]): the
+        views are ordered as itertools.product orders them, ratio slowest, flip fastest); data_preprocessor: the model's
+        SegDataPreProcessor dictionary (mean, std, bgr_to_rgb, pad_val and test_cfg's size / size_divisor are used).  Any other
+        transform, order or option raises NotImplementedError.  reduce_zero_label: what a LoadAnnotations without the option takes
+        (in mmseg: the data set's).  kwargs: batch_size, max_source_pixels, device."""
+        kinds = [t.get("type") for t in pipeline]
+        a = dict(scale=None, scale_factors=None, flips=(False,), reduce_zero_label=bool(reduce_zero_label))
+
+        def annotations(t):
+            _only_test(t, ("reduce_zero_label",), "LoadAnnotations")
+            a["reduce_zero_label"] = bool(t.get("reduce_zero_label", reduce_zero_label))
+
+        if "TestTimeAug" in kinds:
+            if kinds != ["LoadImageFromFile", "TestTimeAug"]:
+                raise NotImplementedError(f"TestAugment: a tta_pipeline is LoadImageFromFile, TestTimeAug; got {kinds}")
+            _only_test(pipeline[0], (), "LoadImageFromFile")
+            _only_test(pipeline[1], ("transforms",), "TestTimeAug")
+            seen = []
+            for group in pipeline[1]["transforms"]:
+                group = [group] if isinstance(group, dict) else list(group)
+                names = sorted({t.get("type") for t in group})
+                for kind in names:
+                    if kind not in _TTA_ORDER:
+                        raise NotImplementedError(f"TestAugment: transform {kind!r} is not implemented on the device")
+                if len(names) != 1:
+                    raise NotImplementedError(f"TestAugment: one kind of transform per TestTimeAug list, got {names}")
+                kind = names[0]
+                if seen and _TTA_ORDER.index(kind) <= _TTA_ORDER.index(seen[-1]):
+                    raise NotImplementedError(f"TestAugment: {kind} after {seen[-1]}: the kernel applies the transforms in the order "
+                                              f"{' -> '.join(_TTA_ORDER)}")
+                seen.append(kind)
+                if kind == "Resize":
+                    args = [_resize_args(t, "Resize") for t in group]
+                    if any(s is not None for s, _ in args):
+                        raise NotImplementedError("TestAugment: TestTimeAug's Resize list takes scale_factor=r entries")
+                    a["scale_factors"] = tuple(r for _, r in args)
+                elif kind == "RandomFlip":
+                    flips = []
+                    for t in group:
+                        _only_test(t, ("prob", "direction"), "RandomFlip")
+                        if t.get("direction", "horizontal") != "horizontal":
+                            raise NotImplementedError(f"TestAugment: RandomFlip direction={t['direction']!r}: only 'horizontal' is "
+                                                      f"implemented on the device")
+                        prob = t.get("prob")
+                        if isinstance(prob, (list, tuple)) or prob is None or float(prob) not in (0.0, 1.0):
+                            raise NotImplementedError(f"TestAugment: RandomFlip prob={prob!r}: a test-time flip is certain (prob 0 or 1)")
+                        flips.append(float(prob) == 1.0)
+                    a["flips"] = tuple(flips)
+                elif kind == "LoadAnnotations":
+                    if len(group) != 1:
+                        raise NotImplementedError("TestAugment: one LoadAnnotations")
+                    annotations(group[0])
+                elif len(group) != 1:
+                    raise NotImplementedError("TestAugment: one PackSegInputs")
+                else:
+                    _only_test(group[0], (), "PackSegInputs")
+            if not seen or seen[-1] != "PackSegInputs":
+                raise NotImplementedError("TestAugment: TestTimeAug's transforms end in [PackSegInputs]")
+            a["tta"] = True
+        else:
+            seen = []
+            for t, kind in zip(pipeline, kinds):
+                if kind not in _TEST_ORDER:
+                    raise NotImplementedError(f"TestAugment: transform {kind!r} is not implemented on the device")
+                if seen and _TEST_ORDER.index(kind) <= _TEST_ORDER.index(seen[-1]):
+                    raise NotImplementedError(f"TestAugment: {kind} after {seen[-1]}: the kernel applies the transforms in the order "
+                                              f"{' -> '.join(_TEST_ORDER)}")
+                seen.append(kind)
+                if kind in ("LoadImageFromFile", "PackSegInputs"):
+                    _only_test(t, (), kind)
+                elif kind == "LoadAnnotations":
+                    annotations(t)
+                else:
+                    scale, ratio = _resize_args(t, "Resize")
+                    a["scale"], a["scale_factors"] = scale, None if ratio is None else (ratio,)
+            a["tta"] = False
+        p = dict(data_preprocessor)
+        if p.pop("type", "SegDataPreProcessor") != "SegDataPreProcessor":
+            raise NotImplementedError("TestAugment: the data preprocessor is a SegDataPreProcessor")
+        _only_test(p, ("mean", "std", "bgr_to_rgb", "rgb_to_bgr", "pad_val", "seg_pad_val", "size", "test_cfg", "batch_augments",
+                       "size_divisor"), "SegDataPreProcessor")
+        if p.get("batch_augments") is not None:
+            raise NotImplementedError("TestAugment: SegDataPreProcessor batch_augments are not implemented on the device")
+        if p.get("bgr_to_rgb") and p.get("rgb_to_bgr"):
+            raise ValueError("`bgr2rgb` and `rgb2bgr` cannot be set to True at the same time")
+        test_cfg = dict(p.get("test_cfg") or {})          # (size / size_divisor OUTSIDE test_cfg are the training branch's)
+        _only_test(test_cfg, ("size", "size_divisor"), "SegDataPreProcessor test_cfg")
+        a.update(mean=p.get("mean"), std=p.get("std"), bgr_to_rgb=bool(p.get("bgr_to_rgb") or p.get("rgb_to_bgr")),
+                 pad_val=p.get("pad_val", 0), size=test_cfg.get("size"), size_divisor=test_cfg.get("size_divisor"))
+        return cls(**a, **kwargs)
+
+    # ------------------------------------------------------------------------------------------------ geometry
+    def padded_size(self, H, W):
+        """mmseg stack_batch on pictures of one size: `size`: max(size - dim, 0) of padding; `size_divisor`: rounded up; else none"""
+        if self.size is not None:
+            return H + max(self.size[0] - H, 0), W + max(self.size[1] - W, 0)
+        if self.size_divisor is not None and self.size_divisor > 1:
+            d = self.size_divisor
+            return (H + d - 1) // d * d, (W + d - 1) // d * d
+        return H, W
+
+    def view_sizes(self, h0, w0):
+        """-> [(H, W, Hp, Wp, flip)] of the views of an h0 x w0 picture, in view order (ratio slowest, flip fastest).  Pure host
+        arithmetic, restated from mmcv 2.x: Resize(scale) is `resized_size(h0, w0, scale, 1.0)`, Resize(scale_factor=r) is
+        `scale_factor_size` (both mmcv.image.geometric.rescale_size on a size from _scale_size); the padding is stack_batch's."""
+        h0, w0 = int(h0), int(w0)
+        views = []
+        for r in self.scale_factors or (None,):
+            if r is not None:
+                H, W = scale_factor_size(h0, w0, r)
+            elif self.scale is not None:
+                H, W = resized_size(h0, w0, self.scale, 1.0)
+            else:
+                H, W = h0, w0
+            views += [(H, W, *self.padded_size(H, W), f) for f in self.flips]
+        return views
+
+    def table(self, h0, w0, B=1, views=None):
+        """-> (the V * B table entries of VIEW_PARAM_DTYPE in (view, image) order, the elements of `out` they span).  Picture b lies
+        at byte 3 h0 w0 b of data; the blocks are packed in entry order, each starting at a multiple of 4 elements (16 bytes)."""
+        views = self.view_sizes(h0, w0) if views is None else [tuple(int(x) for x in v[:4]) + (bool(v[4]),) for v in views]
+        t = np.zeros(len(views) * B, VIEW_PARAM_DTYPE)
+        off = 0
+        for v, (H, W, Hp, Wp, flip) in enumerate(views):
+            for b in range(B):
+                p = t[v * B + b]
+                p["img_off"], p["out_off"] = 3 * h0 * w0 * b, off
+                p["h0"], p["w0"], p["H"], p["W"], p["Hp"], p["Wp"], p["flip"] = h0, w0, H, W, Hp, Wp, int(flip)
+                off = (off + 3 * Hp * Wp + 3) // 4 * 4
+        return t, off
+
+    # ------------------------------------------------------------------------------------------------ device side
+    def _allocate(self):
+        if self.device.type != "cuda":
+            raise RuntimeError("TestAugment runs on the GPU only (HIP kernels): there is no host route")
+        n = self._table_cap + self._data_cap
+        self._pin = torch.empty(n, dtype=torch.uint8).pin_memory()
+        self._dev = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self._copied = torch.cuda.Event()
+
+    def stage(self, images, segs=None, img_paths=None, views=None):
+        """Packs the table, the pictures and (if given) the raw annotations into the pinned staging buffer and queues ONE
+        host-to-device copy on the current stream; grows the packed output buffer if this iteration's views need more than any
+        before.  images: B <= batch_size uint8 [h0, w0, 3] BGR arrays of ONE size (numpy or CPU tensors); segs: uint8 [h0, w0];
+        views: [(H, W, Hp, Wp, flip)] instead of `view_sizes` (any sizes: what the tests of the kernel use).  -> the table."""
+        B = len(images)
+        if not 0 < B <= self.batch_size or (segs is not None and len(segs) != B) or (img_paths is not None and len(img_paths) != B):
+            raise ValueError(f"{B} pictures for a batch size of {self.batch_size} (with as many annotations and paths, if any)")
+        images = [np.ascontiguousarray(np.asarray(i)) for i in images]
+        segs = None if segs is None else [np.ascontiguousarray(np.asarray(s)) for s in segs]
+        shape = images[0].shape
+        for k, i in enumerate(images):
+            if i.dtype != np.uint8 or i.ndim != 3 or i.shape[2] != 3 or i.shape != shape:
+                raise ValueError("pictures are uint8 [h0, w0, 3] of ONE size (the reference's test branch asserts equal sizes)")
+            if segs is not None and (segs[k].dtype != np.uint8 or segs[k].shape != shape[:2]):
+                raise ValueError("annotations are uint8 [h0, w0] of the pictures' size")
+        h0, w0 = shape[:2]
+        if h0 * w0 > self.max_source_pixels or h0 * w0 == 0:
+            raise ValueError(f"a {h0} x {w0} picture does not fit max_source_pixels = {self.max_source_pixels}")
+        if views is not None and len(views) > self.n_views:
+            raise ValueError(f"{len(views)} views, the staging buffer holds the table of {self.n_views}")
+        table, out_elems = self.table(h0, w0, B, views)
+        n_img = 3 * h0 * w0 * B
+        ops.check_view_table(table, n_img, out_elems)
+        if self._pin is None:
+            self._allocate()
+        if self._out is None or self._out.numel() < out_elems:          # a new high-water mark (not inside a graph capture)
+            self._out = torch.empty(out_elems, dtype=torch.float32, device=self.device)
+        self._copied.synchronize()          # the previous copy has left the staging buffer
+        pin = self._pin.numpy()
+        pin[:table.nbytes] = table.view(np.uint8)
+        d0 = self._table_cap
+        for b, i in enumerate(images):
+            pin[d0 + 3 * h0 * w0 * b:d0 + 3 * h0 * w0 * (b + 1)] = i.reshape(-1)
+        n = d0 + n_img
+        if segs is not None:
+            for b, s in enumerate(segs):
+                pin[n + h0 * w0 * b:n + h0 * w0 * (b + 1)] = s.reshape(-1)
+            n += h0 * w0 * B
+        self._dev[:n].copy_(self._pin[:n], non_blocking=True)
+        self._copied.record()
+        self._staged = dict(table=table, B=B, shape=(h0, w0), n_img=n_img, segs=segs is not None, out_elems=out_elems,
+                            paths=list(img_paths) if img_paths is not None else [None] * B, tta=self.tta or views is not None)
+        return table
+
+    def launch(self):
+        """The ONE launch on the current stream over what `stage` last copied (capturable in a hipGraph: the table and the pixels
+        are read from their static device buffers at replay time), and the data the consumers take.  One batch (`tta` False):
+        dict(inputs=[B, 3, Hp, Wp], data_samples=[SegDataSample] * B, preprocessed=True); the TTA form: the same three keys, each a
+        list with one item per view -- what SegTTAModel.split_views splits.  `preprocessed` makes EncoderDecoder.preprocess pass
+        the batch through.  The tensors are views of this object's buffers: valid until the next call.  (B > 1 with 3 Hp Wp no
+        multiple of 4 -- odd sizes without a test_cfg: the blocks of a view cannot be both adjacent and 16-byte aligned; the view
+        is then a tensor whose batch stride is rounded up to 4 elements, not a contiguous one.)"""
+        from .data_preprocessor import PixelData, SegDataSample
+        st = self._staged
+        if st is None or self._dev is None:
+            raise RuntimeError("TestAugment.launch before stage")
+        table, B, (h0, w0) = st["table"], st["B"], st["shape"]
+        d0 = self._table_cap
+        ops.test_views(self._dev[d0:d0 + st["n_img"]], table, self._out[:st["out_elems"]], self.mean, self.std, self.bgr_to_rgb,
+                       self.pad_val, table_dev=self._dev[:table.nbytes])
+        gts = None
+        if st["segs"]:
+            gts = self._dev[d0 + st["n_img"]:d0 + st["n_img"] + h0 * w0 * B].view(B, 1, h0, w0)
+        inputs, samples = [], []
+        for v in range(len(table) // B):
+            p = table[v * B]
+            H, W, Hp, Wp, flip = int(p["H"]), int(p["W"]), int(p["Hp"]), int(p["Wp"]), bool(p["flip"])
+            stride = int(table[v * B + 1]["out_off"] - p["out_off"]) if B > 1 else 3 * Hp * Wp
+            inputs.append(self._out.as_strided((B, 3, Hp, Wp), (stride, Hp * Wp, Wp, 1), int(p["out_off"])))
+            meta = dict(ori_shape=(h0, w0), img_shape=(H, W), pad_shape=(Hp, Wp), scale_factor=(W / w0, H / h0), flip=flip,
+                        flip_direction="horizontal" if flip else None, reduce_zero_label=self.reduce_zero_label)
+            if self.size is not None or self.size_divisor is not None:
+                meta["img_padding_size"] = (0, Wp - W, 0, Hp - H)
+            samples.append([SegDataSample(gt_sem_seg=None if gts is None else PixelData(gts[b]),
+                                          metainfo=dict(meta, img_path=st["paths"][b])) for b in range(B)])
+        if st["tta"]:
+            return dict(inputs=inputs, data_samples=samples, preprocessed=[True] * len(inputs))
+        return dict(inputs=inputs[0], data_samples=samples[0], preprocessed=True)
+
+    def __call__(self, images, segs=None, img_paths=None, views=None):
+        self.stage(images, segs, img_paths, views)
+        return self.launch()

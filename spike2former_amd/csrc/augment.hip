@@ -17,6 +17,14 @@
 // The table lives in device memory the host wrote: both kernels treat it as untrusted.  A picture whose offsets or sizes do not fit
 // the byte buffer is treated as empty (all padding, every flag 0), origins are clamped into [0, margin] and tap indices into the
 // source, so no load leaves `data` whatever the table holds; stores are bounded by the grid alone.
+//
+// The test pipeline's counterpart (include/s2f.h "test-time views") lives here as well, so that it shares axis_taps and the
+// interpolation's order of operations with s2f_aug_apply -- a picture is resized at test time by the arithmetic it was trained on:
+//
+//   s2f_test_views     : ONE launch for every (view, image) of a test / TTA iteration: keep-ratio Resize, horizontal flip,
+//                        channel swap, normalisation and the padding of SegDataPreProcessor's test branch, into blocks of different
+//                        sizes packed in one fp32 buffer.  Here the table carries the store addresses too: an entry whose block
+//                        does not fit `out` is skipped, so no store leaves `out` either.
 #include "s2f_common.h"
 
 #pragma clang fp contract(off)
@@ -310,6 +318,92 @@ __global__ __launch_bounds__(kStatThreads) void aug_crop_stats_kernel(const uint
   if (tid == 0) flags[b * S2F_AUG_CANDIDATES + cand] = (s_present > 1u && (double)s_max / (double)s_sum < max_ratio) ? 1 : 0;
 }
 
+// ---- the test pipeline's views (include/s2f.h "test-time views") ---------------------------------------------------------------
+static_assert(sizeof(S2fViewParams) == 48 && sizeof(S2fViewParams) % 8 == 0, "ops/misc.py VIEW_PARAM_DTYPE mirrors this layout");
+
+struct ViewConst {
+  float mean[3], stdv[3];
+  float pad_val;
+  int swap;
+};
+
+// the entry's block fits `out` and the launch's grid covers it (3 * Hp * Wp <= 3 * 2^24: no overflow)
+__device__ __forceinline__ bool view_block_ok(const S2fViewParams& p, int max_hp, int max_wp, int64_t out_elems) {
+  if (p.Hp <= 0 || p.Wp <= 0 || p.Hp > max_hp || p.Wp > max_wp || p.out_off < 0 || (p.out_off & 3) != 0) return false;
+  return p.out_off <= out_elems - 3 * (int64_t)p.Hp * p.Wp;
+}
+
+// the entry's picture fits `data` and its resized size fits the block: -> h0 * w0 < 2^31, so every pixel index fits an int
+__device__ __forceinline__ bool view_picture_ok(const S2fViewParams& p, int64_t data_bytes) {
+  if (p.h0 <= 0 || p.w0 <= 0 || p.H <= 0 || p.W <= 0 || p.H > p.Hp || p.W > p.Wp || p.img_off < 0) return false;
+  const int64_t px = (int64_t)p.h0 * p.w0;
+  return px < ((int64_t)1 << 31) && p.img_off <= data_bytes - 3 * px;
+}
+
+// grid (tiles of 256 quads, V).  The padded plane of entry v is cut into QUADS of 4 consecutive columns of one row, ceil(Wp / 4) per
+// row; a thread produces one quad for the three channels: the row's taps and its two source rows once, one gather of the HWC source
+// per output column.  An entry with fewer quads than the grid's widest leaves its surplus workgroups at once.  BASE16: `out` is
+// 16-byte aligned, so (out_off % 4 == 0) a block is, and with Wp % 4 == 0 every quad is one 16-byte store per plane.
+template <bool BASE16>
+__global__ __launch_bounds__(256) void test_views_kernel(const uint8_t* __restrict__ data, int64_t data_bytes,
+                                                         const S2fViewParams* __restrict__ params, int max_hp, int max_wp,
+                                                         ViewConst k, float* __restrict__ out, int64_t out_elems) {
+  const S2fViewParams p = params[blockIdx.y];          // (uniform over the workgroup)
+  if (!view_block_ok(p, max_hp, max_wp, out_elems)) return;
+  const int Hp = p.Hp, Wp = p.Wp;
+  const int qpr = (Wp + 3) >> 2;
+  const int quad = (int)blockIdx.x * 256 + (int)threadIdx.x;          // < 2^22 + 256: max_hp, max_wp <= S2F_AUG_MAX_CROP
+  if (quad >= Hp * qpr) return;
+  const int oy = quad / qpr, ox = (quad - oy * qpr) * 4;
+  const bool ok = view_picture_ok(p, data_bytes);
+  const int h0 = p.h0, w0 = p.w0, H = ok ? p.H : 0, W = ok ? p.W : 0;
+  float o[3][4];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[c][j] = k.pad_val;
+  if (oy < H && ox < W) {
+    const float scale_x = (float)w0 / (float)W, scale_y = (float)h0 / (float)H;
+    int y0, y1;
+    float ly;
+    axis_taps(scale_y, h0, oy, y0, y1, ly);
+    const uint8_t* img = data + p.img_off;
+    const uint8_t* r0 = img + (int64_t)y0 * w0 * 3;
+    const uint8_t* r1 = img + (int64_t)y1 * w0 * 3;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (ox + j >= W) continue;
+      int x0, x1;
+      float lx;
+      axis_taps(scale_x, w0, p.flip ? W - 1 - (ox + j) : ox + j, x0, x1, lx);
+      x0 *= 3;
+      x1 *= 3;
+      int bgr[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {          // s2f_aug_apply's resize step, operation for operation
+        const float top = (1.f - lx) * (float)r0[x0 + c] + lx * (float)r0[x1 + c];
+        const float bot = (1.f - lx) * (float)r1[x0 + c] + lx * (float)r1[x1 + c];
+        bgr[c] = (int)rintf((1.f - ly) * top + ly * bot);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c][j] = ((float)bgr[k.swap ? 2 - c : c] - k.mean[c]) / k.stdv[c];
+    }
+  }
+  const int64_t plane = (int64_t)Hp * Wp;
+  float* dst = out + p.out_off + (int64_t)oy * Wp + ox;
+  if (BASE16 && (Wp & 3) == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(dst + c * plane) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (ox + j < Wp) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[c * plane + j] = o[c][j];
+      }
+  }
+}
+
 int check_common(const char* what, const void* data, int64_t data_bytes, const void* params, int B, int Hc, int Wc) {
   S2F_REQUIRE(data && params, S2F_EINVAL, "%s: null pointer", what);
   S2F_REQUIRE(data_bytes > 0, S2F_EINVAL, "%s: bad byte count %lld", what, (long long)data_bytes);
@@ -356,4 +450,30 @@ extern "C" int s2f_aug_apply(const uint8_t* data, int64_t data_bytes, const S2fA
     hipLaunchKernelGGL((aug_apply_kernel<v.value>), grid, dim3(256), 0, s, data, data_bytes, params, flags, Hc, Wc, k, inputs, seg);
   });
   return s2f_check_launch("s2f_aug_apply");
+}
+
+extern "C" int s2f_view_param_bytes(void) { return (int)sizeof(S2fViewParams); }
+
+extern "C" int s2f_test_views(const uint8_t* data, int64_t data_bytes, const S2fViewParams* params, int V, int max_Hp, int max_Wp,
+                              float mean0, float mean1, float mean2, float std0, float std1, float std2, int bgr_to_rgb,
+                              float pad_val, float* out, int64_t out_elems, void* stream) {
+  S2F_REQUIRE(data && params && out, S2F_EINVAL, "s2f_test_views: null pointer");
+  S2F_REQUIRE(data_bytes > 0, S2F_EINVAL, "s2f_test_views: bad byte count %lld", (long long)data_bytes);
+  S2F_REQUIRE(V > 0 && V <= 65535, S2F_EINVAL, "s2f_test_views: bad number of entries V %d (1 .. 65535)", V);
+  S2F_REQUIRE(max_Hp > 0 && max_Wp > 0 && max_Hp <= S2F_AUG_MAX_CROP && max_Wp <= S2F_AUG_MAX_CROP, S2F_EINVAL,
+              "s2f_test_views: bad largest padded size %d x %d (1 .. %d)", max_Hp, max_Wp, S2F_AUG_MAX_CROP);
+  S2F_REQUIRE(reinterpret_cast<uintptr_t>(params) % 8 == 0, S2F_EALIGN, "s2f_test_views: the parameter table is not 8-byte aligned");
+  S2F_REQUIRE(out_elems > 0, S2F_EINVAL, "s2f_test_views: bad element count %lld", (long long)out_elems);
+  S2F_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, S2F_EINVAL, "s2f_test_views: a std of 0 (pass mean 0, std 1 for no normalisation)");
+  S2F_REQUIRE(reinterpret_cast<uintptr_t>(out) % 4 == 0, S2F_EALIGN, "s2f_test_views: out is not aligned to its element size");
+  ViewConst k = {{mean0, mean1, mean2}, {std0, std1, std2}, 0.f, 0};
+  k.pad_val = pad_val;
+  k.swap = bgr_to_rgb ? 1 : 0;
+  const int64_t quads = (int64_t)max_Hp * ((max_Wp + 3) / 4);
+  const dim3 grid((unsigned)((quads + 255) / 256), (unsigned)V);
+  hipStream_t s = (hipStream_t)stream;
+  s2f_dispatch_bool(s2f_aligned16(out), [&](auto a) {
+    hipLaunchKernelGGL((test_views_kernel<a.value>), grid, dim3(256), 0, s, data, data_bytes, params, max_Hp, max_Wp, k, out, out_elems);
+  });
+  return s2f_check_launch("s2f_test_views");
 }

@@ -461,6 +461,79 @@ def aug_apply(data, params, flags, inputs, seg, mean=None, std=None, bgr_to_rgb=
     return inputs, seg
 
 
+# ------------------------------------------------------------------------------------------------ test-time views
+import numpy as _np
+
+VIEW_PARAM_BYTES = lib.s2f_view_param_bytes()
+# include/s2f.h S2fViewParams, field for field
+VIEW_PARAM_DTYPE = _np.dtype([("img_off", "<i8"), ("out_off", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("H", "<i4"), ("W", "<i4"),
+                              ("Hp", "<i4"), ("Wp", "<i4"), ("flip", "<i4"), ("reserved", "<i4")])
+assert VIEW_PARAM_DTYPE.itemsize == VIEW_PARAM_BYTES, "VIEW_PARAM_DTYPE does not mirror S2fViewParams"
+
+
+def check_view_table(table, data_bytes, out_elems):
+    """The rules of s2f_test_views on a table the host wrote, before it is launched on: every picture inside data, every block
+    inside out, 0 < H <= Hp <= AUG_MAX_CROP (W alike), out_off a multiple of 4, the blocks disjoint.  ValueError names the entry."""
+    table = _np.asarray(table)
+    if table.dtype != VIEW_PARAM_DTYPE or table.ndim != 1 or not 0 < len(table) <= 65535:
+        raise ValueError(f"table: 1 .. 65535 entries of VIEW_PARAM_DTYPE, got {table.dtype} {table.shape}")
+    spans = []
+    for v, p in enumerate(table):
+        img_off, out_off, h0, w0, H, W, Hp, Wp = (int(p[k]) for k in ("img_off", "out_off", "h0", "w0", "H", "W", "Hp", "Wp"))
+        if h0 <= 0 or w0 <= 0 or h0 * w0 >= 2 ** 31:
+            raise ValueError(f"view table entry {v}: bad source size {h0} x {w0}")
+        if img_off < 0 or img_off + 3 * h0 * w0 > data_bytes:
+            raise ValueError(f"view table entry {v}: the source picture (bytes {img_off} .. {img_off + 3 * h0 * w0}) leaves data "
+                             f"({data_bytes} bytes)")
+        if not (0 < H <= Hp <= AUG_MAX_CROP and 0 < W <= Wp <= AUG_MAX_CROP):
+            raise ValueError(f"view table entry {v}: resized {H} x {W}, padded {Hp} x {Wp}: need 0 < H <= Hp <= {AUG_MAX_CROP} and "
+                             f"0 < W <= Wp <= {AUG_MAX_CROP}")
+        if out_off % 4:
+            raise ValueError(f"view table entry {v}: out_off {out_off} is not a multiple of 4")
+        if out_off < 0 or out_off + 3 * Hp * Wp > out_elems:
+            raise ValueError(f"view table entry {v}: the block (elements {out_off} .. {out_off + 3 * Hp * Wp}) leaves out "
+                             f"({out_elems} elements)")
+        spans.append((out_off, out_off + 3 * Hp * Wp, v))
+    spans.sort()
+    for (_, end, a), (beg, _, b) in zip(spans, spans[1:]):
+        if beg < end:
+            raise ValueError(f"view table entries {a} and {b}: the blocks overlap")
+    return table
+
+
+def test_views(data, table, out, mean=None, std=None, bgr_to_rgb=False, pad_val=0.0, table_dev=None):
+    """Every view of a test iteration in ONE launch (s2f_test_views): per table entry the keep-ratio bilinear resize of a uint8 BGR
+    picture of `data` (the arithmetic of aug_apply's resize), the horizontal flip, the channel swap, (x - mean) / std and the padding
+    with pad_val, into the entry's [3, Hp, Wp] block of the packed fp32 buffer `out`; elements between the blocks are not touched.
+    table: a numpy array of VIEW_PARAM_DTYPE -- the host wrote it, so check_view_table validates EVERY entry here, before any
+    launch (ValueError); table_dev: its staged copy in device memory as uint8 (None: copied here).  There is no other route: a CPU
+    tensor raises."""
+    if not (data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()):
+        raise ValueError("data: one contiguous uint8 byte buffer")
+    if not (out.dtype == torch.float32 and out.dim() == 1 and out.is_contiguous()):
+        raise ValueError("out: one contiguous fp32 buffer")
+    table = check_view_table(table, data.numel(), out.numel())
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    m = [float(v) for v in mean] if mean is not None else [0.0] * 3
+    s = [float(v) for v in std] if std is not None else [1.0] * 3
+    if len(m) != 3 or len(s) != 3:
+        raise ValueError("mean and std have three values")
+    _aug_cuda(data, out)
+    V = len(table)
+    if table_dev is None:
+        table_dev = torch.from_numpy(_np.ascontiguousarray(table).view(_np.uint8).copy()).to(data.device)
+    _aug_cuda(table_dev)
+    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.numel() >= V * VIEW_PARAM_BYTES, \
+        f"table_dev: the V table entries of {VIEW_PARAM_BYTES} bytes as one uint8 buffer"
+    check(lib.s2f_test_views(_ptr(data), data.numel(), _ptr(table_dev), V, int(table["Hp"].max()), int(table["Wp"].max()), *m, *s,
+                             int(bool(bgr_to_rgb)), float(pad_val), _ptr(out), out.numel(), _stream()), "s2f_test_views")
+    return out
+
+
+test_views.__test__ = False          # (an op, not a test: pytest collects `test_*` names imported into a test module)
+
+
 # ------------------------------------------------------------------------------------------------ evaluation
 SEG_HIST_MAX_CLASSES = 2048          # include/s2f.h S2F_SEG_HIST_MAX_CLASSES
 _SEG_PRED_CODES = {torch.int64: 0, torch.float32: 1}

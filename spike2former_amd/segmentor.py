@@ -135,7 +135,10 @@ class EncoderDecoder(nn.Module):
 
     def preprocess(self, data, training=False):
         """data_preprocessor(data, training) -> dict(inputs, data_samples).  Without a data_preprocessor the inputs are only
-        stacked (a list of [3, H, W]) and moved to the model's device."""
+        stacked (a list of [3, H, W]) and moved to the model's device.  A batch marked `preprocessed` (what augment.TestAugment
+        returns: resized, normalised and padded on the device already) passes through untouched."""
+        if not training and isinstance(data, dict) and data.get("preprocessed"):
+            return dict(inputs=data["inputs"], data_samples=data["data_samples"])
         if self.data_preprocessor is not None:
             return self.data_preprocessor(data, training)
         if not isinstance(data, dict):

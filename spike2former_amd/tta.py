@@ -2,7 +2,9 @@
 `dict(type='SegTTAModel', module=...)` as `configs/_base_/default_runtime.py:23` configures it, or wrapped around a model.
 
 The views of one image (the reference's tta_pipeline: 6 scales x 2 flips, ade20k.py:28-43) arrive already resized by the data
-pipeline, as in mmengine.  Each view's seg logits are softmax-ed (one class: sigmoid) and summed in view order, the sum is divided
+pipeline, as in mmengine: `augment.TestAugment.from_cfg(tta_pipeline, data_preprocessor)` is that pipeline on the device (one copy
+and one launch from the decoded picture to all the views, marked `preprocessed` so that `module.preprocess` passes them through);
+views prepared elsewhere go through the module's data preprocessor as before.  Each view's seg logits are softmax-ed (one class: sigmoid) and summed in view order, the sum is divided
 once by the number of views, and the arg-max (one class: the head's threshold) is the merged prediction.  On fp32 CUDA logits
 `test_step` streams: every view's logits [K, Hp, Wp] go through ONE s2f_tta_accumulate pass -- padding crop, flip undone, bilinear
 resize to `ori_shape`, softmax, += into a [K, H, W] accumulator -- so no view's full-resolution logits are kept, and
