@@ -635,8 +635,8 @@ int s2f_aug_apply(const uint8_t* data, int64_t data_bytes, const S2fAugParams* p
  *   RESIZED picture (before the padding: the padding stays on the right)
  * Entry v, output pixel (c, y, x) of its block:
  *   y < H and x < W : resized pixel (y, flip ? W - 1 - x : x) -- the bilinear sample of the picture with half-pixel centres and no
- *     antialias, scale = in / out, rounded to nearest into uint8: s2f_aug_apply's resize step, operation for operation (the same
- *     device code), so H == h0 and W == w0 reproduces the source bytes; channel (bgr_to_rgb ? 2 - c : c) of that, (v - mean_c) /
+ *     antialias, scale = in / out, rounded to nearest into uint8: s2f_aug_apply's resize step (both kernels call ONE device
+ *     function, sample_bgr), so H == h0 and W == w0 reproduces the source bytes; channel (bgr_to_rgb ? 2 - c : c) of that, (v - mean_c) /
  *     std_c with an IEEE divide (mean 0, std 1: none).  Every step is one fp32 operation (tests/view_ref.py restates them).
  *   elsewhere (up to Hp, Wp) : pad_val itself, un-normalised, as stack_batch pads after the normalisation.
  * Every element of every entry's block is written once; elements of out between the blocks are not touched (the blocks are

@@ -33,24 +33,29 @@ import torch
 from . import ops
 
 CANDIDATES = ops.AUG_CANDIDATES
-# include/s2f.h S2fAugParams, field for field (ops.AUG_PARAM_BYTES is the library's sizeof)
-PARAM_DTYPE = np.dtype([
-    ("img_off", "<i8"), ("seg_off", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("H", "<i4"), ("W", "<i4"),
-    ("crop_y", "<i4", (CANDIDATES,)), ("crop_x", "<i4", (CANDIDATES,)), ("flip", "<i4"),
-    ("bright_on", "<i4"), ("mode", "<i4"), ("contrast_on", "<i4"), ("sat_on", "<i4"), ("hue_on", "<i4"), ("hue_delta", "<i4"),
-    ("bright_beta", "<f4"), ("contrast_alpha", "<f4"), ("sat_alpha", "<f4")])
-assert PARAM_DTYPE.itemsize == ops.AUG_PARAM_BYTES, "PARAM_DTYPE does not mirror S2fAugParams"
+PARAM_DTYPE, VIEW_PARAM_DTYPE = ops.PARAM_DTYPE, ops.VIEW_PARAM_DTYPE          # include/s2f.h S2fAugParams, S2fViewParams
 VARIATES_PER_IMAGE = 2 * CANDIDATES + 11
 
 PHOTOMETRIC_DEFAULTS = dict(brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18)
 _PIPELINE_ORDER = ("LoadImageFromFile", "LoadAnnotations", "RandomResize", "RandomCrop", "RandomFlip", "PhotoMetricDistortion",
                    "PackSegInputs")
+_TEST_ORDER = ("LoadImageFromFile", "Resize", "LoadAnnotations", "PackSegInputs")
+_TTA_ORDER = ("Resize", "RandomFlip", "LoadAnnotations", "PackSegInputs")
 
 
 def resized_size(h0, w0, scale, ratio):
     """mmcv RandomResize(scale, ratio_range, keep_ratio=True) at the drawn ratio -> (H, W): scale = (int(s0 r), int(s1 r)),
     f = min(long / max(h0, w0), short / min(h0, w0)), (int(h0 f + 0.5), int(w0 f + 0.5)) (mmcv.image.geometric.rescale_size)"""
     s = (int(scale[0] * ratio), int(scale[1] * ratio))
+    f = min(max(s) / max(h0, w0), min(s) / min(h0, w0))
+    return int(h0 * f + 0.5), int(w0 * f + 0.5)
+
+
+def scale_factor_size(h0, w0, ratio):
+    """mmcv Resize(scale_factor=ratio, keep_ratio=True) -> (H, W): first scale = (int(w0 r + 0.5), int(h0 r + 0.5)) (_scale_size),
+    then the keep-ratio rescale TO that size: f = min(max(scale) / max(h0, w0), min(scale) / min(h0, w0)), (int(h0 f + 0.5),
+    int(w0 f + 0.5)) (rescale_size).  (512 x 683 at 1.5 -> 768 x 1025: the width is rounded twice.)"""
+    s = (int(w0 * ratio + 0.5), int(h0 * ratio + 0.5))
     f = min(max(s) / max(h0, w0), min(s) / min(h0, w0))
     return int(h0 * f + 0.5), int(w0 * f + 0.5)
 
@@ -67,13 +72,106 @@ def _default_rank():
     return int(os.environ.get("RANK", "0"))
 
 
-def _only(cfg, allowed, what):
+# ---------------------------------------------------------------------------------------------------- reading a configuration
+def _only(cfg, allowed, what, who):
     extra = sorted(set(cfg) - set(allowed) - {"type"})
     if extra:
-        raise NotImplementedError(f"TrainAugment: {what} option(s) {extra} are not implemented on the device")
+        raise NotImplementedError(f"{who}: {what} option(s) {extra} are not implemented on the device")
 
 
-class TrainAugment:
+def _in_order(items, order, who):
+    """items: (kind, payload) pairs of a pipeline -> the same pairs, each after the check that its kind is one of `order` and
+    stands behind its predecessor's"""
+    last = None
+    for kind, payload in items:
+        if kind not in order:
+            raise NotImplementedError(f"{who}: transform {kind!r} is not implemented on the device")
+        if last is not None and order.index(kind) <= order.index(last):
+            raise NotImplementedError(f"{who}: {kind} after {last}: the device applies the transforms in the order "
+                                      f"{' -> '.join(order)}")
+        last = kind
+        yield kind, payload
+
+
+def _preprocessor(cfg, who):
+    """the model's SegDataPreProcessor dictionary -> (mean, std, bgr_to_rgb and pad_val as both classes take them, the checked
+    dictionary for what one side reads: `size`, `size_divisor`, `seg_pad_val` the training branch, `test_cfg` the test branch)"""
+    p = dict(cfg)
+    if p.pop("type", "SegDataPreProcessor") != "SegDataPreProcessor":
+        raise NotImplementedError(f"{who}: the data preprocessor is a SegDataPreProcessor")
+    _only(p, ("mean", "std", "bgr_to_rgb", "rgb_to_bgr", "pad_val", "seg_pad_val", "size", "test_cfg", "batch_augments",
+              "size_divisor"), "SegDataPreProcessor", who)
+    if p.get("batch_augments") is not None:
+        raise NotImplementedError(f"{who}: SegDataPreProcessor batch_augments are not implemented on the device")
+    if p.get("bgr_to_rgb") and p.get("rgb_to_bgr"):
+        raise ValueError("`bgr2rgb` and `rgb2bgr` cannot be set to True at the same time")
+    return dict(mean=p.get("mean"), std=p.get("std"), bgr_to_rgb=bool(p.get("bgr_to_rgb") or p.get("rgb_to_bgr")),
+                pad_val=p.get("pad_val", 0)), p
+
+
+# ---------------------------------------------------------------------------------------------------- staging
+class _Staged:
+    """What TrainAugment and TestAugment share: SegDataPreProcessor's constants, the checks of the decoded pictures, and the pinned
+    staging buffer with its twin in device memory -- the parameter table first (its room is a multiple of 16 bytes: the packed
+    bytes behind it start aligned), then batch_size pictures of max_source_pixels pixels with their annotations (4 bytes per
+    pixel) -- filled and sent by ONE host-to-device copy (`_copy_in`)."""
+    __test__ = False          # (pytest: a class named Test* imported into a test module is not a test)
+
+    def __init__(self, entry_dtype, entries_per_picture, mean, std, bgr_to_rgb, pad_val, batch_size, max_source_pixels, device):
+        self.mean, self.std = (None, None) if mean is None and std is None else ops._mean_std(mean, std)
+        self.bgr_to_rgb, self.pad_val = bool(bgr_to_rgb), float(pad_val)
+        self.batch_size, self.max_source_pixels = int(batch_size), int(max_source_pixels)
+        if self.batch_size <= 0 or self.max_source_pixels <= 0:
+            raise ValueError("batch_size and max_source_pixels are positive")
+        self.device = torch.device(device)
+        self._table_cap = (entries_per_picture * self.batch_size * entry_dtype.itemsize + 15) // 16 * 16
+        self._data_cap = self.batch_size * self.max_source_pixels * 4
+        self._pin = self._dev = self._copied = None
+
+    def _allocate(self):
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} runs on the GPU only (HIP kernels): there is no host route")
+        n = self._table_cap + self._data_cap
+        self._pin = torch.empty(n, dtype=torch.uint8).pin_memory()
+        self._dev = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self._copied = torch.cuda.Event()
+
+    def _pictures(self, images, segs, one_size=False):
+        """-> (images, segs) as contiguous numpy arrays: 1 .. batch_size uint8 [h0, w0, 3] pictures of at most max_source_pixels
+        pixels (one_size: all of the first one's size), and for each, unless segs is None, a uint8 [h0, w0] annotation"""
+        B = len(images)
+        if not 0 < B <= self.batch_size or (segs is not None and len(segs) != B):
+            raise ValueError(f"{B} pictures, {'no' if segs is None else len(segs)} annotations for a batch size of {self.batch_size}")
+        images = [np.ascontiguousarray(np.asarray(i)) for i in images]
+        segs = None if segs is None else [np.ascontiguousarray(np.asarray(s)) for s in segs]
+        for k, i in enumerate(images):
+            if i.dtype != np.uint8 or i.ndim != 3 or i.shape[2] != 3 or (one_size and i.shape != images[0].shape):
+                raise ValueError("pictures are uint8 [h0, w0, 3]" + (" of ONE size (the reference's test branch asserts equal sizes)"
+                                                                     if one_size else ""))
+            if segs is not None and (segs[k].dtype != np.uint8 or segs[k].shape != i.shape[:2]):
+                raise ValueError("annotations are uint8 [h0, w0] of their picture's size")
+            h0, w0 = i.shape[:2]
+            if h0 * w0 > self.max_source_pixels or h0 * w0 == 0:
+                raise ValueError(f"a {h0} x {w0} picture does not fit max_source_pixels = {self.max_source_pixels}")
+        return images, segs
+
+    def _copy_in(self, table, pieces):
+        """The table and the pieces [(byte offset behind the table's room, array)] into the pinned buffer, then ONE host-to-device
+        copy of what they span, queued on the current stream."""
+        if self._pin is None:
+            self._allocate()
+        self._copied.synchronize()          # the previous copy has left the staging buffer (a copy, not the step, is waited for)
+        pin = self._pin.numpy()
+        pin[:table.nbytes] = table.view(np.uint8)
+        n = d0 = self._table_cap
+        for off, a in pieces:
+            pin[d0 + off:d0 + off + a.size] = a.reshape(-1)
+            n = max(n, d0 + off + a.size)
+        self._dev[:n].copy_(self._pin[:n], non_blocking=True)
+        self._copied.record()
+
+
+class TrainAugment(_Staged):
     def __init__(self, scale=(2048, 512), ratio_range=(0.5, 2.0), crop_size=(512, 512), cat_max_ratio=0.75, flip_prob=0.5,
                  photometric=True, reduce_zero_label=False, ignore_index=255, mean=None, std=None, bgr_to_rgb=False, pad_val=0,
                  seg_pad_val=255, batch_size=2, max_source_pixels=2048 * 1024, device="cuda", seed=0, rank=None):
@@ -93,23 +191,12 @@ class TrainAugment:
             photometric = {}
         self.photometric = None if photometric in (None, False) else {**PHOTOMETRIC_DEFAULTS, **photometric}
         if self.photometric is not None:
-            _only(self.photometric, PHOTOMETRIC_DEFAULTS, "PhotoMetricDistortion")
-        self.reduce_zero_label, self.ignore_index = bool(reduce_zero_label), int(ignore_index)
-        if (mean is None) != (std is None):
-            raise ValueError("mean and std go together")
-        self.mean = None if mean is None else [float(v) for v in mean]
-        self.std = None if std is None else [float(v) for v in std]
-        self.bgr_to_rgb, self.pad_val, self.seg_pad_val = bool(bgr_to_rgb), float(pad_val), int(seg_pad_val)
-        self.batch_size, self.max_source_pixels = int(batch_size), int(max_source_pixels)
-        if self.batch_size <= 0 or self.max_source_pixels <= 0:
-            raise ValueError("batch_size and max_source_pixels are positive")
-        self.device = torch.device(device)
+            _only(self.photometric, PHOTOMETRIC_DEFAULTS, "PhotoMetricDistortion", "TrainAugment")
+        self.reduce_zero_label, self.ignore_index, self.seg_pad_val = bool(reduce_zero_label), int(ignore_index), int(seg_pad_val)
+        super().__init__(PARAM_DTYPE, 1, mean, std, bgr_to_rgb, pad_val, batch_size, max_source_pixels, device)
         self.seed, self.rank = int(seed), int(_default_rank() if rank is None else rank)
         self.rng = np.random.default_rng(np.random.SeedSequence([self.seed, self.rank]))
-        # the table first (its size is a multiple of 16: the packed bytes behind it start aligned), then the pixels
-        self._table_cap = (self.batch_size * PARAM_DTYPE.itemsize + 15) // 16 * 16
-        self._data_cap = self.batch_size * self.max_source_pixels * 4
-        self._pin = self._dev = self._flags = self._inputs = self._seg = self._copied = None
+        self._flags = self._inputs = self._seg = None
         self._staged = 0
 
     # ------------------------------------------------------------------------------------------------ configuration
@@ -119,57 +206,42 @@ class TrainAugment:
         RandomCrop, RandomFlip, PhotoMetricDistortion, PackSegInputs, in this order; LoadImageFromFile only marks where the caller's
         decoded pictures enter); data_preprocessor: the model's SegDataPreProcessor dictionary.  Any other transform, order or option
         raises NotImplementedError.  kwargs: batch_size, max_source_pixels, device, seed, rank."""
+        who = "TrainAugment"
         a = dict(scale=None, ratio_range=None, cat_max_ratio=1.0, flip_prob=0.0, photometric=None)
-        seen = []
-        for t in train_pipeline:
-            kind = t.get("type")
-            if kind not in _PIPELINE_ORDER:
-                raise NotImplementedError(f"TrainAugment: transform {kind!r} is not implemented on the device")
-            if seen and _PIPELINE_ORDER.index(kind) <= _PIPELINE_ORDER.index(seen[-1]):
-                raise NotImplementedError(f"TrainAugment: {kind} after {seen[-1]}: the kernels apply the transforms in the order "
-                                          f"{' -> '.join(_PIPELINE_ORDER)}")
-            seen.append(kind)
+        for kind, t in _in_order(((t.get("type"), t) for t in train_pipeline), _PIPELINE_ORDER, who):
             if kind in ("LoadImageFromFile", "PackSegInputs"):
-                _only(t, (), kind)
+                _only(t, (), kind, who)
             elif kind == "LoadAnnotations":
-                _only(t, ("reduce_zero_label",), kind)
+                _only(t, ("reduce_zero_label",), kind, who)
                 a["reduce_zero_label"] = bool(t.get("reduce_zero_label", False))
             elif kind == "RandomResize":
-                _only(t, ("scale", "ratio_range", "keep_ratio"), kind)
+                _only(t, ("scale", "ratio_range", "keep_ratio"), kind, who)
                 if not t.get("keep_ratio", False) or not isinstance(t.get("scale"), (tuple, list)) or len(t["scale"]) != 2 \
                         or not all(isinstance(v, int) for v in t["scale"]):
                     raise NotImplementedError("TrainAugment: RandomResize needs keep_ratio=True and one (long, short) scale")
                 a["scale"], a["ratio_range"] = tuple(t["scale"]), t.get("ratio_range")
             elif kind == "RandomCrop":
-                _only(t, ("crop_size", "cat_max_ratio", "ignore_index"), kind)
+                _only(t, ("crop_size", "cat_max_ratio", "ignore_index"), kind, who)
                 a["crop_size"] = t["crop_size"]
                 a["cat_max_ratio"], a["ignore_index"] = t.get("cat_max_ratio", 1.0), t.get("ignore_index", 255)
             elif kind == "RandomFlip":
-                _only(t, ("prob", "direction"), kind)
+                _only(t, ("prob", "direction"), kind, who)
                 if t.get("direction", "horizontal") != "horizontal" or isinstance(t.get("prob"), (list, tuple)):
                     raise NotImplementedError("TrainAugment: RandomFlip is implemented for one probability, horizontal")
                 a["flip_prob"] = t.get("prob") or 0.0
             elif kind == "PhotoMetricDistortion":
-                _only(t, PHOTOMETRIC_DEFAULTS, kind)
+                _only(t, PHOTOMETRIC_DEFAULTS, kind, who)
                 a["photometric"] = {k: v for k, v in t.items() if k != "type"}
-        if "RandomCrop" not in seen:
+        if "crop_size" not in a:
             raise NotImplementedError("TrainAugment: a train_pipeline without RandomCrop has no fixed output size")
-        p = dict(data_preprocessor)
-        if p.pop("type", "SegDataPreProcessor") != "SegDataPreProcessor":
-            raise NotImplementedError("TrainAugment: the data preprocessor is a SegDataPreProcessor")
-        _only(p, ("mean", "std", "bgr_to_rgb", "rgb_to_bgr", "pad_val", "seg_pad_val", "size", "test_cfg", "batch_augments",
-                  "size_divisor"), "SegDataPreProcessor")
-        if p.get("batch_augments") is not None or p.get("size_divisor") is not None:
-            raise NotImplementedError("TrainAugment: SegDataPreProcessor batch_augments / size_divisor are not implemented")
+        common, p = _preprocessor(data_preprocessor, who)
+        if p.get("size_divisor") is not None:
+            raise NotImplementedError("TrainAugment: SegDataPreProcessor size_divisor is not implemented on the device")
         crop = a["crop_size"]
         crop = (crop, crop) if isinstance(crop, int) else tuple(crop)
         if p.get("size") is not None and tuple(p["size"]) != crop:
             raise NotImplementedError(f"TrainAugment: SegDataPreProcessor size {tuple(p['size'])} is not the crop size {crop}")
-        if p.get("bgr_to_rgb") and p.get("rgb_to_bgr"):
-            raise ValueError("`bgr2rgb` and `rgb2bgr` cannot be set to True at the same time")
-        a.update(mean=p.get("mean"), std=p.get("std"), bgr_to_rgb=bool(p.get("bgr_to_rgb") or p.get("rgb_to_bgr")),
-                 pad_val=p.get("pad_val", 0), seg_pad_val=p.get("seg_pad_val", 255))
-        return cls(**a, **kwargs)
+        return cls(**a, **common, seg_pad_val=p.get("seg_pad_val", 255), **kwargs)
 
     # ------------------------------------------------------------------------------------------------ random numbers
     def draw(self, shapes):
@@ -205,53 +277,30 @@ class TrainAugment:
 
     # ------------------------------------------------------------------------------------------------ device side
     def _allocate(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("TrainAugment runs on the GPU only (HIP kernels): there is no host route")
-        n = self._table_cap + self._data_cap
-        self._pin = torch.empty(n, dtype=torch.uint8).pin_memory()
-        self._dev = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        super()._allocate()
         self._flags = torch.zeros(self.batch_size, CANDIDATES, dtype=torch.int32, device=self.device)
-        self._copied = torch.cuda.Event()
 
     def stage(self, images, segs, params=None):
         """Packs the pictures, the annotations and the table into the pinned staging buffer and queues ONE host-to-device copy on the
         current stream.  images: uint8 [h0, w0, 3] BGR arrays (numpy or CPU tensors); segs: uint8 [h0, w0].  -> params as staged."""
+        images, segs = self._pictures(images, segs)
         B = len(images)
-        if not 0 < B <= self.batch_size or len(segs) != B:
-            raise ValueError(f"{B} pictures, {len(segs)} annotations for a batch size of {self.batch_size}")
-        images = [np.ascontiguousarray(np.asarray(i)) for i in images]
-        segs = [np.ascontiguousarray(np.asarray(s)) for s in segs]
         params = self.draw([i.shape[:2] for i in images]) if params is None else np.array(params, dtype=PARAM_DTYPE)
         if params.shape != (B,):
             raise ValueError(f"{params.shape} parameter entries for {B} pictures")
         Hc, Wc = self.crop_size
-        off = 0
+        off, pieces = 0, []
         for i, s, p in zip(images, segs, params):
-            if i.dtype != np.uint8 or s.dtype != np.uint8 or i.ndim != 3 or i.shape[2] != 3 or s.shape != i.shape[:2]:
-                raise ValueError("pictures are uint8 [h0, w0, 3], annotations uint8 [h0, w0] of the same size")
             h0, w0 = s.shape
-            if h0 * w0 > self.max_source_pixels or h0 * w0 == 0:
-                raise ValueError(f"a {h0} x {w0} picture does not fit max_source_pixels = {self.max_source_pixels}")
             if (p["h0"], p["w0"]) != (h0, w0) or p["H"] <= 0 or p["W"] <= 0:
                 raise ValueError(f"parameter entry for a {p['h0']} x {p['w0']} picture resized to {p['H']} x {p['W']}, picture {h0} x {w0}")
             my, mx = max(int(p["H"]) - Hc, 0), max(int(p["W"]) - Wc, 0)
             if p["crop_y"].min() < 0 or p["crop_y"].max() > my or p["crop_x"].min() < 0 or p["crop_x"].max() > mx:
                 raise ValueError("a candidate crop origin lies outside [0, margin]")
             p["img_off"], p["seg_off"] = off, off + 3 * h0 * w0
+            pieces += [(off, i), (off + 3 * h0 * w0, s)]
             off += 4 * h0 * w0
-        if self._pin is None:
-            self._allocate()
-        self._copied.synchronize()          # the previous copy has left the staging buffer (a copy, not the step, is waited for)
-        pin = self._pin.numpy()
-        pin[:params.nbytes] = params.view(np.uint8)
-        d0 = self._table_cap
-        for i, s, p in zip(images, segs, params):
-            a, b = d0 + int(p["img_off"]), d0 + int(p["seg_off"])
-            pin[a:b] = i.reshape(-1)
-            pin[b:b + s.size] = s.reshape(-1)
-        n = d0 + off
-        self._dev[:n].copy_(self._pin[:n], non_blocking=True)
-        self._copied.record()
+        self._copy_in(params, pieces)
         self._staged = B
         return params
 
@@ -285,28 +334,8 @@ class TrainAugment:
 
 
 # ---------------------------------------------------------------------------------------------------- the test pipeline
-VIEW_PARAM_DTYPE = ops.VIEW_PARAM_DTYPE          # include/s2f.h S2fViewParams (ops.VIEW_PARAM_BYTES is the library's sizeof)
-_TEST_ORDER = ("LoadImageFromFile", "Resize", "LoadAnnotations", "PackSegInputs")
-_TTA_ORDER = ("Resize", "RandomFlip", "LoadAnnotations", "PackSegInputs")
-
-
-def _only_test(cfg, allowed, what):
-    extra = sorted(set(cfg) - set(allowed) - {"type"})
-    if extra:
-        raise NotImplementedError(f"TestAugment: {what} option(s) {extra} are not implemented on the device")
-
-
-def scale_factor_size(h0, w0, ratio):
-    """mmcv Resize(scale_factor=ratio, keep_ratio=True) -> (H, W): first scale = (int(w0 r + 0.5), int(h0 r + 0.5)) (_scale_size),
-    then the keep-ratio rescale TO that size: f = min(max(scale) / max(h0, w0), min(scale) / min(h0, w0)), (int(h0 f + 0.5),
-    int(w0 f + 0.5)) (rescale_size).  (512 x 683 at 1.5 -> 768 x 1025: the width is rounded twice.)"""
-    s = (int(w0 * ratio + 0.5), int(h0 * ratio + 0.5))
-    f = min(max(s) / max(h0, w0), min(s) / min(h0, w0))
-    return int(h0 * f + 0.5), int(w0 * f + 0.5)
-
-
 def _resize_args(t, what):
-    _only_test(t, ("scale", "scale_factor", "keep_ratio"), what)
+    _only(t, ("scale", "scale_factor", "keep_ratio"), what, "TestAugment")
     if not t.get("keep_ratio", False):
         raise NotImplementedError(f"TestAugment: {what} with keep_ratio=False is not implemented on the device")
     if ("scale" in t) == ("scale_factor" in t):
@@ -322,7 +351,7 @@ def _resize_args(t, what):
     return None, float(r)
 
 
-class TestAugment:
+class TestAugment(_Staged):
     """The shipped configs' `test_pipeline` / `tta_pipeline` -- Resize(keep_ratio=True) [x RandomFlip(prob 0 | 1)] -- and the test
     branch of `SegDataPreProcessor` (channel swap, (x - mean) / std, padding by test_cfg's size / size_divisor) as ONE H2D copy and
     ONE HIP launch (s2f_test_views, csrc/augment.hip) from the decoded uint8 pictures of an iteration to every view of it: the
@@ -343,7 +372,6 @@ class TestAugment:
 
     What a call returns -- the views and the annotations -- lives in persistent device buffers of this object and is valid until
     the next call."""
-    __test__ = False          # (pytest: a class named Test* imported into a test module is not a test)
 
     def __init__(self, scale=(2048, 512), scale_factors=None, flips=(False,), reduce_zero_label=False, mean=None, std=None,
                  bgr_to_rgb=False, pad_val=0, size=None, size_divisor=None, batch_size=1, max_source_pixels=2048 * 1024, device="cuda",
@@ -367,24 +395,12 @@ class TestAugment:
         if not self.tta and self.n_views != 1:
             raise ValueError(f"{self.n_views} views need the TTA form")
         self.reduce_zero_label = bool(reduce_zero_label)
-        if (mean is None) != (std is None):
-            raise ValueError("mean and std go together")
-        self.mean = None if mean is None else [float(v) for v in mean]
-        self.std = None if std is None else [float(v) for v in std]
-        self.bgr_to_rgb, self.pad_val = bool(bgr_to_rgb), float(pad_val)
         if size is not None and size_divisor is not None:
             raise ValueError("only one of size and size_divisor should be valid")
         self.size = None if size is None else (int(size[0]), int(size[1]))
         self.size_divisor = None if size_divisor is None else int(size_divisor)
-        self.batch_size, self.max_source_pixels = int(batch_size), int(max_source_pixels)
-        if self.batch_size <= 0 or self.max_source_pixels <= 0:
-            raise ValueError("batch_size and max_source_pixels are positive")
-        self.device = torch.device(device)
-        # the table first (its size is a multiple of 16: the packed bytes behind it start aligned), then the pixels
-        self._table_cap = (self.n_views * self.batch_size * VIEW_PARAM_DTYPE.itemsize + 15) // 16 * 16
-        self._data_cap = self.batch_size * self.max_source_pixels * 4
-        self._pin = self._dev = self._out = self._copied = None
-        self._staged = None
+        super().__init__(VIEW_PARAM_DTYPE, self.n_views, mean, std, bgr_to_rgb, pad_val, batch_size, max_source_pixels, device)
+        self._out = self._staged = None
 
     # ------------------------------------------------------------------------------------------------ configuration
     @classmethod
@@ -396,32 +412,28 @@ class TestAugment:
         SegDataPreProcessor dictionary (mean, std, bgr_to_rgb, pad_val and test_cfg's size / size_divisor are used).  Any other
         transform, order or option raises NotImplementedError.  reduce_zero_label: what a LoadAnnotations without the option takes
         (in mmseg: the data set's).  kwargs: batch_size, max_source_pixels, device."""
+        who = "TestAugment"
         kinds = [t.get("type") for t in pipeline]
-        a = dict(scale=None, scale_factors=None, flips=(False,), reduce_zero_label=bool(reduce_zero_label))
+        a = dict(scale=None, scale_factors=None, flips=(False,), reduce_zero_label=bool(reduce_zero_label), tta="TestTimeAug" in kinds)
 
         def annotations(t):
-            _only_test(t, ("reduce_zero_label",), "LoadAnnotations")
+            _only(t, ("reduce_zero_label",), "LoadAnnotations", who)
             a["reduce_zero_label"] = bool(t.get("reduce_zero_label", reduce_zero_label))
 
-        if "TestTimeAug" in kinds:
+        def group_kind(group):
+            names = sorted({t.get("type") for t in group})
+            if len(names) != 1:
+                raise NotImplementedError(f"TestAugment: one kind of transform per TestTimeAug list, got {names}")
+            return names[0]
+
+        if a["tta"]:
             if kinds != ["LoadImageFromFile", "TestTimeAug"]:
                 raise NotImplementedError(f"TestAugment: a tta_pipeline is LoadImageFromFile, TestTimeAug; got {kinds}")
-            _only_test(pipeline[0], (), "LoadImageFromFile")
-            _only_test(pipeline[1], ("transforms",), "TestTimeAug")
-            seen = []
-            for group in pipeline[1]["transforms"]:
-                group = [group] if isinstance(group, dict) else list(group)
-                names = sorted({t.get("type") for t in group})
-                for kind in names:
-                    if kind not in _TTA_ORDER:
-                        raise NotImplementedError(f"TestAugment: transform {kind!r} is not implemented on the device")
-                if len(names) != 1:
-                    raise NotImplementedError(f"TestAugment: one kind of transform per TestTimeAug list, got {names}")
-                kind = names[0]
-                if seen and _TTA_ORDER.index(kind) <= _TTA_ORDER.index(seen[-1]):
-                    raise NotImplementedError(f"TestAugment: {kind} after {seen[-1]}: the kernel applies the transforms in the order "
-                                              f"{' -> '.join(_TTA_ORDER)}")
-                seen.append(kind)
+            _only(pipeline[0], (), "LoadImageFromFile", who)
+            _only(pipeline[1], ("transforms",), "TestTimeAug", who)
+            groups = [[g] if isinstance(g, dict) else list(g) for g in pipeline[1]["transforms"]]
+            kind = None
+            for kind, group in _in_order(((group_kind(g), g) for g in groups), _TTA_ORDER, who):
                 if kind == "Resize":
                     args = [_resize_args(t, "Resize") for t in group]
                     if any(s is not None for s, _ in args):
@@ -430,7 +442,7 @@ class TestAugment:
                 elif kind == "RandomFlip":
                     flips = []
                     for t in group:
-                        _only_test(t, ("prob", "direction"), "RandomFlip")
+                        _only(t, ("prob", "direction"), "RandomFlip", who)
                         if t.get("direction", "horizontal") != "horizontal":
                             raise NotImplementedError(f"TestAugment: RandomFlip direction={t['direction']!r}: only 'horizontal' is "
                                                       f"implemented on the device")
@@ -439,48 +451,27 @@ class TestAugment:
                             raise NotImplementedError(f"TestAugment: RandomFlip prob={prob!r}: a test-time flip is certain (prob 0 or 1)")
                         flips.append(float(prob) == 1.0)
                     a["flips"] = tuple(flips)
-                elif kind == "LoadAnnotations":
-                    if len(group) != 1:
-                        raise NotImplementedError("TestAugment: one LoadAnnotations")
-                    annotations(group[0])
                 elif len(group) != 1:
-                    raise NotImplementedError("TestAugment: one PackSegInputs")
+                    raise NotImplementedError(f"TestAugment: one {kind}")
+                elif kind == "LoadAnnotations":
+                    annotations(group[0])
                 else:
-                    _only_test(group[0], (), "PackSegInputs")
-            if not seen or seen[-1] != "PackSegInputs":
+                    _only(group[0], (), "PackSegInputs", who)
+            if kind != "PackSegInputs":
                 raise NotImplementedError("TestAugment: TestTimeAug's transforms end in [PackSegInputs]")
-            a["tta"] = True
         else:
-            seen = []
-            for t, kind in zip(pipeline, kinds):
-                if kind not in _TEST_ORDER:
-                    raise NotImplementedError(f"TestAugment: transform {kind!r} is not implemented on the device")
-                if seen and _TEST_ORDER.index(kind) <= _TEST_ORDER.index(seen[-1]):
-                    raise NotImplementedError(f"TestAugment: {kind} after {seen[-1]}: the kernel applies the transforms in the order "
-                                              f"{' -> '.join(_TEST_ORDER)}")
-                seen.append(kind)
+            for kind, t in _in_order(zip(kinds, pipeline), _TEST_ORDER, who):
                 if kind in ("LoadImageFromFile", "PackSegInputs"):
-                    _only_test(t, (), kind)
+                    _only(t, (), kind, who)
                 elif kind == "LoadAnnotations":
                     annotations(t)
                 else:
                     scale, ratio = _resize_args(t, "Resize")
                     a["scale"], a["scale_factors"] = scale, None if ratio is None else (ratio,)
-            a["tta"] = False
-        p = dict(data_preprocessor)
-        if p.pop("type", "SegDataPreProcessor") != "SegDataPreProcessor":
-            raise NotImplementedError("TestAugment: the data preprocessor is a SegDataPreProcessor")
-        _only_test(p, ("mean", "std", "bgr_to_rgb", "rgb_to_bgr", "pad_val", "seg_pad_val", "size", "test_cfg", "batch_augments",
-                       "size_divisor"), "SegDataPreProcessor")
-        if p.get("batch_augments") is not None:
-            raise NotImplementedError("TestAugment: SegDataPreProcessor batch_augments are not implemented on the device")
-        if p.get("bgr_to_rgb") and p.get("rgb_to_bgr"):
-            raise ValueError("`bgr2rgb` and `rgb2bgr` cannot be set to True at the same time")
+        common, p = _preprocessor(data_preprocessor, who)
         test_cfg = dict(p.get("test_cfg") or {})          # (size / size_divisor OUTSIDE test_cfg are the training branch's)
-        _only_test(test_cfg, ("size", "size_divisor"), "SegDataPreProcessor test_cfg")
-        a.update(mean=p.get("mean"), std=p.get("std"), bgr_to_rgb=bool(p.get("bgr_to_rgb") or p.get("rgb_to_bgr")),
-                 pad_val=p.get("pad_val", 0), size=test_cfg.get("size"), size_divisor=test_cfg.get("size_divisor"))
-        return cls(**a, **kwargs)
+        _only(test_cfg, ("size", "size_divisor"), "SegDataPreProcessor test_cfg", who)
+        return cls(**a, **common, size=test_cfg.get("size"), size_divisor=test_cfg.get("size_divisor"), **kwargs)
 
     # ------------------------------------------------------------------------------------------------ geometry
     def padded_size(self, H, W):
@@ -523,55 +514,25 @@ class TestAugment:
         return t, off
 
     # ------------------------------------------------------------------------------------------------ device side
-    def _allocate(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("TestAugment runs on the GPU only (HIP kernels): there is no host route")
-        n = self._table_cap + self._data_cap
-        self._pin = torch.empty(n, dtype=torch.uint8).pin_memory()
-        self._dev = torch.zeros(n, dtype=torch.uint8, device=self.device)
-        self._copied = torch.cuda.Event()
-
     def stage(self, images, segs=None, img_paths=None, views=None):
         """Packs the table, the pictures and (if given) the raw annotations into the pinned staging buffer and queues ONE
         host-to-device copy on the current stream; grows the packed output buffer if this iteration's views need more than any
         before.  images: B <= batch_size uint8 [h0, w0, 3] BGR arrays of ONE size (numpy or CPU tensors); segs: uint8 [h0, w0];
         views: [(H, W, Hp, Wp, flip)] instead of `view_sizes` (any sizes: what the tests of the kernel use).  -> the table."""
+        images, segs = self._pictures(images, segs, one_size=True)
         B = len(images)
-        if not 0 < B <= self.batch_size or (segs is not None and len(segs) != B) or (img_paths is not None and len(img_paths) != B):
-            raise ValueError(f"{B} pictures for a batch size of {self.batch_size} (with as many annotations and paths, if any)")
-        images = [np.ascontiguousarray(np.asarray(i)) for i in images]
-        segs = None if segs is None else [np.ascontiguousarray(np.asarray(s)) for s in segs]
-        shape = images[0].shape
-        for k, i in enumerate(images):
-            if i.dtype != np.uint8 or i.ndim != 3 or i.shape[2] != 3 or i.shape != shape:
-                raise ValueError("pictures are uint8 [h0, w0, 3] of ONE size (the reference's test branch asserts equal sizes)")
-            if segs is not None and (segs[k].dtype != np.uint8 or segs[k].shape != shape[:2]):
-                raise ValueError("annotations are uint8 [h0, w0] of the pictures' size")
-        h0, w0 = shape[:2]
-        if h0 * w0 > self.max_source_pixels or h0 * w0 == 0:
-            raise ValueError(f"a {h0} x {w0} picture does not fit max_source_pixels = {self.max_source_pixels}")
+        if img_paths is not None and len(img_paths) != B:
+            raise ValueError(f"{len(img_paths)} paths for {B} pictures")
+        h0, w0 = images[0].shape[:2]
         if views is not None and len(views) > self.n_views:
             raise ValueError(f"{len(views)} views, the staging buffer holds the table of {self.n_views}")
         table, out_elems = self.table(h0, w0, B, views)
         n_img = 3 * h0 * w0 * B
         ops.check_view_table(table, n_img, out_elems)
-        if self._pin is None:
-            self._allocate()
+        self._copy_in(table, [(3 * h0 * w0 * b, i) for b, i in enumerate(images)]
+                      + [(n_img + h0 * w0 * b, s) for b, s in enumerate(segs or ())])
         if self._out is None or self._out.numel() < out_elems:          # a new high-water mark (not inside a graph capture)
             self._out = torch.empty(out_elems, dtype=torch.float32, device=self.device)
-        self._copied.synchronize()          # the previous copy has left the staging buffer
-        pin = self._pin.numpy()
-        pin[:table.nbytes] = table.view(np.uint8)
-        d0 = self._table_cap
-        for b, i in enumerate(images):
-            pin[d0 + 3 * h0 * w0 * b:d0 + 3 * h0 * w0 * (b + 1)] = i.reshape(-1)
-        n = d0 + n_img
-        if segs is not None:
-            for b, s in enumerate(segs):
-                pin[n + h0 * w0 * b:n + h0 * w0 * (b + 1)] = s.reshape(-1)
-            n += h0 * w0 * B
-        self._dev[:n].copy_(self._pin[:n], non_blocking=True)
-        self._copied.record()
         self._staged = dict(table=table, B=B, shape=(h0, w0), n_img=n_img, segs=segs is not None, out_elems=out_elems,
                             paths=list(img_paths) if img_paths is not None else [None] * B, tta=self.tta or views is not None)
         return table

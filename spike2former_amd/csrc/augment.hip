@@ -18,8 +18,9 @@
 // the byte buffer is treated as empty (all padding, every flag 0), origins are clamped into [0, margin] and tap indices into the
 // source, so no load leaves `data` whatever the table holds; stores are bounded by the grid alone.
 //
-// The test pipeline's counterpart (include/s2f.h "test-time views") lives here as well, so that it shares axis_taps and the
-// interpolation's order of operations with s2f_aug_apply -- a picture is resized at test time by the arithmetic it was trained on:
+// The test pipeline's counterpart (include/s2f.h "test-time views") lives here as well and CALLS what s2f_aug_apply calls -- axis_taps,
+// sample_bgr (the interpolation and its rounding), normalise (channel swap, (x - mean) / std), picture_ok and, on the host, prepare
+// (the argument checks and the PreConst both kernels take) -- so a picture is resized at test time by the code it was trained on:
 //
 //   s2f_test_views     : ONE launch for every (view, image) of a test / TTA iteration: keep-ratio Resize, horizontal flip,
 //                        channel swap, normalisation and the padding of SegDataPreProcessor's test branch, into blocks of different
@@ -34,7 +35,8 @@ namespace {
 constexpr int kStrip = 256, kRowsPerPass = 4, kRowsPerWg = 8;
 constexpr int kStatThreads = 1024;
 constexpr int kParamWords = (int)(sizeof(S2fAugParams) / 4);
-static_assert(sizeof(S2fAugParams) == 160 && sizeof(S2fAugParams) % 8 == 0, "augment.py PARAM_DTYPE mirrors this layout");
+static_assert(sizeof(S2fAugParams) == 160 && sizeof(S2fAugParams) % 8 == 0, "ops/misc.py PARAM_DTYPE mirrors this layout");
+static_assert(sizeof(S2fViewParams) == 48 && sizeof(S2fViewParams) % 8 == 0, "ops/misc.py VIEW_PARAM_DTYPE mirrors this layout");
 
 // resize.hip's axis_taps for align_corners = False: scale = in / out, src = max(scale * (o + 0.5) - 0.5, 0)
 __device__ __forceinline__ void axis_taps(float scale, int in, int o, int& i0, int& i1, float& l1) {
@@ -54,11 +56,39 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // LoadAnnotations(reduce_zero_label=True) on a raw u8 label: the convention of segmetric.hip's seg_key
 __device__ __forceinline__ int reduce_label(int l, int rzl) { return rzl ? ((l == 0 || l == 255) ? 255 : l - 1) : l; }
 
-// the table entry's picture fits `data`: -> h0 * w0 < 2^31, so every pixel index below fits an int
-__device__ __forceinline__ bool entry_ok(const S2fAugParams& p, int64_t data_bytes) {
-  if (p.h0 <= 0 || p.w0 <= 0 || p.H <= 0 || p.W <= 0 || p.img_off < 0 || p.seg_off < 0) return false;
-  const int64_t px = (int64_t)p.h0 * p.w0;
-  return px < ((int64_t)1 << 31) && p.img_off <= data_bytes - 3 * px && p.seg_off <= data_bytes - px;
+// an h0 x w0 picture resized to H x W fits `data` with 3 bytes per pixel at img_off -- and, where seg_off is given, its annotation
+// with 1 byte per pixel there: -> h0 * w0 < 2^31, so every pixel index below fits an int.  (References into the table entry: a
+// field is loaded when its test is reached.  docs/EXPERIMENTS.md has the timings of this form and of two others.)
+__device__ __forceinline__ bool picture_ok(const int& h0, const int& w0, const int& H, const int& W, const int64_t& img_off,
+                                           const int64_t* seg_off, int64_t data_bytes) {
+  if (h0 <= 0 || w0 <= 0 || H <= 0 || W <= 0 || img_off < 0 || (seg_off && *seg_off < 0)) return false;
+  const int64_t px = (int64_t)h0 * w0;
+  return px < ((int64_t)1 << 31) && img_off <= data_bytes - 3 * px && (!seg_off || *seg_off <= data_bytes - px);
+}
+
+// the bilinear sample of one pixel of the HWC source rows r0, r1 at the columns x0, x1 (axis_taps), rounded to nearest into u8:
+// per channel four products and two sums along the row, two products and a sum across the rows, rintf
+__device__ __forceinline__ void sample_bgr(const uint8_t* __restrict__ r0, const uint8_t* __restrict__ r1, int x0, int x1, float lx,
+                                           float ly, int (&bgr)[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float top = (1.f - lx) * (float)r0[3 * x0 + c] + lx * (float)r0[3 * x1 + c];
+    const float bot = (1.f - lx) * (float)r1[3 * x0 + c] + lx * (float)r1[3 * x1 + c];
+    bgr[c] = (int)rintf((1.f - ly) * top + ly * bot);
+  }
+}
+
+// SegDataPreProcessor's constants, as both kernels take them (seg_pad and rzl are the training kernel's alone)
+struct PreConst {
+  float mean[3], stdv[3];
+  float pad_val;
+  int swap, seg_pad, rzl;
+};
+
+// channel swap and (x - mean) / std of one u8 pixel into column j of a thread's three output planes
+__device__ __forceinline__ void normalise(const int (&bgr)[3], const PreConst& k, int j, float (&out)[3][4]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[c][j] = ((float)bgr[k.swap ? 2 - c : c] - k.mean[c]) / k.stdv[c];
 }
 
 // PhotoMetricDistortion.convert: fp32(img) * alpha + beta, clipped to 0 .. 255, truncated
@@ -137,12 +167,6 @@ __device__ __forceinline__ void photometric(const S2fAugParams& p, int& b, int& 
   }
 }
 
-struct AugConst {
-  float mean[3], stdv[3];
-  float pad_val;
-  int seg_pad, rzl, swap;
-};
-
 __device__ __forceinline__ void load_entry(S2fAugParams* dst, const S2fAugParams* __restrict__ src) {
   if (threadIdx.x < kParamWords) reinterpret_cast<int*>(dst)[threadIdx.x] = reinterpret_cast<const int*>(src)[threadIdx.x];
 }
@@ -153,7 +177,7 @@ __device__ __forceinline__ void load_entry(S2fAugParams* dst, const S2fAugParams
 template <bool VEC>
 __global__ __launch_bounds__(256) void aug_apply_kernel(const uint8_t* __restrict__ data, int64_t data_bytes,
                                                         const S2fAugParams* __restrict__ params, const int* __restrict__ flags,
-                                                        int Hc, int Wc, AugConst k, float* __restrict__ inputs,
+                                                        int Hc, int Wc, PreConst k, float* __restrict__ inputs,
                                                         uint8_t* __restrict__ seg) {
   __shared__ S2fAugParams sp;
   __shared__ int s_choice;
@@ -171,7 +195,7 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const uint8_t* __restric
     s_choice = c;
   }
   __syncthreads();
-  const bool ok = entry_ok(sp, data_bytes);
+  const bool ok = picture_ok(sp.h0, sp.w0, sp.H, sp.W, sp.img_off, &sp.seg_off, data_bytes);
   const int h0 = sp.h0, w0 = sp.w0, H = sp.H, W = sp.W;
   const int hv = ok ? min(Hc, H) : 0, wv = ok ? min(Wc, W) : 0;
   const int oy0 = ok ? clampi(sp.crop_y[s_choice], 0, H - hv) : 0, ox0 = ok ? clampi(sp.crop_x[s_choice], 0, W - wv) : 0;
@@ -220,18 +244,10 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const uint8_t* __restric
         lab[j] = k.seg_pad;
         continue;
       }
-      const int x0 = 3 * sc0[s], x1 = 3 * sc1[s];
-      const float lx = sl[s];
       int bgr[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float top = (1.f - lx) * (float)r0[x0 + c] + lx * (float)r0[x1 + c];
-        const float bot = (1.f - lx) * (float)r1[x0 + c] + lx * (float)r1[x1 + c];
-        bgr[c] = (int)rintf((1.f - ly) * top + ly * bot);
-      }
+      sample_bgr(r0, r1, sc0[s], sc1[s], sl[s], ly, bgr);
       photometric(sp, bgr[0], bgr[1], bgr[2]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) out[c][j] = ((float)bgr[k.swap ? 2 - c : c] - k.mean[c]) / k.stdv[c];
+      normalise(bgr, k, j, out);
       lab[j] = reduce_label(ra[ssx[s]], k.rzl);
     }
     float* o = inputs + ((int64_t)b * 3 * Hc + oy) * Wc + strip0;
@@ -269,7 +285,7 @@ __global__ __launch_bounds__(kStatThreads) void aug_crop_stats_kernel(const uint
   if (tid < 256) lds[tid] = 0;
   if (tid == 256) s_sum = s_max = s_present = 0;
   __syncthreads();
-  const bool ok = entry_ok(sp, data_bytes);
+  const bool ok = picture_ok(sp.h0, sp.w0, sp.H, sp.W, sp.img_off, &sp.seg_off, data_bytes);
   if (!ok) {          // (uniform over the workgroup)
     if (tid == 0) flags[b * S2F_AUG_CANDIDATES + cand] = 0;
     return;
@@ -319,25 +335,10 @@ __global__ __launch_bounds__(kStatThreads) void aug_crop_stats_kernel(const uint
 }
 
 // ---- the test pipeline's views (include/s2f.h "test-time views") ---------------------------------------------------------------
-static_assert(sizeof(S2fViewParams) == 48 && sizeof(S2fViewParams) % 8 == 0, "ops/misc.py VIEW_PARAM_DTYPE mirrors this layout");
-
-struct ViewConst {
-  float mean[3], stdv[3];
-  float pad_val;
-  int swap;
-};
-
 // the entry's block fits `out` and the launch's grid covers it (3 * Hp * Wp <= 3 * 2^24: no overflow)
 __device__ __forceinline__ bool view_block_ok(const S2fViewParams& p, int max_hp, int max_wp, int64_t out_elems) {
   if (p.Hp <= 0 || p.Wp <= 0 || p.Hp > max_hp || p.Wp > max_wp || p.out_off < 0 || (p.out_off & 3) != 0) return false;
   return p.out_off <= out_elems - 3 * (int64_t)p.Hp * p.Wp;
-}
-
-// the entry's picture fits `data` and its resized size fits the block: -> h0 * w0 < 2^31, so every pixel index fits an int
-__device__ __forceinline__ bool view_picture_ok(const S2fViewParams& p, int64_t data_bytes) {
-  if (p.h0 <= 0 || p.w0 <= 0 || p.H <= 0 || p.W <= 0 || p.H > p.Hp || p.W > p.Wp || p.img_off < 0) return false;
-  const int64_t px = (int64_t)p.h0 * p.w0;
-  return px < ((int64_t)1 << 31) && p.img_off <= data_bytes - 3 * px;
 }
 
 // grid (tiles of 256 quads, V).  The padded plane of entry v is cut into QUADS of 4 consecutive columns of one row, ceil(Wp / 4) per
@@ -347,7 +348,7 @@ __device__ __forceinline__ bool view_picture_ok(const S2fViewParams& p, int64_t 
 template <bool BASE16>
 __global__ __launch_bounds__(256) void test_views_kernel(const uint8_t* __restrict__ data, int64_t data_bytes,
                                                          const S2fViewParams* __restrict__ params, int max_hp, int max_wp,
-                                                         ViewConst k, float* __restrict__ out, int64_t out_elems) {
+                                                         PreConst k, float* __restrict__ out, int64_t out_elems) {
   const S2fViewParams p = params[blockIdx.y];          // (uniform over the workgroup)
   if (!view_block_ok(p, max_hp, max_wp, out_elems)) return;
   const int Hp = p.Hp, Wp = p.Wp;
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(256) void test_views_kernel(const uint8_t* __restri
   const int quad = (int)blockIdx.x * 256 + (int)threadIdx.x;          // < 2^22 + 256: max_hp, max_wp <= S2F_AUG_MAX_CROP
   if (quad >= Hp * qpr) return;
   const int oy = quad / qpr, ox = (quad - oy * qpr) * 4;
-  const bool ok = view_picture_ok(p, data_bytes);
+  const bool ok = p.H <= p.Hp && p.W <= p.Wp && picture_ok(p.h0, p.w0, p.H, p.W, p.img_off, nullptr, data_bytes);
   const int h0 = p.h0, w0 = p.w0, H = ok ? p.H : 0, W = ok ? p.W : 0;
   float o[3][4];
 #pragma unroll
@@ -376,17 +377,9 @@ __global__ __launch_bounds__(256) void test_views_kernel(const uint8_t* __restri
       int x0, x1;
       float lx;
       axis_taps(scale_x, w0, p.flip ? W - 1 - (ox + j) : ox + j, x0, x1, lx);
-      x0 *= 3;
-      x1 *= 3;
       int bgr[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {          // s2f_aug_apply's resize step, operation for operation
-        const float top = (1.f - lx) * (float)r0[x0 + c] + lx * (float)r0[x1 + c];
-        const float bot = (1.f - lx) * (float)r1[x0 + c] + lx * (float)r1[x1 + c];
-        bgr[c] = (int)rintf((1.f - ly) * top + ly * bot);
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) o[c][j] = ((float)bgr[k.swap ? 2 - c : c] - k.mean[c]) / k.stdv[c];
+      sample_bgr(r0, r1, x0, x1, lx, ly, bgr);
+      normalise(bgr, k, j, o);
     }
   }
   const int64_t plane = (int64_t)Hp * Wp;
@@ -404,13 +397,33 @@ __global__ __launch_bounds__(256) void test_views_kernel(const uint8_t* __restri
   }
 }
 
-int check_common(const char* what, const void* data, int64_t data_bytes, const void* params, int B, int Hc, int Wc) {
-  S2F_REQUIRE(data && params, S2F_EINVAL, "%s: null pointer", what);
-  S2F_REQUIRE(data_bytes > 0, S2F_EINVAL, "%s: bad byte count %lld", what, (long long)data_bytes);
-  S2F_REQUIRE(B > 0 && B <= 65535, S2F_EINVAL, "%s: bad batch size B %d (1 .. 65535)", what, B);
-  S2F_REQUIRE(Hc > 0 && Wc > 0 && Hc <= S2F_AUG_MAX_CROP && Wc <= S2F_AUG_MAX_CROP, S2F_EINVAL, "%s: bad crop size %d x %d (1 .. %d)",
-              what, Hc, Wc, S2F_AUG_MAX_CROP);
-  S2F_REQUIRE(reinterpret_cast<uintptr_t>(params) % 8 == 0, S2F_EALIGN, "%s: the parameter table is not 8-byte aligned", what);
+// the names an entry point's error texts give its table's length and its output size
+struct Names {
+  const char *what, *count, *size;
+};
+constexpr Names kStats = {"s2f_aug_crop_stats", "batch size B", "crop size"}, kApply = {"s2f_aug_apply", "batch size B", "crop size"},
+                kViews = {"s2f_test_views", "number of entries V", "largest padded size"};
+
+// what every launcher checks of data, of its n-entry table and of the size H x W its grid is made for
+int check_common(const Names& e, const void* data, int64_t data_bytes, const void* params, int n, int H, int W) {
+  S2F_REQUIRE(data && params, S2F_EINVAL, "%s: null pointer", e.what);
+  S2F_REQUIRE(data_bytes > 0, S2F_EINVAL, "%s: bad byte count %lld", e.what, (long long)data_bytes);
+  S2F_REQUIRE(n > 0 && n <= 65535, S2F_EINVAL, "%s: bad %s %d (1 .. 65535)", e.what, e.count, n);
+  S2F_REQUIRE(H > 0 && W > 0 && H <= S2F_AUG_MAX_CROP && W <= S2F_AUG_MAX_CROP, S2F_EINVAL, "%s: bad %s %d x %d (1 .. %d)", e.what,
+              e.size, H, W, S2F_AUG_MAX_CROP);
+  S2F_REQUIRE(reinterpret_cast<uintptr_t>(params) % 8 == 0, S2F_EALIGN, "%s: the parameter table is not 8-byte aligned", e.what);
+  return S2F_OK;
+}
+
+// s2f_aug_apply's and s2f_test_views' common half: check_common, the fp32 output non-null and aligned, no std of 0 -> the PreConst
+int prepare(const Names& e, const void* data, int64_t data_bytes, const void* params, int n, int H, int W, const float* out,
+            const float (&mean)[3], const float (&stdv)[3], int bgr_to_rgb, float pad_val, PreConst& k) {
+  if (int rc = check_common(e, data, data_bytes, params, n, H, W)) return rc;
+  S2F_REQUIRE(out, S2F_EINVAL, "%s: null pointer", e.what);
+  S2F_REQUIRE(stdv[0] != 0.f && stdv[1] != 0.f && stdv[2] != 0.f, S2F_EINVAL, "%s: a std of 0 (pass mean 0, std 1 for no normalisation)",
+              e.what);
+  S2F_REQUIRE(reinterpret_cast<uintptr_t>(out) % 4 == 0, S2F_EALIGN, "%s: the fp32 output is not aligned to its element size", e.what);
+  k = {{mean[0], mean[1], mean[2]}, {stdv[0], stdv[1], stdv[2]}, pad_val, bgr_to_rgb ? 1 : 0, 0, 0};
   return S2F_OK;
 }
 
@@ -420,7 +433,7 @@ extern "C" int s2f_aug_param_bytes(void) { return (int)sizeof(S2fAugParams); }
 
 extern "C" int s2f_aug_crop_stats(const uint8_t* data, int64_t data_bytes, const S2fAugParams* params, int B, int Hc, int Wc,
                                   int ignore_index, int reduce_zero_label, double cat_max_ratio, int* flags, void* stream) {
-  if (int rc = check_common("s2f_aug_crop_stats", data, data_bytes, params, B, Hc, Wc)) return rc;
+  if (int rc = check_common(kStats, data, data_bytes, params, B, Hc, Wc)) return rc;
   S2F_REQUIRE(flags, S2F_EINVAL, "s2f_aug_crop_stats: null pointer");
   S2F_REQUIRE(reinterpret_cast<uintptr_t>(flags) % 4 == 0, S2F_EALIGN, "s2f_aug_crop_stats: flags is not 4-byte aligned");
   const size_t lds = (size_t)(256 + Hc + Wc) * sizeof(int);
@@ -432,17 +445,15 @@ extern "C" int s2f_aug_crop_stats(const uint8_t* data, int64_t data_bytes, const
 extern "C" int s2f_aug_apply(const uint8_t* data, int64_t data_bytes, const S2fAugParams* params, const int* flags, int B, int Hc,
                              int Wc, float mean0, float mean1, float mean2, float std0, float std1, float std2, int bgr_to_rgb,
                              float pad_val, int seg_pad_val, int reduce_zero_label, float* inputs, uint8_t* seg, void* stream) {
-  if (int rc = check_common("s2f_aug_apply", data, data_bytes, params, B, Hc, Wc)) return rc;
-  S2F_REQUIRE(inputs && seg, S2F_EINVAL, "s2f_aug_apply: null pointer");
-  S2F_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, S2F_EINVAL, "s2f_aug_apply: a std of 0 (pass mean 0, std 1 for no normalisation)");
+  PreConst k;
+  if (int rc = prepare(kApply, data, data_bytes, params, B, Hc, Wc, inputs, {mean0, mean1, mean2}, {std0, std1, std2}, bgr_to_rgb,
+                       pad_val, k))
+    return rc;
+  S2F_REQUIRE(seg, S2F_EINVAL, "s2f_aug_apply: null pointer");
   S2F_REQUIRE(seg_pad_val >= 0 && seg_pad_val <= 255, S2F_EINVAL, "s2f_aug_apply: seg_pad_val %d is no uint8", seg_pad_val);
-  S2F_REQUIRE(reinterpret_cast<uintptr_t>(inputs) % 4 == 0 && reinterpret_cast<uintptr_t>(flags) % 4 == 0, S2F_EALIGN,
-              "s2f_aug_apply: a pointer is not aligned to its element size");
-  AugConst k = {{mean0, mean1, mean2}, {std0, std1, std2}, 0.f, 0, 0, 0};
-  k.pad_val = pad_val;
+  S2F_REQUIRE(reinterpret_cast<uintptr_t>(flags) % 4 == 0, S2F_EALIGN, "s2f_aug_apply: flags is not 4-byte aligned");
   k.seg_pad = seg_pad_val;
   k.rzl = reduce_zero_label ? 1 : 0;
-  k.swap = bgr_to_rgb ? 1 : 0;
   const dim3 grid((unsigned)((Wc + kStrip - 1) / kStrip), (unsigned)((Hc + kRowsPerWg - 1) / kRowsPerWg), (unsigned)B);
   const bool vec = (Wc % 4) == 0 && s2f_aligned16(inputs) && reinterpret_cast<uintptr_t>(seg) % 4 == 0;
   hipStream_t s = (hipStream_t)stream;
@@ -457,18 +468,11 @@ extern "C" int s2f_view_param_bytes(void) { return (int)sizeof(S2fViewParams); }
 extern "C" int s2f_test_views(const uint8_t* data, int64_t data_bytes, const S2fViewParams* params, int V, int max_Hp, int max_Wp,
                               float mean0, float mean1, float mean2, float std0, float std1, float std2, int bgr_to_rgb,
                               float pad_val, float* out, int64_t out_elems, void* stream) {
-  S2F_REQUIRE(data && params && out, S2F_EINVAL, "s2f_test_views: null pointer");
-  S2F_REQUIRE(data_bytes > 0, S2F_EINVAL, "s2f_test_views: bad byte count %lld", (long long)data_bytes);
-  S2F_REQUIRE(V > 0 && V <= 65535, S2F_EINVAL, "s2f_test_views: bad number of entries V %d (1 .. 65535)", V);
-  S2F_REQUIRE(max_Hp > 0 && max_Wp > 0 && max_Hp <= S2F_AUG_MAX_CROP && max_Wp <= S2F_AUG_MAX_CROP, S2F_EINVAL,
-              "s2f_test_views: bad largest padded size %d x %d (1 .. %d)", max_Hp, max_Wp, S2F_AUG_MAX_CROP);
-  S2F_REQUIRE(reinterpret_cast<uintptr_t>(params) % 8 == 0, S2F_EALIGN, "s2f_test_views: the parameter table is not 8-byte aligned");
+  PreConst k;
+  if (int rc = prepare(kViews, data, data_bytes, params, V, max_Hp, max_Wp, out, {mean0, mean1, mean2}, {std0, std1, std2},
+                       bgr_to_rgb, pad_val, k))
+    return rc;
   S2F_REQUIRE(out_elems > 0, S2F_EINVAL, "s2f_test_views: bad element count %lld", (long long)out_elems);
-  S2F_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, S2F_EINVAL, "s2f_test_views: a std of 0 (pass mean 0, std 1 for no normalisation)");
-  S2F_REQUIRE(reinterpret_cast<uintptr_t>(out) % 4 == 0, S2F_EALIGN, "s2f_test_views: out is not aligned to its element size");
-  ViewConst k = {{mean0, mean1, mean2}, {std0, std1, std2}, 0.f, 0};
-  k.pad_val = pad_val;
-  k.swap = bgr_to_rgb ? 1 : 0;
   const int64_t quads = (int64_t)max_Hp * ((max_Wp + 3) / 4);
   const dim3 grid((unsigned)((quads + 255) / 256), (unsigned)V);
   hipStream_t s = (hipStream_t)stream;

@@ -1,4 +1,5 @@
 """Tiled transposes, exact-2x and general bilinear resizing, the mask-loss kernels of the Hungarian-matched loss."""
+import numpy as _np
 import torch
 
 from .config import cfg
@@ -405,10 +406,20 @@ def tta_finish(acc, n_views, threshold=0.3):
     return out
 
 
-# ------------------------------------------------------------------------------------------------ training augmentation
+# ------------------------------------------------------------------------------------------------ training augmentation, test-time views
 AUG_CANDIDATES = 11                  # include/s2f.h S2F_AUG_CANDIDATES
 AUG_MAX_CROP = 4096                  # include/s2f.h S2F_AUG_MAX_CROP
-AUG_PARAM_BYTES = lib.s2f_aug_param_bytes()
+AUG_PARAM_BYTES, VIEW_PARAM_BYTES = lib.s2f_aug_param_bytes(), lib.s2f_view_param_bytes()
+# include/s2f.h S2fAugParams and S2fViewParams, field for field (augment.py writes the tables)
+PARAM_DTYPE = _np.dtype([
+    ("img_off", "<i8"), ("seg_off", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("H", "<i4"), ("W", "<i4"),
+    ("crop_y", "<i4", (AUG_CANDIDATES,)), ("crop_x", "<i4", (AUG_CANDIDATES,)), ("flip", "<i4"),
+    ("bright_on", "<i4"), ("mode", "<i4"), ("contrast_on", "<i4"), ("sat_on", "<i4"), ("hue_on", "<i4"), ("hue_delta", "<i4"),
+    ("bright_beta", "<f4"), ("contrast_alpha", "<f4"), ("sat_alpha", "<f4")])
+VIEW_PARAM_DTYPE = _np.dtype([("img_off", "<i8"), ("out_off", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("H", "<i4"), ("W", "<i4"),
+                              ("Hp", "<i4"), ("Wp", "<i4"), ("flip", "<i4"), ("reserved", "<i4")])
+assert PARAM_DTYPE.itemsize == AUG_PARAM_BYTES, "PARAM_DTYPE does not mirror S2fAugParams"
+assert VIEW_PARAM_DTYPE.itemsize == VIEW_PARAM_BYTES, "VIEW_PARAM_DTYPE does not mirror S2fViewParams"
 
 
 def _aug_cuda(*ts):
@@ -417,20 +428,38 @@ def _aug_cuda(*ts):
             raise RuntimeError("spike2former_amd ops run on the GPU only (HIP kernels); got a CPU tensor")
 
 
-def _aug_buffers(data, params):
-    _aug_cuda(data, params)
-    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous(), "data: one contiguous uint8 byte buffer"
-    assert params.dtype == torch.uint8 and params.dim() == 1 and params.is_contiguous() and params.numel() % AUG_PARAM_BYTES == 0 \
-        and params.numel() > 0, f"params: B table entries of {AUG_PARAM_BYTES} bytes as one uint8 buffer"
-    return params.numel() // AUG_PARAM_BYTES
+def _mean_std(mean, std):
+    """SegDataPreProcessor's mean and std (both or neither: no normalisation) -> two lists of three floats"""
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    m = [float(v) for v in mean] if mean is not None else [0.0] * 3
+    s = [float(v) for v in std] if std is not None else [1.0] * 3
+    if len(m) != 3 or len(s) != 3:
+        raise ValueError("mean and std have three values")
+    return m, s
+
+
+def _byte_buffer(t, what="data"):
+    if not (t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
+        raise ValueError(f"{what}: one contiguous uint8 byte buffer")
+
+
+def _staged_table(t, entry_bytes, least=1):
+    """a table as staged in device memory: whole entries of entry_bytes, at least `least`, as one uint8 buffer -> their number"""
+    _byte_buffer(t, "the parameter table")
+    if t.numel() % entry_bytes or t.numel() < least * entry_bytes:
+        raise ValueError(f"the parameter table: {least} or more entries of {entry_bytes} bytes, got {t.numel()} bytes")
+    _aug_cuda(t)
+    return t.numel() // entry_bytes
 
 
 def aug_crop_stats(data, params, flags, crop_size, ignore_index=255, reduce_zero_label=False, cat_max_ratio=0.75):
     """flags int32 [B, 11] <- RandomCrop.crop_bbox's test of every candidate crop window of the nearest-resized annotations
     (s2f_aug_crop_stats).  data: the batch's packed uint8 pictures and annotations; params: the B-entry table (S2fAugParams) as
     bytes; both CUDA.  There is no other route: a CPU tensor raises."""
-    B = _aug_buffers(data, params)
-    _aug_cuda(flags)
+    _byte_buffer(data)
+    B = _staged_table(params, AUG_PARAM_BYTES)
+    _aug_cuda(data, flags)
     assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B, AUG_CANDIDATES)
     Hc, Wc = (int(v) for v in crop_size)
     check(lib.s2f_aug_crop_stats(_ptr(data), data.numel(), _ptr(params), B, Hc, Wc, int(ignore_index), int(bool(reduce_zero_label)),
@@ -443,32 +472,20 @@ def aug_apply(data, params, flags, inputs, seg, mean=None, std=None, bgr_to_rgb=
     """inputs fp32 [B, 3, Hc, Wc] and seg uint8 [B, Hc, Wc] <- resize, chosen crop, flip, photometric distortion, channel swap,
     normalisation and padding of every picture of the batch in one launch that writes every element once (s2f_aug_apply).
     flags: what aug_crop_stats wrote, or None (candidate 0).  There is no other route: a CPU tensor raises."""
-    B = _aug_buffers(data, params)
-    _aug_cuda(inputs, seg)
+    _byte_buffer(data)
+    m, s = _mean_std(mean, std)
+    B = _staged_table(params, AUG_PARAM_BYTES)
+    _aug_cuda(data, inputs, seg)
     assert inputs.dtype == torch.float32 and inputs.is_contiguous() and inputs.dim() == 4 and inputs.shape[:2] == (B, 3)
     Hc, Wc = (int(v) for v in inputs.shape[-2:])
     assert seg.dtype == torch.uint8 and seg.is_contiguous() and tuple(seg.shape) == (B, Hc, Wc)
     if flags is not None:
         _aug_cuda(flags)
         assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B, AUG_CANDIDATES)
-    assert (mean is None) == (std is None), "mean and std go together"
-    m = [float(v) for v in mean] if mean is not None else [0.0] * 3
-    s = [float(v) for v in std] if std is not None else [1.0] * 3
-    assert len(m) == 3 and len(s) == 3
     check(lib.s2f_aug_apply(_ptr(data), data.numel(), _ptr(params), _ptr(flags), B, Hc, Wc, *m, *s, int(bool(bgr_to_rgb)),
                             float(pad_val), int(seg_pad_val), int(bool(reduce_zero_label)), _ptr(inputs), _ptr(seg), _stream()),
           "s2f_aug_apply")
     return inputs, seg
-
-
-# ------------------------------------------------------------------------------------------------ test-time views
-import numpy as _np
-
-VIEW_PARAM_BYTES = lib.s2f_view_param_bytes()
-# include/s2f.h S2fViewParams, field for field
-VIEW_PARAM_DTYPE = _np.dtype([("img_off", "<i8"), ("out_off", "<i8"), ("h0", "<i4"), ("w0", "<i4"), ("H", "<i4"), ("W", "<i4"),
-                              ("Hp", "<i4"), ("Wp", "<i4"), ("flip", "<i4"), ("reserved", "<i4")])
-assert VIEW_PARAM_DTYPE.itemsize == VIEW_PARAM_BYTES, "VIEW_PARAM_DTYPE does not mirror S2fViewParams"
 
 
 def check_view_table(table, data_bytes, out_elems):
@@ -503,29 +520,21 @@ def check_view_table(table, data_bytes, out_elems):
 
 def test_views(data, table, out, mean=None, std=None, bgr_to_rgb=False, pad_val=0.0, table_dev=None):
     """Every view of a test iteration in ONE launch (s2f_test_views): per table entry the keep-ratio bilinear resize of a uint8 BGR
-    picture of `data` (the arithmetic of aug_apply's resize), the horizontal flip, the channel swap, (x - mean) / std and the padding
-    with pad_val, into the entry's [3, Hp, Wp] block of the packed fp32 buffer `out`; elements between the blocks are not touched.
-    table: a numpy array of VIEW_PARAM_DTYPE -- the host wrote it, so check_view_table validates EVERY entry here, before any
-    launch (ValueError); table_dev: its staged copy in device memory as uint8 (None: copied here).  There is no other route: a CPU
-    tensor raises."""
-    if not (data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()):
-        raise ValueError("data: one contiguous uint8 byte buffer")
+    picture of `data` (aug_apply's resize: the kernels call one sampler), the horizontal flip, the channel swap, (x - mean) / std and
+    the padding with pad_val, into the entry's [3, Hp, Wp] block of the packed fp32 buffer `out`; elements between the blocks are not
+    touched.  table: a numpy array of VIEW_PARAM_DTYPE -- the host wrote it, so check_view_table validates EVERY entry here, before
+    any launch (ValueError); table_dev: its staged copy in device memory as uint8 (None: copied here).  There is no other route: a
+    CPU tensor raises."""
+    _byte_buffer(data)
     if not (out.dtype == torch.float32 and out.dim() == 1 and out.is_contiguous()):
         raise ValueError("out: one contiguous fp32 buffer")
     table = check_view_table(table, data.numel(), out.numel())
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std go together")
-    m = [float(v) for v in mean] if mean is not None else [0.0] * 3
-    s = [float(v) for v in std] if std is not None else [1.0] * 3
-    if len(m) != 3 or len(s) != 3:
-        raise ValueError("mean and std have three values")
+    m, s = _mean_std(mean, std)
     _aug_cuda(data, out)
     V = len(table)
     if table_dev is None:
         table_dev = torch.from_numpy(_np.ascontiguousarray(table).view(_np.uint8).copy()).to(data.device)
-    _aug_cuda(table_dev)
-    assert table_dev.dtype == torch.uint8 and table_dev.is_contiguous() and table_dev.numel() >= V * VIEW_PARAM_BYTES, \
-        f"table_dev: the V table entries of {VIEW_PARAM_BYTES} bytes as one uint8 buffer"
+    _staged_table(table_dev, VIEW_PARAM_BYTES, V)
     check(lib.s2f_test_views(_ptr(data), data.numel(), _ptr(table_dev), V, int(table["Hp"].max()), int(table["Wp"].max()), *m, *s,
                              int(bool(bgr_to_rgb)), float(pad_val), _ptr(out), out.numel(), _stream()), "s2f_test_views")
     return out

@@ -224,3 +224,24 @@ def test_graph_replays_follow_the_staged_picture():
         for g, w in zip(data["inputs"], want):
             assert np.array_equal(g.cpu().numpy(), w)
     del graph
+
+
+# ------------------------------------------------------------------------------------------------ 9. one sampler, two pipelines
+@pytest.mark.parametrize("flip", (False, True))
+@pytest.mark.parametrize("src, size, padded", [((37, 53), (29, 41), (40, 56)),          # 16-byte stores with padding
+                                               ((37, 53), (29, 41), (29, 41)),          # scalar stores on both sides
+                                               ((24, 40), (48, 80), (48, 80)),          # 2x, 16-byte stores
+                                               ((64, 48), (23, 90), (32, 96))])         # shrinking rows, enlarging columns
+def test_a_view_is_the_training_route_without_its_randomness(src, size, padded, flip):
+    """TrainAugment with nothing random left -- no RandomResize draw (the entry names H x W), the crop at (0, 0) and as large as
+    the padded view, no crop rule, no photometric distortion -- writes the tensor TestAugment writes for the view (H, W, Hp, Wp,
+    flip): both kernels call one sampler and one normalisation.  No tolerance."""
+    from spike2former_amd.augment import TrainAugment
+    from test_gpu_augment import entry, prefilled
+    img, seg = VR.scene(*src, seed=9)
+    pre = dict(pad_val=-1.5, max_source_pixels=64 * 128, **NORM)
+    train = TrainAugment(scale=None, cat_max_ratio=1.0, photometric=None, crop_size=padded, batch_size=1, seed=0, rank=0, **pre)
+    got, _ = train([img], [seg], np.array([entry(train, *src, *size, origins=(0, 0), flip=int(flip))]), out=prefilled(train, 1))
+    data, _ = run(make(**pre), [img], views=[(*size, *padded, flip)])
+    assert tuple(got.shape) == (1, 3, *padded) and not bool(torch.isnan(got).any())
+    assert torch.equal(got, data["inputs"][0])
