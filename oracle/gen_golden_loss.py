@@ -2,9 +2,10 @@
 
 Runs the REFERENCE's own loss path on CPU (mmdet MaskFormerHead.loss_by_feat with HungarianAssigner / MaskPseudoSampler /
 CrossEntropyLoss / FocalLoss / DiceLoss and mmseg's _seg_data_to_instance_data, imported through oracle/ref_loss_shells.py)
-on seeded inputs and stores inputs + outputs in tests/golden/loss_f1.npz.  Usable only where /root/reference is mounted:
+on seeded inputs and stores inputs + outputs in tests/golden/loss_f1.npz (`cases`) and tests/golden/loss_f1_edges.npz
+(`cases_edges`: maps that leave one tile / one chunk of the loss kernels).  Usable only where /root/reference is mounted:
 
-    python -m oracle.gen_golden_loss
+    python -m oracle.gen_golden_loss [f1 | edges]         (default: both files)
 """
 import os
 
@@ -13,7 +14,9 @@ import torch
 
 from . import ref_loss_shells as rl
 
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "loss_f1.npz")
+GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+OUT = os.path.join(GOLDEN, "loss_f1.npz")
+OUT_EDGES = os.path.join(GOLDEN, "loss_f1_edges.npz")
 
 
 def cases():
@@ -36,10 +39,38 @@ def cases():
     return out
 
 
-def main():
+def _region_seg(B, H, W, K, g):
+    """[B, 1, H, W] piecewise-constant label maps: a 3 x 4 grid of blocks with unequal borders, a random class each, and a band of
+    the ignored label that cuts through the blocks"""
+    seg = torch.empty(B, 1, H, W, dtype=torch.int64)
+    ys, xs = [0, H // 3 + 1, (2 * H) // 3 - 1, H], [0, W // 4 + 3, W // 2 + 1, (3 * W) // 4 - 2, W]
+    for b in range(B):
+        pick = torch.randint(0, K, (12,), generator=g)
+        for i in range(3):
+            for j in range(4):
+                seg[b, 0, ys[i]:ys[i + 1], xs[j]:xs[j + 1]] = pick[i * 4 + j]
+        seg[b, 0, H // 2 - 1:H // 2 + 2, W // 5:(4 * W) // 5 + b] = 255
+    return seg
+
+
+def cases_edges():
+    """Maps past one 8 x 64 tile of the label-map backward kernel, region label maps with a band of 255.  Logits within +/-12: the
+    reference's float32 costs and the fp64-following cost kernel agree on the assignment there (see costs_all_classes)."""
+    out = {}
+    g = torch.Generator().manual_seed(23)
+    K, Q = 6, 8                                            # 9 x 66: one row and two columns into the next tiles
+    seg = _region_seg(2, 18, 132, K, g)
+    out["e"] = (torch.randn(2, 2, Q, K + 1, generator=g), (torch.randn(2, 2, Q, 9, 66, generator=g) * 3).clamp(-12, 12), seg, K)
+    K, Q = 12, 5                                           # 17 x 130: three tiles each way with remainders; more classes than queries
+    seg = _region_seg(2, 34, 260, K, g)
+    out["f"] = (torch.randn(2, 2, Q, K + 1, generator=g), (torch.randn(2, 2, Q, 17, 130, generator=g) * 3).clamp(-12, 12), seg, K)
+    return out
+
+
+def write(case_set, path):
     L = rl.load()
     blob = {}
-    for name, (cls, mp, seg, K) in cases().items():
+    for name, (cls, mp, seg, K) in case_set.items():
         Q = cls.shape[2]
         head = rl.reference_loss_head(K, Q)
         cls, mp = cls.clone().requires_grad_(True), mp.clone().requires_grad_(True)
@@ -64,9 +95,17 @@ def main():
         blob[f"{name}_gcls"], blob[f"{name}_gmasks"] = cls.grad.numpy(), mp.grad.numpy()
         blob[f"{name}_labels"] = np.concatenate([i.labels.numpy() for i in inst]) if inst else np.zeros(0, np.int64)
         print(name, {k: round(float(v), 5) for k, v in losses.items()})
-    np.savez_compressed(OUT, **blob)
-    print("wrote", OUT, os.path.getsize(OUT), "bytes")
+    np.savez_compressed(path, **blob)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
+def main(which=("f1", "edges")):
+    if "f1" in which:
+        write(cases(), OUT)
+    if "edges" in which:
+        write(cases_edges(), OUT_EDGES)
 
 
 if __name__ == "__main__":
-    main()
+    import sys
+    main(tuple(sys.argv[1:]) or ("f1", "edges"))

@@ -154,7 +154,11 @@ class MaskFormerLoss:
 
     def costs_all_classes(self, all_cls_scores, all_mask_preds, seg_u8):
         """-> cost [L, B, Q, K] against every class id (hungarian_assigner.py:118-126 for the columns that exist) and the pixel
-        count [B, 256] of every label value in the full-resolution maps (which classes exist)."""
+        count [B, 256] of every label value in the full-resolution maps (which classes exist).
+        The kernel forms 1 - s as sigmoid(-u), without the subtraction, so at saturated logits (u > ~17, where float32 `1 - s` is
+        exactly 0) its costs are not those of `match_costs` evaluated in float32 and the assignment may differ from the reference's.
+        What the kernel follows is the same expression in fp64, to 2e-5 of a bin's terms (tests/test_loss_ref_host.py pins the
+        difference, tests/test_gpu_loss_kernels.py the kernel)."""
         from . import ops
         L, B, Q = all_cls_scores.shape[:3]
         K = self.num_classes
