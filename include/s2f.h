@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 39
+#define S2F_ABI_VERSION 40
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -41,7 +41,7 @@ const char* s2f_last_error(void);
  * (hipExtLaunchKernelGGL start/stop events = the dispatch packet's own begin/end timestamps, what rocprofv3 reports).
  *   s2f_event_create/destroy: a hipEvent_t as void*.
  *   s2f_time_next_call(start, stop): arms THIS thread; the next s2f_lif_fwd / s2f_lif_bwd / s2f_bn_stats /
- *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist call stamps `start` with the begin of
+ *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist / s2f_seg_confusion call stamps `start` with the begin of
  *       its first kernel and `stop` with the end of its last one, then disarms.  Not valid during stream capture.
  *   s2f_event_elapsed_us: stop - start in microseconds (both must have completed: synchronise first). */
 void* s2f_event_create(void);
@@ -568,6 +568,27 @@ int s2f_tta_finish(float* acc, int64_t* label, float* label_f, int K, int64_t HW
 #define S2F_SEG_REDUCE_ZERO_LABEL 1
 int s2f_seg_hist(const void* pred, int pred_dtype, const void* label, int label_dtype, int64_t label_row_stride,
                  int64_t label_pixel_stride, int W, int64_t HW, int K, int ignore_index, int flags, int64_t* totals, void* stream);
+/* The class-pair table behind those histograms (ABI 40): ONE launch that ADDS one image into matrix, an int64 [K, K] device buffer the
+ * caller owns and zeroes, row = label, column = prediction -- what the reference's tools/analysis_tools/confusion_matrix.py:46-65
+ * takes on the host as bincount(n * gt + pred, minlength = n * n).  pred, pred_dtype, label, label_dtype, the strides, W, HW, K, the
+ * bounds, the alignment rules and S2F_SEG_REDUCE_ZERO_LABEL are exactly those of s2f_seg_hist.  For pixel p, with l the label after
+ * the reduce_zero_label mapping (applied to the raw label FIRST) and c the prediction:
+ *   - the pixel counts iff l != ignore_index, 0 <= l < K, and c is a class: 0 <= c < K, for S2F_SEG_PRED_F32 also integral (NaN is
+ *     never a class);
+ *   - then matrix[l][c] += 1.  The accumulator is added to, never cleared.
+ * The reference's function has no ignore_index: a 255 label takes its bincount out of the n * n range and its reshape fails.  The
+ * rule here is the one IoUMetric / s2f_seg_hist apply, so diag(matrix) == totals[0] always, and the column sums == totals[1], the
+ * row sums == totals[2] whenever every participating pixel has both a valid prediction and a valid label (the arg-max of a K-class
+ * head always has).  Integer adds only: exact, independent of the arrival order.  Nothing is allocated and nothing synchronises:
+ * capturable in a hipGraph.
+ * Routes: a [K][K] table of 32-bit counters per workgroup in LDS while 4 K^2 bytes fit S2F_SEG_CONF_LDS_BYTES and what the device
+ * reports for one workgroup (K <= 181; 90 000 B at K = 150, 116 964 B at K = 171: 128 KiB of the CU's 160 KiB hold the data sets'
+ * 150 / 171 classes and leave the rest of the CU's LDS to whatever else is resident); otherwise, or with S2F_SEG_CONF_GLOBAL in
+ * flags at any K, 64-bit global atomics straight into matrix.  Both give the same matrix.  Any other flag bit is S2F_EINVAL. */
+#define S2F_SEG_CONF_LDS_BYTES 131072
+#define S2F_SEG_CONF_GLOBAL 2
+int s2f_seg_confusion(const void* pred, int pred_dtype, const void* label, int label_dtype, int64_t label_row_stride,
+                      int64_t label_pixel_stride, int W, int64_t HW, int K, int ignore_index, int flags, int64_t* matrix, void* stream);
 
 /* ---- training augmentation: the configs' train_pipeline + SegDataPreProcessor on the device (csrc/augment.hip, ABI 37) ------------
  * RandomResize(keep_ratio) -> RandomCrop(cat_max_ratio) -> RandomFlip -> PhotoMetricDistortion (mmseg datasets/transforms/

@@ -17,7 +17,7 @@ from .registry import HOOKS, METRICS, MODELS, ConfigDict, register_upstream  # n
 from . import reparam  # noqa: F401
 from .segmentor import EncoderDecoder, ResetModelHook, headline_loss  # noqa: F401
 from .tta import SegTTAModel  # noqa: F401
-from .metrics import IoUMetric, evaluate  # noqa: F401
+from .metrics import ConfusionMatrix, IoUMetric, evaluate  # noqa: F401
 from .augment import TestAugment, TrainAugment  # noqa: F401
 from .train import LinearThenPoly, OptimWrapper, parse_losses, train_step  # noqa: F401
 

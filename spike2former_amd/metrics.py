@@ -6,7 +6,10 @@ Per image ONE `ops.seg_hist` launch adds the class histograms {intersection, pre
 accumulator on the prediction's device; nothing leaves the device until `evaluate()` reads the accumulator back once.  Stated
 deviations: the totals are summed as int64, not as float32 tensors (exact beyond 2^24 pixels per class), and
 the ranks' totals are all-reduced instead of gathering per-image results -- a sum cannot drop the samples a padding
-DistributedSampler duplicates, so `evaluate` below shards the batches without padding."""
+DistributedSampler duplicates, so `evaluate` below shards the batches without padding.
+
+`ConfusionMatrix` keeps the full class-pair table [K, K] of the same pixels in the same way (one `ops.seg_confusion` launch per
+image); IoUMetric's three rows are its diagonal, column sums and row sums."""
 import logging
 import os.path as osp
 from collections import OrderedDict
@@ -169,6 +172,118 @@ class IoUMetric:
         return out
 
 
+@METRICS.register_module()
+class ConfusionMatrix:
+    """The class-pair table of an evaluation: matrix[label][prediction] in pixels (the reference's
+    tools/analysis_tools/confusion_matrix.py:46-65, there a host-side bincount per image) -- which class the missed pixels of a bad
+    IoU row went to.  Per image ONE `ops.seg_confusion` launch into an int64 [K, K] accumulator on the prediction's device, one
+    all-reduce and one read-back in `evaluate()`, as IoUMetric.  ignore_index / prefix / collect_device (accepted and unused) /
+    label_reduce_zero as IoUMetric; a pixel counts iff its label is not ignore_index and both its label and its prediction are
+    classes (the reference's tool has no ignore_index and fails on a 255 label).  IoUMetric's three rows are this table's diagonal,
+    column sums and row sums -- `totals()` -- so `evaluate()` returns the same aAcc / mIoU / mAcc."""
+    default_prefix = None
+
+    def __init__(self, ignore_index=255, label_reduce_zero=False, prefix=None, collect_device="cpu", **kwargs):
+        self.ignore_index = ignore_index
+        self.label_reduce_zero = bool(label_reduce_zero)
+        self.prefix = prefix or self.default_prefix
+        self.collect_device = collect_device
+        self.dataset_meta = None
+        self._acc = None
+        self.matrix = None          # numpy int64 [K, K] of the last evaluate()
+
+    @property
+    def num_classes(self):
+        assert self.dataset_meta is not None and "classes" in self.dataset_meta, "set dataset_meta = dict(classes=[...]) first"
+        return len(self.dataset_meta["classes"])
+
+    def accumulator(self, device):
+        """the int64 [K, K] accumulator, created on first use (the rules of IoUMetric.totals)"""
+        if self._acc is None or self._acc.device != torch.device(device) or self._acc.shape[0] != self.num_classes:
+            assert self._acc is None or not bool(self._acc.any()), "the predictions moved to another device mid-evaluation"
+            self._acc = torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64, device=device)
+        return self._acc
+
+    def reset(self):
+        if self._acc is not None:
+            self._acc.zero_()
+
+    def process(self, data_batch, data_samples):
+        for sample in data_samples:
+            pred = _field(sample, "pred_sem_seg")
+            label = _field(sample, "gt_sem_seg")
+            if label.device != pred.device:
+                label = label.to(pred.device, non_blocking=True)
+            ops.seg_confusion(pred, label, self.accumulator(pred.device), self.ignore_index, self.label_reduce_zero)
+
+    # ---- views of the last evaluated matrix
+    def _evaluated(self):
+        assert self.matrix is not None, "evaluate() first"
+        return self.matrix
+
+    def _names(self):
+        return [str(n) for n in self.dataset_meta["classes"]]
+
+    def totals(self):
+        """-> int64 [3, K] {diagonal, column sums, row sums} = IoUMetric's {intersection, prediction areas, label areas}"""
+        m = self._evaluated()
+        return np.stack([np.diagonal(m), m.sum(axis=0), m.sum(axis=1)]).astype(np.int64)
+
+    def normalized(self):
+        """-> float64 [K, K]: every row in percent of its sum (confusion_matrix.py:85-88); an empty row is NaN"""
+        m = self._evaluated().astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return m / m.sum(axis=1, keepdims=True) * 100
+
+    def top_confusions(self, n=10):
+        """-> the n largest off-diagonal entries as (label name, prediction name, pixels, percent of the label's row), by pixels
+        (descending), then by label and prediction index (ties are deterministic); the percent of an empty row is NaN"""
+        m = self._evaluated()
+        K = m.shape[0]
+        idx = np.flatnonzero(~np.eye(K, dtype=bool).reshape(-1))
+        idx = idx[np.argsort(-m.reshape(-1)[idx], kind="stable")][:max(int(n), 0)]          # stable: ties stay in index order
+        names, pct = self._names(), self.normalized()
+        return [(names[i // K], names[i % K], int(m.flat[i]), float(pct.flat[i])) for i in (int(i) for i in idx)]
+
+    def save(self, path):
+        """the int64 matrix as .npy, or as .csv with the class names as the header line"""
+        m = self._evaluated()
+        ext = osp.splitext(path)[1].lower()
+        if ext == ".npy":
+            np.save(path, m)
+        elif ext == ".csv":
+            with open(path, "w") as f:
+                f.write(",".join(self._names()) + "\n")
+                for row in m:
+                    f.write(",".join(str(int(v)) for v in row) + "\n")
+        else:
+            raise ValueError(f"{path}: .npy or .csv")
+
+    def evaluate(self, size=None, n=10):
+        """Sum the ranks' matrices (one int64 all-reduce over the default process group when one is initialised), read the sum back
+        once into `self.matrix`, zero the accumulator -> {'aAcc', 'mIoU', 'mAcc'} of the matrix through IoUMetric's arithmetic
+        (keys 'prefix/name' with a prefix).  The per-class table and the `n` largest confusions go to the log.  `size` is accepted
+        and unused, as in IoUMetric.evaluate."""
+        import torch.distributed as dist
+        t = self._acc if self._acc is not None else torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            t = t.clone() if not (t.is_cuda and dist.get_backend() == "gloo") else t.cpu()
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        self.matrix = t.cpu().numpy().astype(np.int64, copy=True)
+        self.reset()
+        scorer = IoUMetric(ignore_index=self.ignore_index, iou_metrics=["mIoU"])
+        scorer.dataset_meta = self.dataset_meta
+        out = scorer.compute_metrics(self.totals())
+        top = [t for t in self.top_confusions(n) if t[2] > 0]
+        if top:
+            lines = ["largest confusions (label -> prediction: pixels, % of the label's row):"]
+            lines += [f"  {a} -> {b}: {px}, {pct:.2f}" for a, b, px, pct in top]
+            logging.getLogger("spike2former_amd").info("\n".join(lines))
+        if self.prefix:
+            out = OrderedDict((f"{self.prefix}/{k}", v) for k, v in out.items())
+        return out
+
+
 def _is_main_process():
     import torch.distributed as dist
     return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
@@ -177,12 +292,21 @@ def _is_main_process():
 def evaluate(model, batches, metric, *, rank=0, world_size=1):
     """mmengine's TestLoop with ResetModelHook.before_test_iter for one rank: every `world_size`-th batch starting at `rank` (no
     padding: see the module docstring) -- membranes reset, `model.test_step(batch)` (an EncoderDecoder or a SegTTAModel),
-    `metric.process` -- then `metric.evaluate()`.  Nothing inside the loop reads the device back."""
+    `metric.process` -- then `metric.evaluate()`.  Nothing inside the loop reads the device back.  `metric` may be a list or tuple
+    of metrics: each processes every batch's samples, and their dictionaries are merged in order."""
+    metrics = list(metric) if isinstance(metric, (list, tuple)) else [metric]
     model.eval()
     with torch.no_grad():
         for i, batch in enumerate(batches):
             if i % world_size != rank:
                 continue
             reset_net(model)
-            metric.process(batch, model.test_step(batch))
-    return metric.evaluate()
+            samples = model.test_step(batch)
+            for m in metrics:
+                m.process(batch, samples)
+    if not isinstance(metric, (list, tuple)):
+        return metric.evaluate()
+    out = OrderedDict()
+    for m in metrics:
+        out.update(m.evaluate())
+    return out

@@ -600,6 +600,60 @@ def seg_hist(pred, label, totals, ignore_index=255, reduce_zero_label=False):
     return totals
 
 
+SEG_CONF_LDS_BYTES = 131072          # include/s2f.h S2F_SEG_CONF_LDS_BYTES: [K][K] 32-bit counters per workgroup up to K = 181
+_SEG_CONF_GLOBAL = 2                 # include/s2f.h S2F_SEG_CONF_GLOBAL
+
+
+def _seg_confusion_torch(pred, label, matrix, ignore_index, reduce_zero_label):
+    """the semantics of s2f_seg_confusion in exact integer torch arithmetic (CPU tensors; CUDA tensors the kernel does not take)"""
+    K = matrix.shape[0]
+    lab = label.to(torch.int64)
+    if reduce_zero_label:
+        lab = torch.where((lab == 0) | (lab == 255), torch.full_like(lab, 255), lab - 1)
+    if pred.is_floating_point():
+        ok = (pred >= 0) & (pred < K) & (pred == pred.trunc())
+        pc = torch.where(ok, pred, torch.zeros_like(pred)).to(torch.int64)
+    else:
+        pc = pred.to(torch.int64)
+        ok = (pc >= 0) & (pc < K)
+    ok = ok & (lab != ignore_index) & (lab >= 0) & (lab < K)
+    matrix += torch.bincount(lab[ok] * K + pc[ok], minlength=K * K).view(K, K)
+    return matrix
+
+
+def seg_confusion(pred, label, matrix, ignore_index=255, reduce_zero_label=False, route=None):
+    """matrix int64 [K, K] += the class-pair counts of ONE image, row = label, column = prediction (s2f_seg_confusion; the reference's
+    tools/analysis_tools/confusion_matrix.py:46-65 with IoUMetric's ignore_index rule, which that function lacks).  A pixel counts
+    iff its (reduce_zero_label-mapped) label != ignore_index and is a class and its prediction is a class; pred / label shapes,
+    dtypes and the transposed label as seg_hist.  route: None -- the kernel chooses between its per-workgroup LDS table and global
+    atomics by K -- or "global" to force the latter (both give the same matrix).  CUDA tensors run the kernel; CPU tensors the same
+    arithmetic in torch (the package's CPU implementation of this op)."""
+    assert route in (None, "global"), f"route {route!r}: None or 'global'"
+    pred = pred[0] if pred.dim() == 3 and pred.shape[0] == 1 else pred
+    label = label[0] if label.dim() == 3 and label.shape[0] == 1 else label
+    assert pred.dim() == 2 and label.dim() == 2, "one [H, W] (or [1, H, W]) prediction and label map"
+    if label.shape[0] != pred.shape[0] and label.shape[0] == pred.shape[1]:
+        label = label.t()
+    assert label.shape == pred.shape, f"label {tuple(label.shape)} does not fit the prediction {tuple(pred.shape)}"
+    assert (matrix.dtype == torch.int64 and matrix.dim() == 2 and matrix.shape[0] == matrix.shape[1] and matrix.is_contiguous()), \
+        "matrix: one contiguous int64 [K, K]"
+    assert pred.device == label.device == matrix.device, "pred, label and matrix on one device"
+    H, W = pred.shape
+    K = matrix.shape[0]
+    if not pred.is_cuda:
+        return _seg_confusion_torch(pred, label, matrix, int(ignore_index), bool(reduce_zero_label))
+    if (pred.dtype not in _SEG_PRED_CODES or label.dtype not in _SEG_LABEL_CODES or not 0 < K <= SEG_HIST_MAX_CLASSES
+            or not 0 < H * W < 2 ** 31 - 8 or abs(int(ignore_index)) >= 2 ** 31):
+        fallback("seg_confusion", f"pred {pred.dtype}, label {label.dtype}, K {K}, {H} x {W}")
+        return _seg_confusion_torch(pred, label, matrix, int(ignore_index), bool(reduce_zero_label))
+    pred = pred.contiguous()
+    flags = int(bool(reduce_zero_label)) | (_SEG_CONF_GLOBAL if route == "global" else 0)
+    check(lib.s2f_seg_confusion(_ptr(pred), _SEG_PRED_CODES[pred.dtype], _ptr(label), _SEG_LABEL_CODES[label.dtype], label.stride(0),
+                                label.stride(1), W, H * W, K, int(ignore_index), flags, _ptr(matrix), _stream()),
+          "s2f_seg_confusion")
+    return matrix
+
+
 # ------------------------------------------------------------------------------------------------ mask losses (row f1)
 class _MaskLossSums(torch.autograd.Function):
     """sums[p] = {sum s t, sum s, sum t, sum focal} over the 2x up-sampled logits of matched prediction p against its binary
