@@ -12,28 +12,99 @@ graph (ops.resplit_all, one launch over a pointer table), so each replay multipl
 step or load_state_dict between replays is honoured, forward and backward stay consistent
 (tests/test_gpu_full_size.py::test_graph_replay_follows_weight_updates).  Weights that enter the model only after the
 capture (none on this path) would need a new capture.
+
+Every step class below is a `_Captured`: the capture protocol (`_capture`) and the replay prologue / epilogue (`_begin`,
+`_end`) are written there once; a class says which warm-up pass it runs, which stages it records and what lies between them.
 """
+import contextlib
+
 import torch
 
 from . import ops
 from .neuron import reset_net
 
 
-def _check_settings(captured):
-    """A captured hipGraph bakes in the launch structure the op-layer switches selected at capture time (ops.cfg): replaying it
-    under different settings would mix two configurations silently -- e.g. eager steps of a comparison running with a switch
-    flipped while the graph still replays the old kernels."""
-    now = ops.cfg.snapshot()
-    if now != captured:
-        diff = {k: (captured[k], now[k]) for k in now if now[k] != captured.get(k)}
-        raise RuntimeError(f"this hipGraph was captured under different op-layer settings (captured, now): {diff}; re-capture")
+def _process_group():
+    import torch.distributed as dist
+    return dist.is_available() and dist.is_initialized()
 
 
-class GraphedStep:
+class _Captured:
+    """A step with static input `static_in`, recorded as one hipGraph per stage.  `red`: the flat gradient buffer
+    (dist.FlatGradAllReduce) of the steps that pack into one; `optimizer`: a train.FlatAdamW captured behind the packing."""
+    optimizer = None
+
+    def _capture(self, warm, warmup, stages, context=None):
+        """`warmup` calls of `warm` on a side stream (allocator pools, lazy inits, caches), then each callable of `stages`
+        recorded into a hipGraph of its own -> the graphs, in that order.  `context`: a context manager factory that changes
+        the launch structure; every stage is recorded under it, after one more warm-up pass under it."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                warm()
+            if context is not None:
+                with context():
+                    warm()
+        torch.cuda.current_stream().wait_stream(side)
+        # Warm-up gradients are not packed: drop their deferred launches.  A pass that ends without ops.wgrad_join() leaves
+        # them queued, and inside a capture the drop of `red.zero()` is a no-op: the recorded join would launch them into the
+        # graph, over warm-up tensors that are freed by the time it replays.
+        ops.wgrad_drop()
+        ops.resplit_all(self.static_in.device)          # builds the weight-split job table the captured step replays
+        torch.cuda.synchronize()
+        # With a process group alive, RCCL's watchdog thread polls its events while this thread captures: "thread_local"
+        # keeps its (legal, uncaptured) calls from invalidating the capture; single-process runs keep the strict default.
+        mode = "thread_local" if _process_group() else "global"
+        pool = torch.cuda.graph_pool_handle() if len(stages) > 1 else None          # a later stage reads an earlier one's tensors
+        graphs = [torch.cuda.CUDAGraph() for _ in stages]
+        for graph, stage in zip(graphs, stages):
+            with torch.cuda.graph(graph, pool=pool, capture_error_mode=mode), (context or contextlib.nullcontext)():
+                stage()
+        torch.cuda.synchronize()
+        # the graphs bake in the addresses of the conversion job tables and of every cached split / pack buffer: hold them (an
+        # eager forward after an optimiser step re-converts INTO the same buffers, ops._cache_buffer, and replaces tables)
+        self._converted = ops.conversion_state()
+        # ... and the launch structure the op-layer switches selected (ops.cfg): see _begin
+        self._settings = ops.cfg.snapshot()
+        return graphs
+
+    def _begin(self, x):
+        """Before a replay.  Replaying under other op-layer settings than the captured ones would mix two configurations
+        silently -- e.g. eager steps of a comparison running with a switch flipped while the graph still replays the old
+        kernels.  The optimizer's per-parameter (lr, weight_decay) table is uploaded (a scheduler may have rewritten it)."""
+        now = ops.cfg.snapshot()
+        if now != self._settings:
+            diff = {k: (self._settings[k], now[k]) for k in now if now[k] != self._settings.get(k)}
+            raise RuntimeError(f"this hipGraph was captured under different op-layer settings (captured, now): {diff}; re-capture")
+        if x is not None:
+            self.static_in.copy_(x, non_blocking=True)
+        if self.optimizer is not None:
+            self.optimizer.sync_hyper()
+
+    def _end(self):
+        """After the last replay of a step.  A replayed update changed every weight after this replay's own re-split ran (at
+        its START): the version-keyed conversion caches now hold the terms of the weights BEFORE the update under unchanged
+        version counters -- an eager forward (validation, predict(), export) would multiply by one-step-stale bf16 terms.
+        Bump the versions."""
+        if self.optimizer is not None:
+            self.optimizer.mark_updated()
+
+    def _forward(self):
+        reset_net(self.model)
+        self.red.zero()
+        return tuple(self.model(self.static_in))
+
+    def _grads(self, outputs, grad_outputs=None):
+        grads = torch.autograd.grad(outputs, self.red.params, grad_outputs, allow_unused=True)
+        ops.wgrad_join()                  # side-stream (ops.WGRAD_STREAM) and deferred weight gradients are in their sinks
+        return grads
+
+
+class GraphedStep(_Captured):
     """`optimizer` (train.FlatAdamW over `grad_buffer`): the parameter update -- clip + AdamW, three launches -- is captured behind
     the gradient packing, so one replay is one training ITERATION (single process; with N > 1 the all-reduce sits between the step
-    and the update, which the caller then runs eagerly: `step(); grad_buffer.reduce(); optimizer.step()`).  Its per-parameter
-    (lr, weight_decay) table is uploaded before every replay (a scheduler may have rewritten it)."""
+    and the update, which the caller then runs eagerly: `step(); grad_buffer.reduce(); optimizer.step()`)."""
 
     def __init__(self, model, loss_fn, example_input, grad_buffer=None, warmup=3, optimizer=None):
         self.model, self.loss_fn = model, loss_fn
@@ -42,32 +113,12 @@ class GraphedStep:
         self.optimizer = optimizer
         if optimizer is not None:
             optimizer.sync_hyper()
-        self.graph = torch.cuda.CUDAGraph()
-        self.static_loss = None
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                  # warm-up on a side stream (allocator pools, lazy inits, caches)
-            for _ in range(warmup):
-                self._eager_step()
-        if ops.GLUE_MODE:                              # one more warm-up on the launch structure that is captured (ops.GlueMode)
-            with torch.cuda.stream(side), ops.glue_mode():
-                self._eager_step()
-        torch.cuda.current_stream().wait_stream(side)
-        ops.resplit_all(self.static_in.device)          # builds the weight-split job table the captured step replays
-        torch.cuda.synchronize()
-        # With a process group alive, RCCL's watchdog thread polls its events while this thread captures: "thread_local"
-        # keeps its (legal, uncaptured) calls from invalidating the capture; single-process runs keep the strict default.
-        import torch.distributed as dist
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
+
+        def record():
+            self.static_loss = self._eager_step()
         # ops.GLUE_MODE: the residual aten calls of the step (autograd's gradient accumulation, scalar multiples, copies, fills, small
         # sums) are routed to csrc/glue.hip while the step is RECORDED -- the replay then consists of this package's kernels only
-        with torch.cuda.graph(self.graph, capture_error_mode=mode), ops.glue_mode():
-            self.static_loss = self._eager_step()
-        torch.cuda.synchronize()
-        # the graph bakes in the addresses of the conversion job tables and of every cached split / pack buffer: hold them (an
-        # eager forward after an optimiser step re-converts INTO the same buffers, ops._cache_buffer, and replaces tables)
-        self._converted = ops.conversion_state()
-        self._settings = ops.cfg.snapshot()
+        self.graph, = self._capture(self._eager_step, warmup, [record], context=ops.glue_mode if ops.GLUE_MODE else None)
 
     def _eager_step(self):
         reset_net(self.model)
@@ -87,21 +138,13 @@ class GraphedStep:
         return loss.detach()
 
     def __call__(self, x=None):
-        _check_settings(self._settings)
-        if x is not None:
-            self.static_in.copy_(x, non_blocking=True)
-        if self.optimizer is not None:
-            self.optimizer.sync_hyper()
+        self._begin(x)
         self.graph.replay()
-        if self.optimizer is not None:
-            # the replayed update changed every weight after this replay's own re-split ran (at its START): the version-keyed
-            # conversion caches now hold the terms of the weights BEFORE the update under unchanged version counters -- an eager
-            # forward (validation, predict(), export) would multiply by one-step-stale bf16 terms.  Bump the versions.
-            self.optimizer.mark_updated()
+        self._end()
         return self.static_loss
 
 
-class GraphedSplitStep:
+class GraphedSplitStep(_Captured):
     """The training step with a loss that needs the host in the middle (the Hungarian assignment):
     TWO hipGraphs around an eager loss --
         graph A : membrane reset + gradient-buffer clear + model forward           (autograd recorded once, at capture)
@@ -116,41 +159,23 @@ class GraphedSplitStep:
     def __init__(self, model, example_input, grad_buffer, warmup=3):
         self.model, self.red = model, grad_buffer
         self.static_in = example_input.clone()
-        params = [p for p in grad_buffer.params]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                outs = self._forward()
-                torch.autograd.grad(outs, params, [torch.ones_like(o) for o in outs], allow_unused=True)
-        torch.cuda.current_stream().wait_stream(side)
-        ops.resplit_all(self.static_in.device)          # builds the weight-split job table graph A replays
-        torch.cuda.synchronize()
-        import torch.distributed as dist
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        pool = torch.cuda.graph_pool_handle()
-        with torch.cuda.graph(self.graph_a, pool=pool, capture_error_mode=mode):
-            self.outs = self._forward()
-        self.grad_outs = [torch.zeros_like(o) for o in self.outs]
-        with torch.cuda.graph(self.graph_b, pool=pool, capture_error_mode=mode):
-            grads = torch.autograd.grad(self.outs, params, self.grad_outs, allow_unused=True)
-            ops.wgrad_join()
-            self.red.pack(grads)
-        torch.cuda.synchronize()
-        self._converted = ops.conversion_state()
-        self._settings = ops.cfg.snapshot()          # see GraphedStep
 
-    def _forward(self):
-        reset_net(self.model)
-        self.red.zero()
-        return tuple(self.model(self.static_in))
+        def warm():
+            outs = self._forward()
+            self._grads(outs, [torch.ones_like(o) for o in outs])
+
+        def graph_a():
+            self.outs = self._forward()
+
+        def graph_b():
+            # static inputs of this graph, from its pool (an allocation, no launch): backward() fills every one before a replay
+            self.grad_outs = [torch.empty_like(o) for o in self.outs]
+            self.red.pack(self._grads(self.outs, self.grad_outs))
+        self.graph_a, self.graph_b = self._capture(warm, warmup, [graph_a, graph_b])
 
     def forward(self, x=None):
         """-> the model outputs (static tensors, valid until the next forward), detached leaves that require grad."""
-        _check_settings(self._settings)
-        if x is not None:
-            self.static_in.copy_(x, non_blocking=True)
+        self._begin(x)
         self.graph_a.replay()
         return [o.detach().requires_grad_(True) for o in self.outs]
 
@@ -164,7 +189,7 @@ class GraphedSplitStep:
         self.graph_b.replay()
 
 
-class GraphedHungarianStep:
+class GraphedHungarianStep(_Captured):
     """The REAL training step (Hungarian-matched loss on semantic maps) as two hipGraphs around the one
     thing that has to happen on the host, the assignment:
         graph A : membrane reset + gradient-buffer clear + model forward + matching costs against every class id
@@ -172,7 +197,7 @@ class GraphedHungarianStep:
         host    : scipy linear_sum_assignment per (layer, image) on the columns of the classes present -> three small tables
                   (loss.MaskFormerLoss.match_tables), uploaded into static device buffers
         graph B : the losses from the tables (loss_from_tables: every shape is independent of the matching) + backward of the
-                  whole model + packing of the gradients into the flat buffer
+                  whole model + packing of the gradients into the flat buffer (+ `optimizer`'s update, see GraphedStep)
     Between the graphs the GPU idles for the copy, the assignment and one upload -- not for ~450 eager launches of the loss and
     its backward as with GraphedSplitStep.  `__call__` returns the loss dictionary (static tensors, valid until the next call).
 
@@ -197,133 +222,102 @@ class GraphedHungarianStep:
                                "has no host fall-back")
         self.assign = assign
         head = model.decode_head
-        self.optimizer = optimizer          # train.FlatAdamW: captured at the end of graph B (single process; see GraphedStep)
+        self.optimizer = optimizer
         if optimizer is not None:
             optimizer.sync_hyper()
         self.model, self.red, self.crit = model, grad_buffer, head.criterion
         self.ignore_index = head.ignore_index if ignore_index is None else ignore_index
         self.static_in = example_input.clone()
         self.static_seg = self.crit.seg_as_u8(example_seg, self.ignore_index).clone()
-        params = [p for p in grad_buffer.params]
         dev = example_input.device
         with torch.no_grad():                                     # shapes of the outputs (and a first warm-up)
             cls, masks = self._forward()
         if not self.crit.semantic_ok(masks, self.static_seg):
             raise RuntimeError("GraphedHungarianStep needs semantic maps at twice the mask predictions' resolution")
         L, B, Q = cls.shape[:3]
+        del cls, masks
         self.tgt_labels = torch.full((L, B, Q), self.crit.num_classes, dtype=torch.int64, device=dev)
         self.row_class = torch.full((B, L * Q), -1, dtype=torch.int32, device=dev)
         self.num_masks = torch.ones(L, dtype=torch.float32, device=dev)
-        if assign == "device":
-            del cls, masks
-            self._capture_device(params, dev, warmup)
-            return
-        self.host_cost = torch.empty(L, B, Q, self.crit.num_classes, dtype=torch.float32).pin_memory()
-        self.host_count = torch.empty(B, 256, dtype=torch.float32).pin_memory()
-        self.host_tgt, self.host_rows, self.host_avg = (torch.empty(t.shape, dtype=t.dtype).pin_memory()
-                                                        for t in (self.tgt_labels, self.row_class, self.num_masks))
-        del cls, masks
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                outs = self._forward()
-                self._costs(outs)
-                side.synchronize()
-                self._match()
-                total = sum(self._losses(outs).values())
-                torch.autograd.grad(total, params, allow_unused=True)
-                ops.wgrad_join()
-                del outs, total
-        torch.cuda.current_stream().wait_stream(side)
-        ops.wgrad_drop()                                 # warm-up gradients are not packed: drop their deferred launches
-        ops.resplit_all(dev)
-        torch.cuda.synchronize()
-        import torch.distributed as dist
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        pool = torch.cuda.graph_pool_handle()
-        with torch.cuda.graph(self.graph_a, pool=pool, capture_error_mode=mode):
+        if assign == "device":                                    # no pinned cost buffer: a status word instead
+            self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.sticky = torch.zeros(1, dtype=torch.int32, device=dev)          # OR of the status words since the last raise
+            self.host_status = torch.zeros(1, dtype=torch.int32).pin_memory()
+        else:
+            self.host_cost = torch.empty(L, B, Q, self.crit.num_classes, dtype=torch.float32).pin_memory()
+            self.host_count = torch.empty(B, 256, dtype=torch.float32).pin_memory()
+            self.host_tgt, self.host_rows, self.host_avg = (torch.empty(t.shape, dtype=t.dtype).pin_memory()
+                                                            for t in (self.tgt_labels, self.row_class, self.num_masks))
+        self.two_graphs = assign == "host" or _process_group()
+
+        def warm():
+            outs = self._forward()
+            self._costs(outs)
+            self._assign()
+            self._grads(sum(self._losses(outs).values()))
+
+        def head():
             self.outs = self._forward()
             self._costs(self.outs)
-        with torch.cuda.graph(self.graph_b, pool=pool, capture_error_mode=mode):
+
+        def tail():
             losses = self._losses(self.outs)
-            grads = torch.autograd.grad(sum(losses.values()), params, allow_unused=True)
-            ops.wgrad_join()
-            self.red.pack(grads)
+            self.red.pack(self._grads(sum(losses.values())))
             if self.optimizer is not None:
                 self.optimizer.step(sync_hyper=False)
             self.losses = {k: v.detach() for k, v in losses.items()}
-        torch.cuda.synchronize()
-        self._converted = ops.conversion_state()
-        self._settings = ops.cfg.snapshot()          # see GraphedStep
+            if assign == "device":
+                self.sticky.bitwise_or_(self.status)
+                self.host_status.copy_(self.sticky, non_blocking=True)
 
-    def _capture_device(self, params, dev, warmup):
-        """assign="device": one graph (single process) or graph A | all-reduce | graph B (process group); no pinned cost buffer"""
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.sticky = torch.zeros(1, dtype=torch.int32, device=dev)          # OR of the status words since the last raise
-        self.host_status = torch.zeros(1, dtype=torch.int32).pin_memory()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                outs = self._forward()
-                self._tables(outs)
-                self._reduce_num_masks()
-                total = sum(self._losses(outs).values())
-                torch.autograd.grad(total, params, allow_unused=True)
-                ops.wgrad_join()
-                del outs, total
-        torch.cuda.current_stream().wait_stream(side)
-        ops.wgrad_drop()                                 # warm-up gradients are not packed: drop their deferred launches
-        ops.resplit_all(dev)
-        torch.cuda.synchronize()
-        import torch.distributed as dist
-        self.two_graphs = dist.is_available() and dist.is_initialized()
-        mode = "thread_local" if self.two_graphs else "global"
+        def whole():
+            head()
+            tail()
+        self._graphs = self._capture(warm, warmup, [head, tail] if self.two_graphs else [whole])
+        for name, graph in zip(("graph", "graph_tail") if assign == "device" else ("graph_a", "graph_b"), self._graphs):
+            setattr(self, name, graph)
+        if assign == "device":
+            self.sticky.zero_()                              # (whatever the warm-up on the example inputs left is not a replay's)
+            torch.cuda.synchronize()
+            self.host_status.zero_()
 
-        def tail(outs):
-            losses = self._losses(outs)
-            grads = torch.autograd.grad(sum(losses.values()), params, allow_unused=True)
-            ops.wgrad_join()
-            self.red.pack(grads)
-            if self.optimizer is not None:
-                self.optimizer.step(sync_hyper=False)
-            self.losses = {k: v.detach() for k, v in losses.items()}
-            self.sticky.bitwise_or_(self.status)
-            self.host_status.copy_(self.sticky, non_blocking=True)
-
-        self.graph = torch.cuda.CUDAGraph()
-        if self.two_graphs:
-            self.graph_tail = torch.cuda.CUDAGraph()
-            pool = torch.cuda.graph_pool_handle()
-            with torch.cuda.graph(self.graph, pool=pool, capture_error_mode=mode):
-                self.outs = self._forward()
-                self._tables(self.outs)
-            with torch.cuda.graph(self.graph_tail, pool=pool, capture_error_mode=mode):
-                tail(self.outs)
-        else:
-            with torch.cuda.graph(self.graph, capture_error_mode=mode):
-                self.outs = self._forward()
-                self._tables(self.outs)
-                tail(self.outs)
-        torch.cuda.synchronize()
-        self.sticky.zero_()                              # (whatever the warm-up on the example inputs left is not a replay's)
-        torch.cuda.synchronize()
-        self.host_status.zero_()
-        self._converted = ops.conversion_state()
-        self._settings = ops.cfg.snapshot()          # see GraphedStep
-
-    def _tables(self, outs):
-        """costs + device assignment into the static tables (and the status word)"""
+    def _costs(self, outs):
+        """matching costs against every class id -> host: pinned memory, for _match; device: the assignment kernel, into the
+        static tables (and the status word)"""
         with torch.no_grad():
             cost, count = self.crit.costs_all_classes(outs[0], outs[1], self.static_seg)
-            self.crit.match_tables_device(cost, count, out=(self.tgt_labels, self.row_class, self.num_masks, self.status))
+            if self.assign == "device":
+                self.crit.match_tables_device(cost, count, out=(self.tgt_labels, self.row_class, self.num_masks, self.status))
+            else:
+                self.host_cost.copy_(cost, non_blocking=True)
+                self.host_count.copy_(count, non_blocking=True)
+
+    def _assign(self):
+        """what lies between the two graphs (in the one-graph form: nothing, there is no process group)"""
+        if self.assign == "device":
+            self._reduce_num_masks()
+        else:
+            torch.cuda.current_stream().synchronize()
+            self._match()
+
+    def _match(self):
+        """host_cost / host_count (complete: the stream was synchronised) -> the three device tables."""
+        tgt, rows, avg = self.crit.match_tables(self.host_cost.numpy(), self.host_count.numpy())
+        self.host_tgt.copy_(torch.from_numpy(tgt))
+        self.host_rows.copy_(torch.from_numpy(rows))
+        self.host_avg.copy_(torch.from_numpy(avg))
+        self.tgt_labels.copy_(self.host_tgt, non_blocking=True)
+        self.row_class.copy_(self.host_rows, non_blocking=True)
+        self.num_masks.copy_(self.host_avg, non_blocking=True)
+        self._reduce_num_masks()
 
     def _reduce_num_masks(self):
         import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if _process_group() and dist.get_world_size() > 1:
             dist.all_reduce(self.num_masks.div_(dist.get_world_size()))          # reduce_mean (maskformer_head.py:459)
+
+    def _losses(self, outs):
+        return self.crit.loss_from_tables(outs[0], outs[1], self.static_seg, self.tgt_labels, self.row_class, self.num_masks)
 
     def _raise_for(self, word):
         if word:
@@ -341,61 +335,21 @@ class GraphedHungarianStep:
             torch.cuda.current_stream().synchronize()
             self._raise_for(int(self.host_status[0]))
 
-    def _forward(self):
-        reset_net(self.model)
-        self.red.zero()
-        return tuple(self.model(self.static_in))
-
-    def _costs(self, outs):
-        with torch.no_grad():
-            cost, count = self.crit.costs_all_classes(outs[0], outs[1], self.static_seg)
-            self.host_cost.copy_(cost, non_blocking=True)
-            self.host_count.copy_(count, non_blocking=True)
-
-    def _match(self):
-        """host_cost / host_count (complete: the stream was synchronised) -> the three device tables."""
-        tgt, rows, avg = self.crit.match_tables(self.host_cost.numpy(), self.host_count.numpy())
-        self.host_tgt.copy_(torch.from_numpy(tgt))
-        self.host_rows.copy_(torch.from_numpy(rows))
-        self.host_avg.copy_(torch.from_numpy(avg))
-        self.tgt_labels.copy_(self.host_tgt, non_blocking=True)
-        self.row_class.copy_(self.host_rows, non_blocking=True)
-        self.num_masks.copy_(self.host_avg, non_blocking=True)
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            dist.all_reduce(self.num_masks.div_(dist.get_world_size()))          # reduce_mean (maskformer_head.py:459)
-
-    def _losses(self, outs):
-        return self.crit.loss_from_tables(outs[0], outs[1], self.static_seg, self.tgt_labels, self.row_class, self.num_masks)
-
     def __call__(self, x=None, seg=None):
-        _check_settings(self._settings)
         if self.assign == "device":
             self._raise_for(int(self.host_status[0]))          # the word of an earlier replay, if it has landed; no wait
-        if x is not None:
-            self.static_in.copy_(x, non_blocking=True)
+        self._begin(x)
         if seg is not None:
             self.static_seg.copy_(self.crit.seg_as_u8(seg, self.ignore_index), non_blocking=True)
-        if self.optimizer is not None:
-            self.optimizer.sync_hyper()
-        if self.assign == "device":
-            self.graph.replay()
-            if self.two_graphs:
-                self._reduce_num_masks()
-                self.graph_tail.replay()
-            if self.optimizer is not None:
-                self.optimizer.mark_updated()
-            return self.losses
-        self.graph_a.replay()
-        torch.cuda.current_stream().synchronize()
-        self._match()
-        self.graph_b.replay()
-        if self.optimizer is not None:
-            self.optimizer.mark_updated()          # see GraphedStep.__call__
+        self._graphs[0].replay()
+        if self.two_graphs:
+            self._assign()
+            self._graphs[1].replay()
+        self._end()
         return self.losses
 
 
-class GraphedOverlapStep:
+class GraphedOverlapStep(_Captured):
     """BENCHMARK-ONLY (no weight update between steps): forward(k+1) replays before all-reduce(k) has finished, so an optimiser
     could not apply the averaged gradients of step k before step k+1 reads (and re-splits) the weights -- with an optimiser in the
     loop this would be one-step-stale data parallelism, not the reference's synchronous MMDistributedDataParallel step.  The
@@ -412,42 +366,26 @@ class GraphedOverlapStep:
     def __init__(self, model, loss_fn, example_input, grad_buffer, warmup=3, buckets=1):
         self.model, self.loss_fn, self.red, self.buckets = model, loss_fn, grad_buffer, buckets
         self.static_in = example_input.clone()
-        params = [p for p in grad_buffer.params]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                loss = self._forward()
-                grad_buffer.zero()
-                torch.autograd.grad([loss], params, allow_unused=True)
-                ops.wgrad_join()
-        torch.cuda.current_stream().wait_stream(side)
-        ops.wgrad_drop()                                 # warm-up gradients are not packed: drop their deferred launches
-        ops.resplit_all(self.static_in.device)
-        torch.cuda.synchronize()
-        import torch.distributed as dist
-        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-        self.graph_f, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        pool = torch.cuda.graph_pool_handle()
-        with torch.cuda.graph(self.graph_f, pool=pool, capture_error_mode=mode):
-            self.loss = self._forward()
-        with torch.cuda.graph(self.graph_b, pool=pool, capture_error_mode=mode):
+
+        def warm():
+            loss = self._forward()
             self.red.zero()
-            grads = torch.autograd.grad([self.loss], params, allow_unused=True)
-            ops.wgrad_join()
-            self.red.pack(grads)
-        torch.cuda.synchronize()
-        self._converted = ops.conversion_state()
-        self._settings = ops.cfg.snapshot()          # see GraphedStep
+            self._grads([loss])
+
+        def graph_f():
+            self.loss = self._forward()
+
+        def graph_b():
+            self.red.zero()
+            self.red.pack(self._grads([self.loss]))
+        self.graph_f, self.graph_b = self._capture(warm, warmup, [graph_f, graph_b])
 
     def _forward(self):
         reset_net(self.model)
         return self.loss_fn(*self.model(self.static_in))
 
     def __call__(self, x=None):
-        _check_settings(self._settings)
-        if x is not None:
-            self.static_in.copy_(x, non_blocking=True)
+        self._begin(x)
         self.graph_f.replay()                 # runs under the previous step's all-reduce
         self.red.wait()                       # ... which must be done before the buffer is cleared
         self.graph_b.replay()

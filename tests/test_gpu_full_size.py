@@ -603,14 +603,12 @@ def test_overlap_step_is_the_single_graph_step():
         red.close()
 
 
-def test_tiny_split_graph_step_with_the_hungarian_loss_is_the_eager_step():
-    """graph.GraphedSplitStep (forward graph | eager Hungarian-matched loss | backward graph) against the eager
-    `mode="loss"` step on the tiny config: same loss values bit for bit, same gradients (flat buffer) to the run-to-run
-    noise of the split-K atomics."""
+def _split_graph_step_is_the_eager_step(sinks):
     import spike2former_amd as s2f
     from spike2former_amd.dist import FlatGradAllReduce
     from spike2former_amd.graph import GraphedSplitStep
     from spike2former_amd.init_utils import seeded_init
+    from spike2former_amd.ops import core
     w = s2f.WORKLOADS["C1_64"]
     model = seeded_init(s2f.MODELS.build(s2f.model_cfg("C1_64"))).cuda().train()
     sd = {k: v.clone() for k, v in model.state_dict().items()}
@@ -619,33 +617,54 @@ def test_tiny_split_graph_step_with_the_hungarian_loss_is_the_eager_step():
     seg = _region_maps(2, w["H"], w["W"], w["K"], 6, 6).cuda()
     gts = [s2f.seg_to_instances(seg[i]) for i in range(2)]
     red = FlatGradAllReduce(model.parameters(), 1)
+    if sinks:
+        red.install_sinks()
+    try:
+        model.load_state_dict(sd); s2f.reset_net(model); red.zero()
+        losses = model(img, [seg[i] for i in range(2)], mode="loss")     # the semantic-map path (loss.MaskFormerLoss.loss_semantic)
+        sum(losses.values()).backward()
+        # with sinks the short-contraction weight gradients (32x32 / 64x64 stages, 100-token decoder layers) wait for gather()
+        assert bool(sum(map(len, core._DW_PENDING.values())) + len(core._DWG_PENDING)) == sinks
+        red.gather()
+        want_loss = {k: float(v) for k, v in losses.items()}
+        want = red.flat.clone()
+        del losses                                            # no autograd graph of the eager step may outlive this point
+        for p in model.parameters():
+            p.grad = None
+        import gc
+        gc.collect()
 
-    model.load_state_dict(sd); s2f.reset_net(model); red.zero()
-    losses = model(img, [seg[i] for i in range(2)], mode="loss")     # the semantic-map path (loss.MaskFormerLoss.loss_semantic)
-    sum(losses.values()).backward()
-    red.gather()
-    want_loss = {k: float(v) for k, v in losses.items()}
-    want = red.flat.clone()
-    del losses                                            # no autograd graph of the eager step may outlive this point
-    for p in model.parameters():
-        p.grad = None
-    import gc
-    gc.collect()
-
-    model.load_state_dict(sd)
-    step = GraphedSplitStep(model, img, red, warmup=1)
-    for _ in range(2):                                    # replayed twice: the second replay must not depend on the first
         model.load_state_dict(sd)
-        leaves = step.forward()
-        got = model.decode_head.loss_by_feat(leaves[0], leaves[1], gts)
-        sum(got.values()).backward()
-        step.backward(leaves)
-        torch.cuda.synchronize()
-        # eager step: label-map kernels; here: the generic instance-mask path -- the same numbers to fp32 round-off
-        assert list(got.keys()) == list(want_loss.keys())
-        assert all(abs(float(v) - want_loss[k]) <= 1e-5 * max(abs(want_loss[k]), 1e-3) for k, v in got.items())
-        scale = want.abs().max().item()
-        assert (red.flat - want).abs().max().item() <= 1e-4 * scale
+        step = GraphedSplitStep(model, img, red, warmup=1)
+        for _ in range(2):                                    # replayed twice: the second replay must not depend on the first
+            model.load_state_dict(sd)
+            leaves = step.forward()
+            got = model.decode_head.loss_by_feat(leaves[0], leaves[1], gts)
+            sum(got.values()).backward()
+            step.backward(leaves)
+            torch.cuda.synchronize()
+            # eager step: label-map kernels; here: the generic instance-mask path -- the same numbers to fp32 round-off
+            assert list(got.keys()) == list(want_loss.keys())
+            assert all(abs(float(v) - want_loss[k]) <= 1e-5 * max(abs(want_loss[k]), 1e-3) for k, v in got.items())
+            scale = want.abs().max().item()
+            assert (red.flat - want).abs().max().item() <= 1e-4 * scale
+    finally:
+        red.close()
+
+
+def test_tiny_split_graph_step_with_the_hungarian_loss_is_the_eager_step():
+    """graph.GraphedSplitStep (forward graph | eager Hungarian-matched loss | backward graph) against the eager
+    `mode="loss"` step on the tiny config: same loss values bit for bit, same gradients (flat buffer) to the run-to-run
+    noise of the split-K atomics."""
+    _split_graph_step_is_the_eager_step(sinks=False)
+
+
+def test_tiny_split_graph_step_with_gradient_sinks_is_the_eager_step():
+    """The same with gradient sinks installed (as bench.py builds its buffer): the eager step and the warm-up pass of the
+    capture then DEFER their short-contraction weight gradients.  What the warm-up left queued must not be launched by the
+    join that graph B records: those launches would read tensors of the warm-up, freed by the time the graph replays, and
+    add a second share into the sinks."""
+    _split_graph_step_is_the_eager_step(sinks=True)
 
 
 def _region_maps(B, H, W, K, n, seed):
