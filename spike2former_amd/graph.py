@@ -63,7 +63,7 @@ class _Captured:
                 stage()
         torch.cuda.synchronize()
         # the graphs bake in the addresses of the conversion job tables and of every cached split / pack buffer: hold them (an
-        # eager forward after an optimiser step re-converts INTO the same buffers, ops._cache_buffer, and replaces tables)
+        # eager forward after an optimiser step re-converts INTO the same buffers, ops/wcache.py, and replaces tables)
         self._converted = ops.conversion_state()
         # ... and the launch structure the op-layer switches selected (ops.cfg): see _begin
         self._settings = ops.cfg.snapshot()

@@ -4,6 +4,7 @@ import torch
 from .config import cfg
 from .core import *          # noqa: F401,F403  (the shared plumbing: _ptr, _stream, check, lib, Spikes, ...)
 from .gemm import *          # noqa: F401,F403
+from .wcache import pack_weight, pack_weight_conv3, split_weight, split_weight_conv3, split_weight_tconv3
 
 
 # ------------------------------------------------------------------------------------------------ depthwise conv
@@ -88,15 +89,18 @@ def dwconv(x, w, pad, border=None, stats=False):
     """x: fp32 tensor or Spikes.  stats: the consumer is a train-mode BatchNorm -- where the stencil can (3 x 3, pad 1, no border,
     cfg.BN_PARTIALS) it stores the BatchNorm partials with y and hands them over as y's `_s2f_part` (gemm.stats_of)"""
     data, tok = _unpack(x)
-    y, part = _DWConv.apply(data, tok, w, border, pad, bool(stats))
-    if part.numel():
-        y._s2f_part = (part, y._version, y.data_ptr())
-    return y
+    return _with_part(*_DWConv.apply(data, tok, w, border, pad, bool(stats)))
 
 
 
 
 # ------------------------------------------------------------------------------------------------ dense k x k convolution
+# 3x3 / stride 1 / pad 1 spike convolutions as implicit GEMMs (no im2col matrix; s2f_spike_conv3x3_fwd / _dw).  Round 1 measured
+# the pair (forward + weight gradient) as a win on the >= 128x128 maps only (tools/probe_conv3.py: 64x64 maps 485 vs 420 and
+# 795 vs 660 us against the saved column matrix).  With the loaders' prefetches freed of their predicates (round 2, conv3_fix)
+# the implicit form wins from 32x32 up -- same-box A/B of the step: threshold 128x128 43.92, 64x64 43.39, 32x32 43.44 ms -- and
+# the bf16 column matrices of the 64x64 / 32x32 stages (ATen im2col) are gone.
+# Input gradient of the 3x3 convolutions: an implicit transposed convolution on the 6-pass split GEMM (no unfold / col2im).
 def im2col(x, kh, kw, stride, padding):
     """torch.nn.functional.unfold(x, (kh, kw), 1, padding, stride) for fp32 maps and bf16 spike maps, as one gather kernel
     (csrc/im2col.hip): [N, C, H, W] -> [N, C kh kw, Ho Wo], the column matrix of the reference's stride-2 / 7x7 nn.Conv2d

@@ -49,19 +49,8 @@ _ARENA_DOUBLES = 1 << 20
 
 
 def begin_step(device=None):
-    # a step that is being captured into a hipGraph re-splits every weight first (one launch, recorded in the graph): the
-    # replays then read the live fp32 weights instead of the bf16 terms of capture time
-    from . import gemm as _g          # (the weight-conversion caches live with the GEMM ops)
-    _g._TRUST_ALL[0] = False
-    if device is not None and torch.cuda.is_current_stream_capturing() and cfg.RESPLIT_IN_GRAPH:
-        n = _g.resplit_all(device, build=False)
-        if n > 0:
-            _g._TRUST_ALL[0] = True
-        elif n < 0:
-            # no job table for the current set of weights: forget every cached version instead, so that each weight is
-            # re-split by its own launch inside this capture (correct, ~180 launches more per replay)
-            for k, v in list(_g._SPLIT_CACHE.items()):
-                _g._SPLIT_CACHE[k] = (None,) + tuple(v[1:])
+    from . import wcache          # (imports this module)
+    wcache.step_begins(device)        # a step that is being captured re-converts every weight first
     a = _ARENA
     if a["buf"] is None:
         if device is None:

@@ -1,10 +1,11 @@
-"""GEMM-shaped ops: the packed-weight spike GEMMs and their gradients (csrc/pgemm.hip, gemm.hip, gemm_bf16.hip), the weight
-conversion caches, dense-input products, token-major nn.Linear, the mask contraction."""
+"""GEMM-shaped ops: the packed-weight spike GEMMs and their gradients (csrc/pgemm.hip, gemm.hip, gemm_bf16.hip), dense-input
+products, token-major nn.Linear, the mask contraction.  The converted weights they multiply by come from ops/wcache.py."""
 import torch
 
 from .config import cfg
 from .core import *          # noqa: F401,F403  (the shared plumbing: _ptr, _stream, check, lib, Spikes, ...)
 from .misc import channel_sum, transpose_last2
+from .wcache import pack_weight, pack_weight_conv3, split_weight          # the cached bf16 conversions of the weights
 
 
 # ------------------------------------------------------------------------------------------------ small / ragged products
@@ -144,26 +145,12 @@ def dense_gemm(x, w, stats=False):
 
 
 
-# ------------------------------------------------------------------------------------------------ spike GEMM (bf16 MFMA)
-_SPLIT_CACHE = {}
-# 3x3 / stride 1 / pad 1 spike convolutions as implicit GEMMs (no im2col matrix; s2f_spike_conv3x3_fwd / _dw).  Round 1 measured
-# the pair (forward + weight gradient) as a win on the >= 128x128 maps only (tools/probe_conv3.py: 64x64 maps 485 vs 420 and
-# 795 vs 660 us against the saved column matrix).  With the loaders' prefetches freed of their predicates (round 2, conv3_fix)
-# the implicit form wins from 32x32 up -- same-box A/B of the step: threshold 128x128 43.92, 64x64 43.39, 32x32 43.44 ms -- and
-# the bf16 column matrices of the 64x64 / 32x32 stages (ATen im2col) are gone.
-# input gradient of the 3x3 convolutions as an implicit transposed convolution on the 6-pass split GEMM (no unfold / col2im)
-# Round 3: the LDS-DMA pipelined kernels (csrc/pgemm.hip): forward spike GEMMs on s2f_pgemm_nn_bf16 (packed weight, bf16
-# spikes, any N % 4 == 0 since the register-staged form); every fp32 x fp32 product that ran on the library in rounds 1-2 -- the input
-# gradients of the 1x1 convolutions and the forward products of the convolutions whose input is not a spike map -- on
-# s2f_pgemm_dx_f32 (6 bf16 passes = fp32 accuracy), their weight gradients on s2f_gemm_dw_general.
-# Round 4: BatchNorm statistics from the producing GEMM's epilogue, without atomics (s2f.h "BatchNorm statistics from the producing
-# GEMM's epilogue").  A forward convolution of a module in training mode stores per-(tile, row) partial sums next to its output
+# BatchNorm statistics from the producing GEMM's epilogue, without atomics (s2f.h "BatchNorm statistics from the producing GEMM's
+# epilogue").  A forward convolution of a module in training mode stores per-(tile, row) partial sums next to its output
 # and hands them over as the attribute `_s2f_part` of the tensor it returns (`carry_stats` moves it across a view); fused.bn_act
 # passes them to the BatchNorm apply kernel instead of launching s2f_bn_stats.  A tensor that lost the attribute on the way simply
 # takes the statistics pass.  BN_PARTIALS_SINGLE: also for the small maps whose BatchNorm computes its statistics itself in one
 # pass (then the row-walking apply kernel runs instead of the single-pass kernel).
-
-
 def _want_partials(stats, B, M, L):
     """-> number of partials per channel (> 0) if the product [B, M, L] should store BatchNorm partials, else 0"""
     if not (stats and cfg.BN_PARTIALS and L % 4 == 0):
@@ -173,12 +160,20 @@ def _want_partials(stats, B, M, L):
     return int(lib.s2f_bn_partials_count(B, L))
 
 
+def _hand_over(part, z):
+    """The partials travel as z's `_s2f_part`, with z's version counter and address at hand-over (stats_of)."""
+    z._s2f_part = (part, z._version, z.data_ptr())
+    return z
+
+
+def _with_part(y, part):
+    return _hand_over(part, y) if part.numel() else y
+
+
 def carry_stats(src, dst):
     """dst is a view / reshape of the GEMM output src: the BatchNorm partials stored with src describe dst as well"""
     part = stats_of(src)
-    if part is not None:
-        dst._s2f_part = (part, dst._version, dst.data_ptr())
-    return dst
+    return dst if part is None else _hand_over(part, dst)
 
 
 def stats_of(z):
@@ -192,203 +187,7 @@ def stats_of(z):
     return part if (z._version == version and z.data_ptr() == ptr) else None
 
 
-def _owner(t):
-    """The long-lived tensor object a cached split belongs to: the parameter a view was taken from (or the first twin of a
-    zero-copy concatenation).  The cache keeps a weak reference to it -- an address is not an identity: once a model is
-    freed, another model's weight of the same shape lands on the same address with the same version counter."""
-    o = getattr(t, "_s2f_owner", None)
-    if o is not None:
-        return o
-    return t._base if t._base is not None else t
-
-
-# A cache entry: (version, out, shape, weakref(owner), job) with job = (src address, mode, C, M, K) -- what
-# s2f_split_bf16x3_multi needs to redo this split from the live weight (resplit_all).  Only the address is kept (a tensor
-# would keep a freed model's weights allocated); it is used only while the owner is alive and its storage still covers it.
-_TRUST_ALL = [False]          # set by resplit_all() inside a capture: every registered split was just redone from the live weights
-
-
-def _cache_get(key, version, shape, owner):
-    hit = _SPLIT_CACHE.get(key)
-    if hit is not None and hit[2] == shape and hit[3]() is owner:
-        if hit[0] == version:
-            return hit[1]
-        if _TRUST_ALL[0] and hit[4] is not None and torch.cuda.is_current_stream_capturing():
-            _SPLIT_CACHE[key] = (version,) + hit[1:]
-            return hit[1]
-    return None
-
-
-def _cache_buffer(key, shape, owner, out_shape, device):
-    """The destination of a (re-)conversion: the buffer of a stale entry of the same weight is converted INTO again -- a
-    captured hipGraph (and the job tables of resplit_all) hold its address, a fresh allocation would leave them writing into
-    freed memory -- otherwise a new one."""
-    hit = _SPLIT_CACHE.get(key)
-    if (hit is not None and hit[2] == shape and hit[3]() is owner and hit[1].device == device
-            and tuple(hit[1].shape) == tuple(out_shape)):
-        return hit[1]
-    return torch.empty(out_shape, dtype=torch.int16, device=device)
-
-
-def _cache_put(key, version, out, shape, owner, job=None, kind="split"):
-    import weakref
-    if len(_SPLIT_CACHE) > 4096:                       # dead entries of freed models
-        for k in [k for k, v in _SPLIT_CACHE.items() if v[3]() is None]:
-            del _SPLIT_CACHE[k]
-    old = _SPLIT_CACHE.get(key)
-    _SPLIT_CACHE[key] = (version, out, shape, weakref.ref(owner), job, kind)
-    if old is None or old[1] is not out or old[4] != job:
-        _SPLIT_TABLE["keys"] = None                    # a new destination: the job tables must be rebuilt (never mutated)
-
-
-# Job tables of resplit_all: one per conversion kernel.  A table tensor is REPLACED, never written again, once built: a
-# captured graph keeps reading the tensor it recorded (graph.py holds references to the tables and buffers of its capture).
-_SPLIT_TABLE = {"keys": None, "jobs": None, "blocks": 0, "njobs": 0, "pack_jobs": None, "pack_blocks": 0, "pack_njobs": 0}
-
-
-def conversion_state():
-    """What a captured step must keep alive: the job tables resplit_all launched with and every cached conversion buffer."""
-    return (_SPLIT_TABLE["jobs"], _SPLIT_TABLE["pack_jobs"], [v[1] for v in _SPLIT_CACHE.values()])
-
-
-def resplit_all(device, build=True):
-    """Redo EVERY cached weight conversion (bf16 hi/mid/lo splits and packs) from the live fp32 weights: one launch per
-    conversion kernel (s2f_split_bf16x3_multi, s2f_pack_bf16x3_multi).  A training step owes this after each optimiser update;
-    a captured step (graph.GraphedStep) records it, so every replay multiplies by the current weights -- without it the graph
-    would replay the bf16 terms of capture time while its backward reads the live fp32 weights.  -> number of weights
-    converted; -1 when the job tables would have to be (re)built and `build` is False (they are uploaded from the host, which
-    a stream capture does not allow: GraphedStep calls this once before capturing)."""
-    def covered(v):
-        o = v[3]()
-        if o is None or v[4] is None or v[1].device != device:
-            return False
-        st = o.untyped_storage()
-        return st.data_ptr() <= v[4][0] and v[4][0] + 4 * v[4][3] * v[4][4] <= st.data_ptr() + st.nbytes()
-    live = [(k, v) for k, v in _SPLIT_CACHE.items() if covered(v)]
-    if not live:
-        return 0
-    keys = tuple(k for k, _ in live)
-    tab = _SPLIT_TABLE
-    if tab["keys"] != keys or (tab["jobs"] is None and tab["pack_jobs"] is None) or \
-            (tab["jobs"] if tab["jobs"] is not None else tab["pack_jobs"]).device != device:
-        if not build:
-            return -1
-        rows, first, prows, pfirst = [], 0, [], 0
-        for _, (_ver, out, _shape, _own, (src, mode, cdim, M, K), kind) in live:
-            if kind == "pack":
-                prows.append([src, out.data_ptr(), M, K, mode | (cdim << 8), pfirst, 0, 0])
-                pfirst += ((M + 63) // 64) * ((K + 31) // 32) * 2
-            else:
-                Mpad, Kpad = out.shape[1], out.shape[2]
-                rows.append([src, out.data_ptr(), M, K, Mpad, Kpad, mode | (cdim << 8), first])
-                first += (Mpad * Kpad + 1023) // 1024
-        tab.update(keys=keys, blocks=first, njobs=len(rows), pack_blocks=pfirst, pack_njobs=len(prows),
-                   jobs=torch.tensor(rows, dtype=torch.int64).to(device) if rows else None,
-                   pack_jobs=torch.tensor(prows, dtype=torch.int64).to(device) if prows else None)
-    if tab["njobs"]:
-        check(lib.s2f_split_bf16x3_multi(_ptr(tab["jobs"]), tab["njobs"], tab["blocks"], _stream()), "s2f_split_bf16x3_multi")
-    if tab["pack_njobs"]:
-        check(lib.s2f_pack_bf16x3_multi(_ptr(tab["pack_jobs"]), tab["pack_njobs"], tab["pack_blocks"], _stream()),
-              "s2f_pack_bf16x3_multi")
-    return len(live)
-
-
-def split_weight(w2d):
-    """fp32 [M, K] -> cached bf16 [3, Mpad, Kpad] (hi, mid, lo).  Re-split when the parameter is modified in place
-    (optimiser step, load_state_dict) -- tracked through the tensor version counter; weights must not be mutated through
-    `.data` (its own version counter).  Inside a captured step the splits are redone by resplit_all()."""
-    key = (w2d.data_ptr(), w2d.numel())
-    M, K = w2d.shape
-    # a zero-copy concatenation of sibling parameters (cat_params) is a fresh tensor every call: it carries the sum of the
-    # parameters' version counters instead of its own
-    version = getattr(w2d, "_s2f_version", w2d._version)
-    owner = _owner(w2d)
-    hit = _cache_get(key, version, (M, K), owner)
-    if hit is not None:
-        return hit
-    Mpad, Kpad = (M + 63) // 64 * 64, (K + 31) // 32 * 32
-    out = _cache_buffer(key, (M, K), owner, (3, Mpad, Kpad), w2d.device)
-    src = w2d.detach()
-    job = (src.data_ptr(), 0, 0, M, K) if src.is_contiguous() else None
-    check(lib.s2f_split_bf16x3(_ptr(src.contiguous()), _ptr(out), M, K, Mpad, Kpad, _stream()), "s2f_split_bf16x3")
-    _cache_put(key, version, out, (M, K), owner, job)
-    return out
-
-
-def pack_weight(w2d, transposed=False):
-    """fp32 [M, K] -> the cached bf16 PACK of it (s2f.h "pipelined GEMMs": blocks of [3 terms][64 rows][32 k], the LDS image of
-    the LDS-DMA kernels), or of its transpose (`transposed`: the pack of w2d^T, the A operand of the forward product of a
-    convolution whose input is a general fp32 tensor).  The pack of W serves its forward product (s2f_pgemm_nn_bf16) AND the
-    input gradient W^T dY (s2f_pgemm_dx_f32).  Versioning and in-graph refresh as split_weight."""
-    key = ("pack", bool(transposed), w2d.data_ptr(), w2d.numel())
-    R, Cc = w2d.shape
-    M, K = (Cc, R) if transposed else (R, Cc)
-    version = getattr(w2d, "_s2f_version", w2d._version)
-    owner = _owner(w2d)
-    hit = _cache_get(key, version, (M, K), owner)
-    if hit is not None:
-        return hit
-    out = _cache_buffer(key, (M, K), owner, (int(lib.s2f_pack_elems(M, K)),), w2d.device)
-    src = w2d.detach()
-    mode = 3 if transposed else 0
-    job = (src.data_ptr(), mode, 0, M, K) if src.is_contiguous() else None
-    check(lib.s2f_pack_bf16x3(_ptr(src.contiguous()), _ptr(out), M, K, mode, 0, _stream()), "s2f_pack_bf16x3")
-    _cache_put(key, version, out, (M, K), owner, job, kind="pack")
-    return out
-
-
-def pack_weight_conv3(weight, transposed=False):
-    """[M, C, 3, 3] -> the cached PACK (see pack_weight) of the TAP-MAJOR matrix [M, (ky, kx, c)] the implicit 3x3 kernels contract
-    over (s2f_pgemm_conv3x3_bf16), or -- `transposed` -- of the transposed-convolution matrix [C, (ky, kx, m)] with flipped taps,
-    Wt[c][(ky, kx), m] = weight[m][c][2 - ky][2 - kx]: the A operand of the input gradient (s2f_pgemm_conv3x3_f32)."""
-    key = ("pack3", bool(transposed), weight.data_ptr())
-    Mw, C = weight.shape[:2]
-    M, K, mode, cdim = (C, 9 * Mw, 2, Mw) if transposed else (Mw, 9 * C, 1, C)
-    owner = _owner(weight)
-    hit = _cache_get(key, weight._version, (Mw, C), owner)
-    if hit is not None:
-        return hit
-    out = _cache_buffer(key, (Mw, C), owner, (int(lib.s2f_pack_elems(M, K)),), weight.device)
-    src = weight.detach()
-    job = (src.data_ptr(), mode, cdim, M, K) if src.is_contiguous() else None
-    check(lib.s2f_pack_bf16x3(_ptr(src.contiguous()), _ptr(out), M, K, mode, cdim, _stream()), "s2f_pack_bf16x3")
-    _cache_put(key, weight._version, out, (Mw, C), owner, job, kind="pack")
-    return out
-
-
-def split_weight_conv3(weight):
-    """[M, C, 3, 3] -> cached bf16 split of the TAP-MAJOR matrix [M, (ky, kx, c)] that the implicit 3x3 kernels contract over."""
-    key = ("tap", weight.data_ptr())
-    M, C = weight.shape[:2]
-    hit = _cache_get(key, weight._version, (M, C), _owner(weight))
-    if hit is not None:
-        return hit
-    w2d = weight.detach().permute(0, 2, 3, 1).reshape(M, 9 * C)
-    Mpad, Kpad = (M + 63) // 64 * 64, (9 * C + 31) // 32 * 32
-    out = _cache_buffer(key, (M, C), _owner(weight), (3, Mpad, Kpad), weight.device)
-    check(lib.s2f_split_bf16x3(_ptr(w2d), _ptr(out), M, 9 * C, Mpad, Kpad, _stream()), "s2f_split_bf16x3")
-    src = weight.detach()
-    _cache_put(key, weight._version, out, (M, C), _owner(weight), (src.data_ptr(), 1, C, M, 9 * C) if src.is_contiguous() else None)
-    return out
-
-
-def split_weight_tconv3(weight):
-    """[M, C, 3, 3] -> cached bf16 split of the transposed-convolution matrix [C, (ky, kx, m)] with flipped taps
-    (Wt[c][(ky, kx), m] = weight[m][c][2 - ky][2 - kx]), rows padded to a multiple of 128 for s2f_conv3x3_general."""
-    key = ("tconv", weight.data_ptr())
-    M, C = weight.shape[:2]
-    hit = _cache_get(key, weight._version, (M, C), _owner(weight))
-    if hit is not None:
-        return hit
-    w2d = weight.detach().flip(2, 3).permute(1, 2, 3, 0).reshape(C, 9 * M)
-    Mpad, Kpad = (C + 127) // 128 * 128, (9 * M + 31) // 32 * 32
-    out = _cache_buffer(key, (M, C), _owner(weight), (3, Mpad, Kpad), weight.device)
-    check(lib.s2f_split_bf16x3(_ptr(w2d), _ptr(out), C, 9 * M, Mpad, Kpad, _stream()), "s2f_split_bf16x3")
-    src = weight.detach()
-    _cache_put(key, weight._version, out, (M, C), _owner(weight), (src.data_ptr(), 2, M, C, 9 * M) if src.is_contiguous() else None)
-    return out
-
-
+# ------------------------------------------------------------------------------------------------ spike GEMM (bf16 MFMA)
 def _is_spike_grid(x):
     xf = x.float()
     return torch.equal(xf * 8, torch.round(xf * 8)) and float(xf.abs().max()) <= 16
@@ -575,12 +374,6 @@ def conv3x3_bn_lif_eval(x, weight, running_mean, running_var, gamma, beta, eps, 
                                          _ptr(gamma), _ptr(beta), float(eps), _ptr(residual), _ptr(u), _ptr(v_in), _ptr(y), _ptr(v_out),
                                          _ptr(stats), B, M, C, H, W, float(vth), int(D), _stream()), "s2f_conv3x3_bn_lif_fwd")
     return u, (Spikes(y, _new_tok(y)) if lif else None), v_out
-
-
-def _with_part(y, part):
-    if part.numel():
-        y._s2f_part = (part, y._version, y.data_ptr())
-    return y
 
 
 def spike_gemm(x, w2d, bias=None, stats=False):

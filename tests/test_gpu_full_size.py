@@ -554,10 +554,10 @@ def test_graph_replay_follows_weight_updates():
     assert l_replay == l_eager
     assert (g_replay - g_eager).abs().max().item() <= 1e-4 * g_eager.abs().max().item()
     # replay -> optimiser step -> EAGER forward -> replay: the eager step sees stale versions of every cached split / pack and
-    # re-converts.  It must convert INTO the buffers the graph has baked in (ops._cache_buffer) and may not touch the job tables
+    # re-converts.  It must convert INTO the buffers the graph has baked in (ops/wcache.py) and may not touch the job tables
     # the graph recorded: a fresh allocation would leave the replay writing bf16 terms into freed, possibly reused memory.
-    ptrs = {k: v[1].data_ptr() for k, v in ops._SPLIT_CACHE.items()}
-    tables = (ops._SPLIT_TABLE["jobs"], ops._SPLIT_TABLE["pack_jobs"])
+    ptrs = {k: e.out.data_ptr() for k, e in ops.conversions.entries.items()}
+    tables = (ops.conversions.split.rows, ops.conversions.pack.rows)
     with torch.no_grad():
         for p in model.parameters():
             p.mul_(0.97)
@@ -565,8 +565,8 @@ def test_graph_replay_follows_weight_updates():
     l_e2, g_e2 = eager()                                      # eager step on the new weights (re-converts every weight)
     junk = [torch.randn(1 << 20, device="cuda") for _ in range(8)]      # churn the allocator: freed blocks would be reused here
     del junk
-    assert all(ops._SPLIT_CACHE[k][1].data_ptr() == ptr for k, ptr in ptrs.items() if k in ops._SPLIT_CACHE)
-    assert ops._SPLIT_TABLE["jobs"] is tables[0] and ops._SPLIT_TABLE["pack_jobs"] is tables[1]
+    assert all(ops.conversions.entries[k].out.data_ptr() == ptr for k, ptr in ptrs.items() if k in ops.conversions.entries)
+    assert ops.conversions.split.rows is tables[0] and ops.conversions.pack.rows is tables[1]
     model.load_state_dict(sd2)
     l_r2 = float(gs())
     g_r2 = torch.cat([p.grad.flatten() for p in model.parameters() if p.grad is not None])

@@ -694,7 +694,7 @@ def test_resplit_all_redoes_every_cached_split(ops):
     assert torch.equal(a0, a) and torch.equal(b0, b) and torch.equal(c0, c)          # same weights -> same terms
     w2d.data.mul_(1.7); wc.data.mul_(-0.3)
     assert ops.resplit_all(w2d.device) >= 3
-    ops._SPLIT_CACHE.clear()
+    ops.clear_conversions()
     a1, b1, c1 = ops.split_weight(w2d), ops.split_weight_conv3(wc), ops.split_weight_tconv3(wc)      # fresh per-weight splits
     assert not torch.equal(a0, a) and torch.equal(a1, a) and torch.equal(b1, b) and torch.equal(c1, c)
     # hi + mid + lo reproduces the fp32 weight to 2^-24
@@ -1070,6 +1070,28 @@ def test_pack_is_refreshed_in_place(ops):
     assert ops.pack_weight(w).data_ptr() == ptr and not torch.equal(p1, snap)
     pt = ops.pack_weight(w, transposed=True)
     assert pt.numel() == ((72 + 63) // 64) * ((100 + 31) // 32) * 6144
+
+
+@pytest.mark.parametrize("layout", ["split", "split_tap", "split_flip", "pack", "pack_t", "pack_tap", "pack_flip"])
+def test_resplit_all_redoes_each_layout(ops, layout):
+    """The two multi-launches of ops.resplit_all read each of the seven layouts (three split sources; pack modes 0-3) from the job
+    row the host built for it: after a change THROUGH `.data` (no version bump) only they can have produced the new terms, and
+    these are bit-equal to a fresh per-weight conversion."""
+    g = torch.Generator().manual_seed(11)
+    w = (torch.randn(100, 72, generator=g) if layout in ("split", "pack", "pack_t") else torch.randn(40, 32, 3, 3, generator=g)).cuda()
+    convert = {"split": ops.split_weight, "split_tap": ops.split_weight_conv3, "split_flip": ops.split_weight_tconv3,
+               "pack": ops.pack_weight, "pack_t": lambda t: ops.pack_weight(t, transposed=True), "pack_tap": ops.pack_weight_conv3,
+               "pack_flip": lambda t: ops.pack_weight_conv3(t, transposed=True)}[layout]
+    ops.clear_conversions()
+    buf = convert(w)
+    first = buf.clone()
+    w.data.mul_(-1.7)
+    assert ops.resplit_all(w.device) == 1
+    torch.cuda.synchronize()
+    redone = buf.clone()
+    ops.clear_conversions()
+    fresh = convert(w)
+    assert fresh is not buf and torch.equal(redone, fresh) and not torch.equal(redone, first)
 
 
 # ----------------------------------------------------------------------------------------------- eval-mode fusion (row f4)
