@@ -731,17 +731,19 @@ def test_fused_attention_neuron_kernel_is_core_plus_neuron(ops, TB, heads, d, N,
         yb = ops.sdsa_packed(yb16, heads, scale, lif=lif_b)
     else:
         # three separate spike maps, each with its own handle
-        hs = [ops.lif((ycat[:, i * C:(i + 1) * C].clone().requires_grad_(True)) * 8.0, None, keep_v=False, spikes=True)[0] for i in range(3)]
+        srcs = [ycat[:, i * C:(i + 1) * C].clone().requires_grad_(True) for i in range(3)]
+        hs = [ops.lif(s * 8.0, None, keep_v=False, spikes=True)[0] for s in srcs]
         yb = ops.sdsa(hs[0], hs[1], hs[2], heads, scale, lif=lif_b)
     assert isinstance(yb, ops.Spikes) and yb.data.dtype == torch.bfloat16
     assert torch.equal(yb.data.float(), ya.detach())
     assert torch.equal(ops.read_stats(lif_a.stats), ops.read_stats(lif_b.stats))
-    if packed:
-        (yb.float() * wgt).sum().backward()
-        # d Q_IFNode(8 src) / d src = 8 * (in-range / 8) = 1 on [0, 1]; the gradient itself is a general fp32 tensor whose
-        # k^T v-sized partial sums are combined with atomics: equal to fp32 round-off, not bit for bit
-        err = (src.grad - ref_in.grad).abs().max().item()
-        assert err <= 1e-5 * ref_in.grad.abs().max().item(), err
+    (yb.float() * wgt).sum().backward()
+    # d Q_IFNode(8 src) / d src = 8 * (in-range / 8) = 1 on [0, 1]; the gradient itself is a general fp32 tensor whose
+    # k^T v-sized partial sums are combined with atomics: equal to fp32 round-off, not bit for bit
+    grads = [src.grad[:, i * C:(i + 1) * C] for i in range(3)] if packed else [s.grad for s in srcs]
+    for i, got in enumerate(grads):
+        err = (got - ref_in.grad[:, i * C:(i + 1) * C]).abs().max().item()
+        assert err <= 1e-5 * ref_in.grad.abs().max().item(), (i, err)
 
 
 @pytest.mark.parametrize("N,C,H,W,K", [(2, 8, 16, 16, 7), (1, 4, 128, 128, 3), (2, 3, 12, 20, 5)])

@@ -288,7 +288,7 @@ def test_class_mask_product_writes_every_image_into_its_slice():
 @pytest.mark.parametrize("Nq,Nk", [(100, 100), (100, 1024), (100, 16384), (36, 4096)])
 def test_inference_attention_and_its_neuron_as_one_launch_pair(Nq, Nk):
     """Under no_grad ops.sdsa(.., lif=) on the decoder's 100-query maps takes s2f_sdsa_lif_fwd_bf16_nomask (attention core + neuron,
-    o never written): the same spikes, bit for bit, as the core followed by the neuron's own kernel."""
+    o never written): the same spikes, bit for bit, and the same firing counters as the core followed by the neuron's own kernel."""
     from spike2former_amd import ops
     from spike2former_amd.neuron import Q_IFNode, Quant
     from spike2former_amd.ops.core import _new_tok
@@ -301,6 +301,7 @@ def test_inference_attention_and_its_neuron_as_one_launch_pair(Nq, Nk):
     q, k, v = spikes(Nq), spikes(Nk), spikes(Nk)
     scale = 1.0 / 16
     a, b = Q_IFNode(surrogate_function=Quant()).cuda(), Q_IFNode(surrogate_function=Quant()).cuda()
+    a.stats, b.stats = ops.new_stats("cuda"), ops.new_stats("cuda")
     with torch.no_grad():
         fused = ops.sdsa(q, k, v, heads, scale, lif=a)
         o = ops.sdsa(q, k, v, heads, scale)
@@ -308,6 +309,8 @@ def test_inference_attention_and_its_neuron_as_one_launch_pair(Nq, Nk):
     assert isinstance(fused, ops.Spikes) and fused.data.dtype == torch.bfloat16
     assert torch.equal(fused.data, two.data if isinstance(two, ops.Spikes) else two.to(torch.bfloat16))
     assert fused.data.float().abs().sum().item() > 0
+    # the firing counters of the epilogue (summed over a wave whose lanes past Nq hold no column) are the neuron kernel's own
+    assert torch.equal(ops.read_stats(a.stats), ops.read_stats(b.stats)) and int(ops.read_stats(a.stats)[1]) > 0
 
 
 @pytest.mark.parametrize("G,B,K,M,N", [(1, 8, 512, 256, 1024), (3, 8, 256, 256, 1024), (1, 2, 147, 32, 4096), (2, 3, 96, 72, 260)])
