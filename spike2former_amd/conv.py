@@ -35,7 +35,7 @@ def _gemm_nc(weight2d, x3, bias, spike_input=False, stats=False):
     that follows can take its statistics from the product's epilogue (ops.BN_PARTIALS)."""
     if (spike_input or isinstance(x3, ops.Spikes)) and ops.SPIKE_GEMM_ENABLED and x3.shape[2] % 4 == 0:
         return ops.spike_gemm(x3, weight2d, bias, stats=stats)       # bf16 matrix cores, exact for spike activations
-    # general fp32 input: ops.dense_gemm (6-pass packed-weight kernel; the library GEMM only for shapes it does not take)
+    # general fp32 input: ops.dense_gemm (6-pass packed-weight kernel; ops.bmm_small for the shapes it does not take)
     y = ops.dense_gemm(ops.spikes_float(x3), weight2d, stats=stats and bias is None)
     if bias is not None:
         y = y + bias.view(1, -1, 1)

@@ -1,10 +1,12 @@
 """Depthwise stencils (csrc/dwconv.hip) and dense k x k convolutions lowered to the GEMM kernels."""
+import ctypes
+
 import torch
 
 from .config import cfg
 from .core import *          # noqa: F401,F403  (the shared plumbing: _ptr, _stream, check, lib, Spikes, ...)
 from .gemm import *          # noqa: F401,F403
-from .wcache import pack_weight, pack_weight_conv3, split_weight, split_weight_conv3, split_weight_tconv3
+from .wcache import pack_weight_conv3, split_weight_conv3, split_weight_tconv3
 
 
 # ------------------------------------------------------------------------------------------------ depthwise conv
@@ -181,57 +183,22 @@ class _ConvDense(torch.autograd.Function):
             ctx.save_for_backward(x, weight)
             ctx.geo = (N, C, H, W, M, kh, kw, Ho, Wo, stride, padding, bias is not None, True)
             ctx.implicit = True
-            part = y.new_empty(0) if part is None else part
-            ctx.mark_non_differentiable(part)
-            ctx.set_materialize_grads(False)
-            return y.view(N, M, Ho, Wo), part
+            return y.view(N, M, Ho, Wo), _part_output(ctx, y, part)
         ctx.implicit = False
         cols = im2col(x, kh, kw, stride, padding)                                       # [N, C*kh*kw, Ho*Wo]
         use_mfma = spike_input and cfg.SPIKE_GEMM_ENABLED and cols.shape[2] % 4 == 0
-        L = Ho * Wo
         if use_mfma:
-            y = torch.empty(N, M, L, dtype=torch.float32, device=x.device)
-            _time_next("spike_gemm_fwd", 4 * N * L * (cols.shape[1] + M), 2 * N * M * L * cols.shape[1],
-                       moved=N * L * ((2 if xb else 4) * cols.shape[1] + 4 * M))
-            pg = xb and L >= 8 and cfg.SPIKE_GEMM_TERMS == 3          # as _SpikeGemm (use_mfma: L % 4 == 0)
-            P = _want_partials(stats and pg and bias is None, N, M, L)
-            if P:
-                part = torch.empty(M, P, 2, dtype=torch.float32, device=x.device)
-                check(lib.s2f_pgemm_nn_bf16_stats(_ptr(pack_weight(w2d)), _ptr(cols), _ptr(y), _ptr(part), N, M, L, cols.shape[1],
-                                                  _stream()), "s2f_pgemm_nn_bf16_stats")
-            elif pg:
-                check(lib.s2f_pgemm_nn_bf16(_ptr(pack_weight(w2d)), _ptr(cols), _ptr(bias), _ptr(y), N, M, L, cols.shape[1],
-                                            cfg.SPIKE_GEMM_TERMS, 0, _stream()), "s2f_pgemm_nn_bf16")
-            else:
-                ws = split_weight(w2d)
-                fn = lib.s2f_spike_gemm_fwd_bf16 if xb else lib.s2f_spike_gemm_fwd
-                check(fn(_ptr(ws), _ptr(cols), _ptr(bias), _ptr(y), N, M, L, cols.shape[1], ws.shape[1], ws.shape[2],
-                         cfg.SPIKE_GEMM_TERMS, _stream()), "s2f_spike_gemm_fwd")
+            y, part = _spike_product(cols, w2d, bias, stats)
         else:
             if xb:
                 cols = cols.float()
-            if L % 4 == 0 and L >= _PGEMM_MIN_N:
-                # general fp32 input (the stem reads the image): the transposed product on the pack of W^T, 6 passes
-                y = torch.empty(N, M, L, dtype=torch.float32, device=x.device)
-                _time_next("dx_gemm", 4 * N * L * (cols.shape[1] + M), 2 * N * M * L * cols.shape[1])
-                P = _want_partials(stats and bias is None, N, M, L)
-                if P:
-                    part = torch.empty(M, P, 2, dtype=torch.float32, device=x.device)
-                    check(lib.s2f_pgemm_dx_f32_stats(_ptr(pack_weight(w2d, transposed=True)), _ptr(cols), 0, _ptr(y), 0, _ptr(part), N,
-                                                     cols.shape[1], M, L, _stream()), "s2f_pgemm_dx_f32_stats")
-                else:
-                    check(lib.s2f_pgemm_dx_f32(_ptr(pack_weight(w2d, transposed=True)), _ptr(cols), 0, _ptr(y), 0, N, cols.shape[1], M,
-                                               L, 0.0, 0, _stream()), "s2f_pgemm_dx_f32")
-            else:
-                y = bmm_small(w2d.unsqueeze(0).expand(N, -1, -1), cols)
+            # general fp32 input (the stem reads the image): the product of dense_gemm with one weight, the bias added after it
+            y, part = _dense_product(cols, [w2d], stats and bias is None)
             if bias is not None:
                 y = y + bias.view(1, -1, 1)
         ctx.save_for_backward(cols, weight)
         ctx.geo = (N, C, H, W, M, kh, kw, Ho, Wo, stride, padding, bias is not None, use_mfma)
-        part = y.new_empty(0) if part is None else part
-        ctx.mark_non_differentiable(part)
-        ctx.set_materialize_grads(False)
-        return y.view(N, M, Ho, Wo), part
+        return y.view(N, M, Ho, Wo), _part_output(ctx, y, part)
 
     @staticmethod
     def backward(ctx, gy, _gpart=None):
@@ -280,7 +247,6 @@ class _ConvDense(torch.autograd.Function):
                     # the LDS-DMA pipelined kernel (csrc/dwp.hip): the horizontal taps come from a copy shifted by one element.
                     # Its tile is 128 output channels x 256 (tap, input channel) rows: narrower layers stay on the round-2 kernel
                     # (measured, tools/probe_dwp_conv.py: M = 32 / 64 lose 10-70 %, C = 32 ties)
-                    import ctypes
                     xs = torch.empty(x.numel() + 16, dtype=x.dtype, device=x.device)
                     check(lib.s2f_shift1_bf16(_ptr(x), _ptr(xs), x.numel(), _stream()), "s2f_shift1_bf16")
                     arr = (ctypes.c_int64 * 9)(_ptr(gy), _ptr(x), _ptr(xs), _ptr(gt), N, M, C, H, W)
@@ -297,22 +263,8 @@ class _ConvDense(torch.autograd.Function):
                 else:
                     gw = gt.permute(0, 3, 1, 2).contiguous()
             elif use_mfma and M >= 16:
-                sink = _sink_for(weight)
-                gw = torch.empty(M, K, dtype=torch.float32, device=gy.device) if sink is None else None
-                if _may_defer_dw(sink, N, Ho * Wo) and xb:          # (cols is im2col's own allocation: aligned)
-                    _defer_dw(gy, cols, sink, N, M, K, Ho * Wo)
-                    return _grad_pair(ctx.has_tok, gx) + (None, gy.sum((0, 2)) if (has_bias and ctx.needs_input_grad[3]) else None,
-                                                          None, None, None, None)
-                _time_next("spike_gemm_dw", 4 * N * Ho * Wo * (K + M), 2 * N * M * Ho * Wo * K,
-                           moved=N * Ho * Wo * ((2 if xb else 4) * K + 4 * M))
-                side = _wgrad_stream(sink, gy, cols)
-                st = side.cuda_stream if side is not None else _stream()
-                if xb:
-                    check(lib.s2f_spike_gemm_dw_bf16(_ptr(gy), _ptr(cols), _ptr(gw if sink is None else sink), N, M, K, Ho * Wo,
-                                                     int(sink is not None), st), "s2f_spike_gemm_dw_bf16")
-                else:
-                    check(lib.s2f_spike_gemm_dw(_ptr(gy), _ptr(cols), _ptr(gw if sink is None else sink), N, M, K, Ho * Wo,
-                                                int(sink is not None), 1, st), "s2f_spike_gemm_dw")
+                # (the stand-alone pipelined kernel: not measured for column-matrix operands, therefore off)
+                gw = _spike_dw(gy, cols, weight, N, M, K, Ho * Wo, pipe=False)
             elif (Ho * Wo) % 4 == 0 and cols.dtype == torch.float32:
                 # both operands general fp32 (the stem): 6-pass weight-gradient kernel, straight into the sink when there is one
                 sink = _sink_for(weight)

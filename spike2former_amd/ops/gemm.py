@@ -1,5 +1,7 @@
 """GEMM-shaped ops: the packed-weight spike GEMMs and their gradients (csrc/pgemm.hip, gemm.hip, gemm_bf16.hip), dense-input
 products, token-major nn.Linear, the mask contraction.  The converted weights they multiply by come from ops/wcache.py."""
+import ctypes
+
 import torch
 
 from .config import cfg
@@ -38,6 +40,52 @@ def bmm_small(a, b, reduce_batch=False):
 _PGEMM_MIN_N = 128          # the forward products of s2f_pgemm_dx_f32 want at least one 128-column tile
 
 
+def _dense_fast(L):
+    """what s2f_pgemm_dx_f32 takes: rows of whole 16-byte groups, at least one 128-column tile"""
+    return L % 4 == 0 and L >= _PGEMM_MIN_N
+
+
+def _part_output(ctx, y, part):
+    """-> the BatchNorm partials as the second, non-differentiable output of the autograd Function that produced y (an empty tensor
+    for none; autograd would otherwise zero-fill a [M, P, 2] "gradient" of the partials per launch)"""
+    part = y.new_empty(0) if part is None else part
+    ctx.mark_non_differentiable(part)
+    ctx.set_materialize_grads(False)
+    return part
+
+
+def _dense_product(x, ws, stats):
+    """ws[g] [M, K] @ x[:, g K : (g + 1) K] for a contiguous fp32 x [B, G K, L] -> (y [B, G M, L], BatchNorm partials or None): the
+    forward of _DenseGemm and, with one weight, of the stem convolution's column matrix."""
+    G = len(ws)
+    M, K = ws[0].shape
+    B, _, L = x.shape
+    if not _dense_fast(L):
+        wb = torch.stack(ws, 0).unsqueeze(0).expand(B, G, M, K).reshape(B * G, M, K) if G > 1 else ws[0].expand(B, M, K)
+        return bmm_small(wb, x.view(B * G, K, L)).view(B, G * M, L), None
+    y = torch.empty(B, G * M, L, dtype=torch.float32, device=x.device)
+    P = _want_partials(stats, B, G * M, L)
+    part = torch.empty(G * M, P, 2, dtype=torch.float32, device=x.device) if P else None
+    if 1 < G <= 4 and cfg.DENSE_GROUPED:
+        # the G products as ONE launch (blockIdx.z = group): three workgroups per CU instead of one on the 32x32-stage maps
+        packs = (ctypes.c_void_p * G)(*[pack_weight(w, transposed=True).data_ptr() for w in ws])
+        _time_next("dx_gemm", 4 * B * L * G * (K + M), 2 * B * G * M * L * K)
+        check(lib.s2f_pgemm_dx_f32_grouped(packs, G, _ptr(x), G * K * L, K * L, _ptr(y), G * M * L, M * L, _ptr(part), 2 * M * P, B, K, M, L,
+                                           _stream()), "s2f_pgemm_dx_f32_grouped")
+        return y, part
+    for g, w in enumerate(ws):
+        _time_next("dx_gemm", 4 * B * L * (K + M), 2 * B * M * L * K)
+        if P:
+            check(lib.s2f_pgemm_dx_f32_stats(_ptr(pack_weight(w, transposed=True)), x.data_ptr() + 4 * g * K * L, G * K * L,
+                                             y.data_ptr() + 4 * g * M * L, G * M * L, part.data_ptr() + 8 * g * M * P,
+                                             B, K, M, L, _stream()), "s2f_pgemm_dx_f32_stats")
+        else:
+            check(lib.s2f_pgemm_dx_f32(_ptr(pack_weight(w, transposed=True)), x.data_ptr() + 4 * g * K * L, G * K * L,
+                                       y.data_ptr() + 4 * g * M * L, G * M * L, B, K, M, L, 0.0, 0, _stream()),
+                  "s2f_pgemm_dx_f32")
+    return y, part
+
+
 class _DenseGemm(torch.autograd.Function):
     """Y[b] = W @ X[b] for a general fp32 X (the 1x1 convolutions that do not read spikes: SepConv.pwconv2, RepConv's second
     1x1, sdtv2.py:124-125, 164) with G independent weights applied to consecutive channel groups: ws = G matrices [M, K],
@@ -49,42 +97,11 @@ class _DenseGemm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stats, x, *ws):
         _need_cuda(x, *ws)
-        G = len(ws)
-        M, K = ws[0].shape
-        B, _, L = x.shape
         x = x.contiguous()
         ctx.save_for_backward(x, *ws)
-        ctx.fast = L % 4 == 0 and L >= _PGEMM_MIN_N          # rows of whole 16-byte groups, at least one 128-column tile
-        if ctx.fast:
-            y = torch.empty(B, G * M, L, dtype=torch.float32, device=x.device)
-            P = _want_partials(stats, B, G * M, L)
-            part = torch.empty(G * M, P, 2, dtype=torch.float32, device=x.device) if P else x.new_empty(0)
-            ctx.mark_non_differentiable(part)
-            ctx.set_materialize_grads(False)
-            if 1 < G <= 4 and cfg.DENSE_GROUPED:
-                # the G products as ONE launch (blockIdx.z = group): three workgroups per CU instead of one on the 32x32-stage maps
-                import ctypes
-                packs = (ctypes.c_void_p * G)(*[pack_weight(w, transposed=True).data_ptr() for w in ws])
-                _time_next("dx_gemm", 4 * B * L * G * (K + M), 2 * B * G * M * L * K)
-                check(lib.s2f_pgemm_dx_f32_grouped(packs, G, _ptr(x), G * K * L, K * L, _ptr(y), G * M * L, M * L, _ptr(part) if P else 0,
-                                                   2 * M * P, B, K, M, L, _stream()), "s2f_pgemm_dx_f32_grouped")
-                return y, part
-            for g, w in enumerate(ws):
-                _time_next("dx_gemm", 4 * B * L * (K + M), 2 * B * M * L * K)
-                if P:
-                    check(lib.s2f_pgemm_dx_f32_stats(_ptr(pack_weight(w, transposed=True)), x.data_ptr() + 4 * g * K * L, G * K * L,
-                                                     y.data_ptr() + 4 * g * M * L, G * M * L, part.data_ptr() + 8 * g * M * P,
-                                                     B, K, M, L, _stream()), "s2f_pgemm_dx_f32_stats")
-                else:
-                    check(lib.s2f_pgemm_dx_f32(_ptr(pack_weight(w, transposed=True)), x.data_ptr() + 4 * g * K * L, G * K * L,
-                                               y.data_ptr() + 4 * g * M * L, G * M * L, B, K, M, L, 0.0, 0, _stream()),
-                          "s2f_pgemm_dx_f32")
-            return y, part
-        part = x.new_empty(0)
-        ctx.mark_non_differentiable(part)
-        ctx.set_materialize_grads(False)
-        wb = torch.stack(ws, 0).unsqueeze(0).expand(B, G, M, K).reshape(B * G, M, K) if G > 1 else ws[0].expand(B, M, K)
-        return bmm_small(wb, x.view(B * G, K, L)).view(B, G * M, L), part
+        ctx.fast = _dense_fast(x.shape[2])
+        y, part = _dense_product(x, ws, stats)
+        return y, _part_output(ctx, y, part)
 
     @staticmethod
     def backward(ctx, gy, _gpart=None):
@@ -98,7 +115,6 @@ class _DenseGemm(torch.autograd.Function):
         gx, gws = None, [None] * G
         if ctx.fast:
             if ctx.needs_input_grad[1] and 1 < G <= 4 and cfg.DENSE_GROUPED:
-                import ctypes
                 gx = torch.empty(B, G * K, L, dtype=torch.float32, device=gy.device)
                 packs = (ctypes.c_void_p * G)(*[pack_weight(w).data_ptr() for w in ws])
                 _time_next("dx_gemm", 4 * B * L * G * (K + M), 2 * B * G * M * L * K)
@@ -193,6 +209,65 @@ def _is_spike_grid(x):
     return torch.equal(xf * 8, torch.round(xf * 8)) and float(xf.abs().max()) <= 16
 
 
+def _spike_product(x, w2d, bias, stats):
+    """W [M, K] @ x[b] (+ bias) for a contiguous spike operand x [B, K, L], bf16 or fp32 -> (y [B, M, L] fp32, BatchNorm partials or
+    None): the forward of _SpikeGemm and of a convolution's spike column matrix."""
+    B, K, L = x.shape
+    M = w2d.shape[0]
+    if cfg.SPIKE_GEMM_CHECK:
+        assert _is_spike_grid(x), "not a spike tensor"
+    y = torch.empty(B, M, L, dtype=torch.float32, device=x.device)
+    xb = x.dtype == torch.bfloat16
+    _time_next("spike_gemm_fwd", 4 * B * L * (K + M), 2 * B * M * L * K, moved=B * L * ((2 if xb else 4) * K + 4 * M))
+    pg = xb and L % 4 == 0 and L >= 8 and cfg.SPIKE_GEMM_TERMS == 3          # what the packed-weight pipeline takes
+    P = _want_partials(stats and pg and bias is None, B, M, L)
+    part = torch.empty(M, P, 2, dtype=torch.float32, device=x.device) if P else None
+    if P:
+        check(lib.s2f_pgemm_nn_bf16_stats(_ptr(pack_weight(w2d)), _ptr(x), _ptr(y), _ptr(part), B, M, L, K, _stream()),
+              "s2f_pgemm_nn_bf16_stats")
+    elif pg:
+        check(lib.s2f_pgemm_nn_bf16(_ptr(pack_weight(w2d)), _ptr(x), _ptr(bias), _ptr(y), B, M, L, K, cfg.SPIKE_GEMM_TERMS, 0,
+                                    _stream()), "s2f_pgemm_nn_bf16")
+    else:
+        ws = split_weight(w2d)
+        fn = lib.s2f_spike_gemm_fwd_bf16 if xb else lib.s2f_spike_gemm_fwd
+        check(fn(_ptr(ws), _ptr(x), _ptr(bias), _ptr(y), B, M, L, K, ws.shape[1], ws.shape[2], cfg.SPIKE_GEMM_TERMS, _stream()),
+              "s2f_spike_gemm_fwd")
+    return y, part
+
+
+def _spike_dw_launch(gy, x, out, B, M, K, L, accumulate, st):
+    """out [M, K] (+)= sum_b gy[b] [M, L] @ x[b]^T for a spike operand x [B, K, L], bf16 or fp32, on stream handle `st`"""
+    if x.dtype == torch.bfloat16:
+        check(lib.s2f_spike_gemm_dw_bf16(_ptr(gy), _ptr(x), _ptr(out), B, M, K, L, accumulate, st), "s2f_spike_gemm_dw_bf16")
+    else:
+        check(lib.s2f_spike_gemm_dw(_ptr(gy), _ptr(x), _ptr(out), B, M, K, L, accumulate, 1, st), "s2f_spike_gemm_dw")
+
+
+def _spike_dw(gy, x, w, B, M, K, L, pipe):
+    """The weight gradient sum_b gy[b] @ x[b]^T of `w` ([M, K], or any view from its first element) on the matrix-core kernels
+    (L % 4 == 0, M >= 16: the caller checks) -> the gradient [M, K], or None when it went to w's sink or into the queue of
+    wgrad_flush().  `pipe`: long contractions may launch the LDS-DMA pipelined kernel on their own."""
+    sink = _sink_for(w)
+    xb = x.dtype == torch.bfloat16
+    # (x may be a slice of a bf16 map at any 2-byte offset; the grouped kernels read 8-byte pieces)
+    if _may_defer_dw(sink, B, L) and xb and x.data_ptr() % 8 == 0:
+        _defer_dw(gy, x, sink, B, M, K, L)
+        return None
+    gw = torch.empty(M, K, dtype=torch.float32, device=x.device) if sink is None else None
+    _time_next("spike_gemm_dw", 4 * B * L * (K + M), 2 * B * M * L * K, moved=B * L * ((2 if xb else 4) * K + 4 * M))
+    side = _wgrad_stream(sink, gy, x)
+    st = side.cuda_stream if side is not None else _stream()
+    if (pipe and xb and cfg.DW_PIPE and M >= 128 and K >= 128 and lib.s2f_spike_gemm_dw_pipe_ok(B, M, K, L)
+            and gy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0):
+        # the LDS-DMA pipeline where its 128 x 256 tile is filled
+        check(lib.s2f_spike_gemm_dw_pipe(_ptr(gy), _ptr(x), _ptr(gw if sink is None else sink), B, M, K, L, int(sink is not None), 0, 0,
+                                         st), "s2f_spike_gemm_dw_pipe")
+    else:
+        _spike_dw_launch(gy, x, gw if sink is None else sink, B, M, K, L, int(sink is not None), st)
+    return gw
+
+
 class _SpikeGemm(torch.autograd.Function):
     """Y[b] = W @ X[b] (+ bias) with X spikes (bf16 pair or fp32): forward and weight gradient on the bf16 matrix cores (W /
     dY split hi+mid+lo), input gradient on the transposed packed-weight kernel (dx_gemm: s2f_pgemm_dx_f32, 6 passes)."""
@@ -201,34 +276,10 @@ class _SpikeGemm(torch.autograd.Function):
     def forward(ctx, x, tok, w2d, bias, stats=False):
         _need_cuda(w2d, bias, spikes=x)
         x = x.contiguous()
-        B, K, N = x.shape
-        M = w2d.shape[0]
-        if cfg.SPIKE_GEMM_CHECK:
-            assert _is_spike_grid(x), "not a spike tensor"
-        y = torch.empty(B, M, N, dtype=torch.float32, device=x.device)
-        xb = x.dtype == torch.bfloat16
-        _time_next("spike_gemm_fwd", 4 * B * N * (K + M), 2 * B * M * N * K, moved=B * N * ((2 if xb else 4) * K + 4 * M))
-        pg = xb and N % 4 == 0 and N >= 8 and cfg.SPIKE_GEMM_TERMS == 3          # what the packed-weight pipeline takes
-        P = _want_partials(stats and pg and bias is None, B, M, N)
-        part = torch.empty(M, P, 2, dtype=torch.float32, device=x.device) if P else None
-        if P:
-            check(lib.s2f_pgemm_nn_bf16_stats(_ptr(pack_weight(w2d)), _ptr(x), _ptr(y), _ptr(part), B, M, N, K, _stream()),
-                  "s2f_pgemm_nn_bf16_stats")
-        elif pg:
-            check(lib.s2f_pgemm_nn_bf16(_ptr(pack_weight(w2d)), _ptr(x), _ptr(bias), _ptr(y), B, M, N, K, cfg.SPIKE_GEMM_TERMS, 0,
-                                        _stream()), "s2f_pgemm_nn_bf16")
-        else:
-            ws = split_weight(w2d)
-            fn = lib.s2f_spike_gemm_fwd_bf16 if xb else lib.s2f_spike_gemm_fwd
-            check(fn(_ptr(ws), _ptr(x), _ptr(bias), _ptr(y), B, M, N, K, ws.shape[1], ws.shape[2], cfg.SPIKE_GEMM_TERMS, _stream()),
-                  "s2f_spike_gemm_fwd")
+        y, part = _spike_product(x, w2d, bias, stats)
         ctx.save_for_backward(x, w2d)
         ctx.has_bias, ctx.has_tok = bias is not None, tok is not None
-        if part is None:
-            part = y.new_empty(0)
-        ctx.mark_non_differentiable(part)
-        ctx.set_materialize_grads(False)          # (autograd would zero-fill a [P, M, 2] "gradient" of the partials per launch)
-        return y, part
+        return y, _part_output(ctx, y, part)
 
     @staticmethod
     def backward(ctx, gy, _gpart=None):
@@ -244,28 +295,7 @@ class _SpikeGemm(torch.autograd.Function):
             M, K = w2d.shape
             L = x.shape[2]
             if L % 4 == 0 and M >= 16:     # the matrix-core kernels: 32- / 64- / 128-row tiles by M
-                sink = _sink_for(w2d)
-                gw = torch.empty(M, K, dtype=torch.float32, device=x.device) if sink is None else None
-                xb = x.dtype == torch.bfloat16
-                # (x may be a slice of a bf16 map at any 2-byte offset; the grouped kernels read 8-byte pieces)
-                if _may_defer_dw(sink, B, L) and xb and x.data_ptr() % 8 == 0:
-                    _defer_dw(gy, x, sink, B, M, K, L)
-                    return _grad_pair(ctx.has_tok, gx) + (None, gy.sum((0, 2)) if (ctx.has_bias and ctx.needs_input_grad[3]) else None,
-                                                          None)
-                _time_next("spike_gemm_dw", 4 * B * L * (K + M), 2 * B * M * L * K, moved=B * L * ((2 if xb else 4) * K + 4 * M))
-                side = _wgrad_stream(sink, gy, x)
-                st = side.cuda_stream if side is not None else _stream()
-                if (xb and cfg.DW_PIPE and M >= 128 and K >= 128 and lib.s2f_spike_gemm_dw_pipe_ok(B, M, K, L)
-                        and gy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0):
-                    # long contractions launch on their own: the LDS-DMA pipeline where its 128 x 256 tile is filled
-                    check(lib.s2f_spike_gemm_dw_pipe(_ptr(gy), _ptr(x), _ptr(gw if sink is None else sink), B, M, K, L,
-                                                     int(sink is not None), 0, 0, st), "s2f_spike_gemm_dw_pipe")
-                elif xb:
-                    check(lib.s2f_spike_gemm_dw_bf16(_ptr(gy), _ptr(x), _ptr(gw if sink is None else sink), B, M, K, L,
-                                                     int(sink is not None), st), "s2f_spike_gemm_dw_bf16")
-                else:
-                    check(lib.s2f_spike_gemm_dw(_ptr(gy), _ptr(x), _ptr(gw if sink is None else sink), B, M, K, L,
-                                                int(sink is not None), 1, st), "s2f_spike_gemm_dw")
+                gw = _spike_dw(gy, x, w2d, B, M, K, L, pipe=True)
             else:
                 gw = bmm_small(gy, x.float().transpose(1, 2), reduce_batch=True)          # shapes the matrix-core kernels do not take
         if ctx.has_bias and ctx.needs_input_grad[3]:
@@ -519,9 +549,9 @@ class _MaskEinsum(torch.autograd.Function):
     `e_exact`: E is exactly representable in bf16 (the head passes alpha * spikes = multiples of 1/2): forward and
     d(mask_features) then run on the bf16 matrix cores with MF / the incoming gradient split hi+mid+lo in the kernel
     (s2f_split_gemm, 3 passes, exact products, fp32 accumulation) -- the forward as ONE GEMM of K = T*C, no partial-sum
-    traffic.  dE (two general fp32 operands, K = HW) and the non-exact case stay on rocBLAS fp32.  The backward writes each
-    dMF[t] / dE[t] slice straight into its final buffer: autograd's select_backward would zero-fill and add T full-size
-    [T,B,C,HW] tensors (4 x 537 MB at C2)."""
+    traffic.  dE (two general fp32 operands, K = HW) runs on s2f_spike_gemm_dw with both sides split (6 passes), the non-exact
+    case on ops.bmm_small.  The backward writes each dMF[t] / dE[t] slice straight into its final buffer: autograd's
+    select_backward would zero-fill and add T full-size [T,B,C,HW] tensors (4 x 537 MB at C2)."""
 
     @staticmethod
     def forward(ctx, e, mf, scale, e_exact):
@@ -675,7 +705,6 @@ class _MaskEinsumFolded(torch.autograd.Function):
             if xb and T * B <= 56 and HW % 4 == 0:
                 # the T * B products H[t, b] = g[b] S[t, b]^T as ONE grouped launch (12 output tiles each over a 65 536-long
                 # contraction: one by one they run at 183 TF/s) into the zeroed H
-                import ctypes
                 H.zero_()
                 flat = []
                 for t in range(T):
@@ -690,12 +719,7 @@ class _MaskEinsumFolded(torch.autograd.Function):
             else:
                 for t in range(T):
                     for b in range(B):
-                        if xb:
-                            check(lib.s2f_spike_gemm_dw_bf16(_ptr(g[b]), _ptr(S[t, b]), _ptr(H[t, b]), 1, Q, C, HW, 0, _stream()),
-                                  "s2f_spike_gemm_dw_bf16")
-                        else:
-                            check(lib.s2f_spike_gemm_dw(_ptr(g[b]), _ptr(S[t, b]), _ptr(H[t, b]), 1, Q, C, HW, 0, 1, _stream()),
-                                  "s2f_spike_gemm_dw")
+                        _spike_dw_launch(g[b], S[t, b], H[t, b], 1, Q, C, HW, 0, _stream())
             rs = channel_sum(g.view(1, B * Q, HW)).view(B, Q) if bias is not None else None                      # [B, Q]
             if ctx.needs_input_grad[0]:
                 ge = _mm_tm(H.view(-1, C), W).view(T, B, Q, Co)                                   # H @ W^T

@@ -680,6 +680,69 @@ def test_conv_dense_vs_aten_cpu(ops, N, C, M, H, W, k, s, p, spike):
             assert (a.detach().cpu() - r.detach()).abs().max().item() <= 2e-5 * r.abs().max().item(), implicit
 
 
+@pytest.mark.parametrize("M", [128, 40])
+def test_conv_dense_on_bf16_spike_columns_is_spike_gemm_on_im2col(ops, monkeypatch, M):
+    """ops.conv_dense fed a bf16 ops.Spikes pair through the column-matrix lowering (3x3, stride 2: cols [2, 288, 256]; a full
+    128-row tile and a ragged one), without and with BatchNorm partials: the forward and the partials are BIT-IDENTICAL to
+    ops.spike_gemm on ops.im2col of the same spikes -- one product routine serves both.  Weight gradients of both against the fp64
+    einsum to 3e-6 of sum|dY||X| (split-K atomics do not repeat bit for bit), the input gradient arriving on the spikes' handle
+    against F.conv2d's on the CPU to 2e-5 of its max.  The column-matrix site does not launch the stand-alone pipelined
+    weight-gradient kernel, although M = 128, K = 288 would pass the 1x1 site's size gate."""
+    import torch.nn.functional as F
+    from spike2former_amd._lib import lib
+    g = torch.Generator().manual_seed(7 * M)
+    xs = _spikes_bf16((2, 32, 32, 32), g)
+    w = torch.randn(M, 32, 3, 3, generator=g) * 288 ** -0.5
+    gy = torch.randn(2, M, 16, 16, generator=g)
+    xo = xs.float().cpu().requires_grad_(True)
+    F.conv2d(xo, w, None, 2, 1).backward(gy)
+    cols64, gy64 = F.unfold(xs.float().cpu().double(), 3, 1, 1, 2), gy.view(2, M, 256).double()
+    gw_ref = torch.einsum("bml,bkl->mk", gy64, cols64)
+    gw_bound = 3e-6 * torch.einsum("bml,bkl->mk", gy64.abs(), cols64.abs()).max().item()
+    pipe_calls, pipe = [], lib.s2f_spike_gemm_dw_pipe
+    monkeypatch.setattr(lib, "s2f_spike_gemm_dw_pipe", lambda *a: (pipe_calls.append(a), pipe(*a))[1])
+    for stats in (False, True):
+        single, ops.BN_PARTIALS_SINGLE = ops.BN_PARTIALS_SINGLE, stats          # (a map this small stores partials only under it)
+        try:
+            wc = w.clone().cuda().requires_grad_(True)
+            tok = ops._new_tok(xs).clone().requires_grad_(True)
+            before = len(pipe_calls)
+            yc = ops.conv_dense(ops.Spikes(xs, tok), wc, None, 2, 1, True, stats=stats)
+            pc = ops.stats_of(yc)
+            yc.backward(gy.cuda())
+            assert len(pipe_calls) == before          # (the 1x1 site below may take that kernel)
+            cols = ops.im2col(xs, 3, 3, 2, 1)
+            wr = w.view(M, -1).clone().cuda().requires_grad_(True)
+            yr = ops.spike_gemm(ops.Spikes(cols, ops._new_tok(cols).clone().requires_grad_(True)), wr, None, stats=stats)
+            pr = ops.stats_of(yr)
+            yr.backward(gy.cuda().view(2, M, 256))
+        finally:
+            ops.BN_PARTIALS_SINGLE = single
+        assert tuple(cols.shape) == (2, 288, 256) and torch.equal(yc.view(2, M, 256), yr), stats
+        assert (pc is not None) == stats and (pr is not None) == stats and (not stats or torch.equal(pc, pr))
+        for gw in (wc.grad.view(M, -1), wr.grad):
+            err = (gw.cpu().double() - gw_ref).abs().max().item()
+            print(f"M={M} stats={stats}: dW error {err:.3e}, bound {gw_bound:.3e}")
+            assert err <= gw_bound, (stats, err, gw_bound)
+        err = (tok.grad.cpu() - xo.grad).abs().max().item()
+        print(f"M={M} stats={stats}: dX error {err:.3e}, bound {2e-5 * xo.grad.abs().max().item():.3e}")
+        assert err <= 2e-5 * xo.grad.abs().max().item(), stats
+
+
+def test_conv_dense_on_a_dense_map_is_dense_gemm_on_im2col(ops):
+    """The stem's shape (fp32 image, 7x7, stride 2, padding 3; L = 256): ops.conv_dense gives what ops.dense_gemm gives on ops.im2col
+    of the image, from the same product routine -- equal, or within 2e-6 of max(|w| @ |x|), the allowance of
+    test_gemm_epilogue_partials_are_the_tile_sums for s2f_pgemm_dx_f32."""
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(2, 3, 32, 32, generator=g).cuda()
+    w = (torch.randn(32, 3, 7, 7, generator=g) * 147 ** -0.5).cuda()
+    yc = ops.conv_dense(x, w, None, 2, 3, False).view(2, 32, 256)
+    cols = ops.im2col(x, 7, 7, 2, 3)
+    yr = ops.dense_gemm(cols, w.view(32, -1))
+    bound = 2e-6 * torch.matmul(w.view(32, -1).abs().double(), cols.abs().double()).max().item()
+    assert torch.equal(yc, yr) or (yc - yr).abs().max().item() <= bound
+
+
 def test_resplit_all_redoes_every_cached_split(ops):
     """ops.resplit_all (s2f_split_bf16x3_multi: all weights in one launch) writes, for each of the three source layouts, exactly
     the bf16 terms the per-weight split wrote -- checked after changing the weights THROUGH `.data` (no version bump), i.e.
