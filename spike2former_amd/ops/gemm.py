@@ -628,15 +628,20 @@ class _MaskEinsumFolded(torch.autograd.Function):
     the convolution's own forward (69 GFLOP at C2), its weight gradient and the 537 MB fp32 mask_features tensor it wrote for
     the einsum to read back never exist, and dE needs 3 MFMA passes (spike operand) instead of 6.  Same value as the
     reference's two steps up to the association of fp32 sums (nothing thresholds this output).
-    Backward: dS[t,b] = (scale E[t,b] W)^T g[b] (the forward's [Q, C] matrix again; ragged HW: W^T (scale E^T g) on ops.bmm_small);
+    Backward: dS[t,b] = (scale E[t,b] W)^T g[b] (the forward's [Q, C] matrix again);
     H[t,b] = g[b] S[t,b]^T (weight-gradient kernel on a spike operand) -> dE = scale (H W^T + rowsum(g) bias^T),
-    dW = scale sum E^T H, dbias = scale sum E^T rowsum(g)."""
+    dW = scale sum E^T H, dbias = scale sum E^T rowsum(g).
+    Contract: C % 32 == 0 (a 32-long contraction step never straddles two time slices) and HW % 4 == 0 (rows of whole 8-byte groups
+    of bf16 spikes); forward raises a RuntimeError for any other shape before it launches anything.  HW % 8 == 0 runs on
+    s2f_pgemm_nn_bf16_ex, HW % 8 == 4 on s2f_spike_gemm_fwd_bf16_ex."""
 
     @staticmethod
     def forward(ctx, e, sdata, stok, W, bias, scale, T, B, e_exact):
         _need_cuda(e, W, bias, spikes=sdata)
         Q, Co = e.shape[2], e.shape[3]
         C, HW = sdata.shape[1], sdata.shape[2]
+        if not (C % 32 == 0 and HW % 4 == 0):
+            raise RuntimeError(f"mask_einsum_folded: needs C % 32 == 0 and HW % 4 == 0; got C={C}, HW={HW}")
         e = e.contiguous()
         sdata = sdata.contiguous()
         dev = e.device
@@ -679,7 +684,7 @@ class _MaskEinsumFolded(torch.autograd.Function):
         dev = g.device
         gs = ge = gW = gb = None
         S = sdata.view(T, B, C, HW)
-        if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and HW % 4 == 0:
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             # dS[t, b] = W^T (scale E[t, b]^T g[b]) = (scale E[t, b] W)^T g[b]: the fold of the forward, read backwards -- ONE product
             # per (t, b) over the Q queries with the [Q, C] matrix the forward already formed, instead of the [Co x Q] product into a
             # [T, B, Co, HW] intermediate (537 MB at C2) followed by the convolution's input-gradient GEMM over it.  Both operands
@@ -690,19 +695,11 @@ class _MaskEinsumFolded(torch.autograd.Function):
             for t in range(T):
                 for b in range(B):
                     _mtm_tm(ews[t, b], g[b], out=gs[t * B + b])
-        elif ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            # ragged rows (HW % 4 != 0): dS[t, b] = W^T (scale E[t, b]^T g[b]) in two steps on ops.bmm_small -- the second is the
-            # mask_feature convolution's input gradient
-            G = torch.empty(T, B, Co, HW, dtype=torch.float32, device=dev)
-            es = e * scale
-            for t in range(T):
-                G[t].copy_(bmm_small(es[t].transpose(1, 2), g))
-            gs = dx_gemm(W, G.view(T * B, Co, HW))
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
             H = torch.empty(T, B, Q, C, dtype=torch.float32, device=dev)
             xb = sdata.dtype == torch.bfloat16
             _time_next("spike_gemm_dw", 4 * T * B * HW * (C + Q), 2 * T * B * Q * HW * C, moved=T * B * HW * ((2 if xb else 4) * C + 4 * Q))
-            if xb and T * B <= 56 and HW % 4 == 0:
+            if xb and T * B <= 56:
                 # the T * B products H[t, b] = g[b] S[t, b]^T as ONE grouped launch (12 output tiles each over a 65 536-long
                 # contraction: one by one they run at 183 TF/s) into the zeroed H
                 H.zero_()
@@ -755,7 +752,8 @@ def class_mask_product(cls_score, mask_probs):
 
 
 def mask_einsum_folded(e, spikes, W, bias, scale, T, B, e_exact=False):
-    """e [T, B, Q, Co], spikes: bf16 Spikes [T*B, C, HW] (mask_feature_spike's output), W [Co, C], bias [Co] or None -> [B, Q, HW]"""
+    """e [T, B, Q, Co], spikes: bf16 Spikes [T*B, C, HW] (mask_feature_spike's output), W [Co, C], bias [Co] or None -> [B, Q, HW].
+    Needs C % 32 == 0 and HW % 4 == 0 (RuntimeError otherwise, nothing launched): see _MaskEinsumFolded."""
     assert isinstance(spikes, Spikes) and spikes.tok is not None and spikes.data.dtype == torch.bfloat16
     return _MaskEinsumFolded.apply(e, spikes.data, spikes.tok, W, bias, float(scale), int(T), int(B), bool(e_exact))
 
