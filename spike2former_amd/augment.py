@@ -1,8 +1,17 @@
-"""`TrainAugment`: the shipped configs' `train_pipeline` -- RandomResize(keep_ratio) -> RandomCrop(cat_max_ratio) -> RandomFlip ->
-PhotoMetricDistortion (mmseg/datasets/transforms/transforms.py:215-331, 575-737; the resize is mmcv's) -- and the training branch of
+"""`TrainAugment`: the shipped configs' `train_pipeline` -- a resize -> RandomCrop(cat_max_ratio) -> RandomFlip ->
+PhotoMetricDistortion (mmseg/datasets/transforms/transforms.py:215-331, 575-737) -- and the training branch of
 `SegDataPreProcessor` as two HIP launches (csrc/augment.hip) from the decoded uint8 pictures of a batch to the [B, 3, Hc, Wc] fp32 /
 [B, Hc, Wc] uint8 tensors a training step replays on.  File loading is not here: the caller hands in decoded
 BGR pictures and raw annotations.
+
+The configs ship two resize rules, and the kernels, functions of the table's (h0, w0, H, W), serve both; only `draw` differs:
+  * RandomResize(scale, ratio_range=(0.5, 2.0), keep_ratio=True), mmcv's: a continuous ratio on a (long, short) box
+    (`resized_size`).  The pipeline of configs/_base_/datasets/*.py, which the two VOC and the two FPN configs under
+    configs/Spike2Former/ keep.
+  * RandomChoiceResize(scales, resize_type='ResizeShortestEdge', max_size), mmcv's choice among mmseg's ResizeShortestEdge
+    (transforms.py:1373-1404): one of 16 short-edge lengths, uniformly, under a cap on the long edge (`shortest_edge_size`).  The
+    pipeline the six MaskFormer / Spike2former configs for ADE20K, Cityscapes and COCO-Stuff set for themselves (320 .. 1280
+    under 2560; Cityscapes 512 .. 2048 under 4096).
 
     aug = TrainAugment.from_cfg(train_pipeline, data_preprocessor, batch_size=2, seed=0)
     step = GraphedHungarianStep(model, example_in, example_seg, red, assign="device")
@@ -12,10 +21,11 @@ BGR pictures and raw annotations.
 
 The host draws the random numbers (`draw`), the kernels are functions of the parameter table.  Two deliberate differences from the
 reference's stream of random numbers, neither of which changes a distribution:
-  * `draw` always consumes the SAME number of variates per image (the ratio, eleven crop origins, the flip and every photometric
-    switch and value, used or not), where the reference draws a new crop origin only after a refused one and a photometric value
-    only behind its switch.  The eleven origins are independent and identically distributed and the chosen one is the first that
-    passes among the first ten, else the eleventh: the distribution of the chosen crop is the reference's.
+  * `draw` always consumes the SAME number of variates per image (the ratio or the choice among the scales, eleven crop origins,
+    the flip and every photometric switch and value, used or not), where the reference draws a new crop origin only after a
+    refused one and a photometric value only behind its switch.  The eleven origins are independent and identically distributed
+    and the chosen one is the first that passes among the first ten, else the eleventh: the distribution of the chosen crop is
+    the reference's.
   * the generator is a `numpy.random.Generator` seeded from (seed, rank), not mmcv's use of the global `numpy.random` state: a run
     here does not reproduce the reference's sequence of augmentations, only its distribution.
 
@@ -37,32 +47,68 @@ PARAM_DTYPE, VIEW_PARAM_DTYPE = ops.PARAM_DTYPE, ops.VIEW_PARAM_DTYPE          #
 VARIATES_PER_IMAGE = 2 * CANDIDATES + 11
 
 PHOTOMETRIC_DEFAULTS = dict(brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18)
-_PIPELINE_ORDER = ("LoadImageFromFile", "LoadAnnotations", "RandomResize", "RandomCrop", "RandomFlip", "PhotoMetricDistortion",
-                   "PackSegInputs")
+_PIPELINE_ORDER = ("LoadImageFromFile", "LoadAnnotations", ("RandomResize", "RandomChoiceResize", "ResizeShortestEdge"), "RandomCrop",
+                   "RandomFlip", "PhotoMetricDistortion", "PackSegInputs")
 _TEST_ORDER = ("LoadImageFromFile", "Resize", "LoadAnnotations", "PackSegInputs")
 _TTA_ORDER = ("Resize", "RandomFlip", "LoadAnnotations", "PackSegInputs")
 
 
-def resized_size(h0, w0, scale, ratio):
-    """mmcv RandomResize(scale, ratio_range, keep_ratio=True) at the drawn ratio -> (H, W): scale = (int(s0 r), int(s1 r)),
-    f = min(long / max(h0, w0), short / min(h0, w0)), (int(h0 f + 0.5), int(w0 f + 0.5)) (mmcv.image.geometric.rescale_size)"""
-    s = (int(scale[0] * ratio), int(scale[1] * ratio))
+def _rescaled(h0, w0, s):
+    """mmcv Resize(scale=s, keep_ratio=True) on an h0 x w0 picture -> (H, W): f = min(max(s) / max(h0, w0), min(s) / min(h0, w0)),
+    (int(h0 f + 0.5), int(w0 f + 0.5)) (mmcv.image.geometric.rescale_size) -- the step every resize rule below ends in"""
     f = min(max(s) / max(h0, w0), min(s) / min(h0, w0))
     return int(h0 * f + 0.5), int(w0 * f + 0.5)
+
+
+def resized_size(h0, w0, scale, ratio):
+    """mmcv RandomResize(scale, ratio_range, keep_ratio=True) at the drawn ratio -> (H, W): scale = (int(s0 r), int(s1 r)), then
+    the keep-ratio rescale to it (`_rescaled`)"""
+    return _rescaled(h0, w0, (int(scale[0] * ratio), int(scale[1] * ratio)))
 
 
 def scale_factor_size(h0, w0, ratio):
     """mmcv Resize(scale_factor=ratio, keep_ratio=True) -> (H, W): first scale = (int(w0 r + 0.5), int(h0 r + 0.5)) (_scale_size),
-    then the keep-ratio rescale TO that size: f = min(max(scale) / max(h0, w0), min(scale) / min(h0, w0)), (int(h0 f + 0.5),
-    int(w0 f + 0.5)) (rescale_size).  (512 x 683 at 1.5 -> 768 x 1025: the width is rounded twice.)"""
-    s = (int(w0 * ratio + 0.5), int(h0 * ratio + 0.5))
-    f = min(max(s) / max(h0, w0), min(s) / min(h0, w0))
-    return int(h0 * f + 0.5), int(w0 * f + 0.5)
+    then the keep-ratio rescale TO that size (`_rescaled`).  (512 x 683 at 1.5 -> 768 x 1025: the width is rounded twice.)"""
+    return _rescaled(h0, w0, (int(w0 * ratio + 0.5), int(h0 * ratio + 0.5)))
+
+
+def shortest_edge_scale(h0, w0, scale, max_size):
+    """mmseg ResizeShortestEdge._get_output_shape (mmseg/datasets/transforms/transforms.py:1373-1400), operation for operation in
+    Python floats -> (new_w, new_h): the short edge to `scale` (an int, or the minimum of a tuple), the long edge in proportion;
+    both scaled down once more if the long edge exceeds max_size; each int(v + 0.5).  A square picture takes the second branch."""
+    size = float(scale) if isinstance(scale, int) else float(min(scale))
+    r = size / min(h0, w0)
+    new_h, new_w = (size, r * w0) if h0 < w0 else (r * h0, size)
+    if max(new_h, new_w) > max_size:
+        r = max_size * 1.0 / max(new_h, new_w)
+        new_h *= r
+        new_w *= r
+    return int(new_w + 0.5), int(new_h + 0.5)
+
+
+def shortest_edge_size(h0, w0, scale, max_size):
+    """mmseg ResizeShortestEdge(scale, max_size) -> (H, W) of the picture after it: `transform` (transforms.py:1402-1404) hands
+    `shortest_edge_scale` to a keep-ratio Resize as its scale, so the size is rounded a second time (`_rescaled`).  (256 x 1000 at
+    1280 under a cap of 2560 -> 655 x 2559: the long edge ends one short of the cap.)"""
+    return _rescaled(h0, w0, shortest_edge_scale(h0, w0, scale, max_size))
 
 
 def _pick(u, n):
     """a uniform variate u in [0, 1) -> an integer in [0, n)"""
     return min(int(u * n), n - 1)
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _checked_scale(s, pairs_only):
+    """one entry of RandomChoiceResize's `scales` -> a positive int or a 2-tuple of positive ints (pairs_only: the latter)"""
+    if _is_int(s) and s > 0 and not pairs_only:
+        return int(s)
+    if isinstance(s, (tuple, list)) and len(s) == 2 and all(_is_int(v) and v > 0 for v in s):
+        return int(s[0]), int(s[1])
+    raise ValueError(f"scales holds {'2-tuples of positive ints' if pairs_only else 'positive ints or 2-tuples of them'}, got {s!r}")
 
 
 def _default_rank():
@@ -81,14 +127,16 @@ def _only(cfg, allowed, what, who):
 
 def _in_order(items, order, who):
     """items: (kind, payload) pairs of a pipeline -> the same pairs, each after the check that its kind is one of `order` and
-    stands behind its predecessor's"""
+    stands behind its predecessor's.  A slot of `order` is a name, or a tuple of names of which a pipeline holds at most one."""
+    slots = [(s,) if isinstance(s, str) else s for s in order]
+    place = {kind: i for i, s in enumerate(slots) for kind in s}
     last = None
     for kind, payload in items:
-        if kind not in order:
+        if kind not in place:
             raise NotImplementedError(f"{who}: transform {kind!r} is not implemented on the device")
-        if last is not None and order.index(kind) <= order.index(last):
+        if last is not None and place[kind] <= place[last]:
             raise NotImplementedError(f"{who}: {kind} after {last}: the device applies the transforms in the order "
-                                      f"{' -> '.join(order)}")
+                                      f"{' -> '.join(' | '.join(s) for s in slots)}")
         last = kind
         yield kind, payload
 
@@ -174,13 +222,35 @@ class _Staged:
 class TrainAugment(_Staged):
     def __init__(self, scale=(2048, 512), ratio_range=(0.5, 2.0), crop_size=(512, 512), cat_max_ratio=0.75, flip_prob=0.5,
                  photometric=True, reduce_zero_label=False, ignore_index=255, mean=None, std=None, bgr_to_rgb=False, pad_val=0,
-                 seg_pad_val=255, batch_size=2, max_source_pixels=2048 * 1024, device="cuda", seed=0, rank=None):
-        """scale / ratio_range: RandomResize's (scale None: no resize; ratio_range None: ratio 1); crop_size (h, w), cat_max_ratio,
-        ignore_index: RandomCrop's; flip_prob: RandomFlip's (horizontal); photometric: True (PhotoMetricDistortion's defaults), a
-        dictionary of its arguments, or None / False; reduce_zero_label: LoadAnnotations'; mean, std, bgr_to_rgb, pad_val,
-        seg_pad_val: SegDataPreProcessor's (its `size` is crop_size).  batch_size images of at most max_source_pixels pixels each
-        fit the staging buffers (4 bytes per pixel: the picture and its annotation).  rank: the data-parallel rank the generator is
-        seeded with next to `seed` (default: the process group's, else $RANK, else 0)."""
+                 seg_pad_val=255, batch_size=2, max_source_pixels=2048 * 1024, device="cuda", seed=0, rank=None, scales=None,
+                 resize_type="ResizeShortestEdge", max_size=None):
+        """scale / ratio_range: RandomResize's (scale None: no resize; ratio_range None: ratio 1); scales / resize_type / max_size:
+        RandomChoiceResize's, INSTEAD of scale (say scale=None): one of `scales` per picture, uniformly -- short-edge lengths (ints,
+        or tuples whose minimum counts) under the cap max_size on the long edge for resize_type "ResizeShortestEdge", (long, short)
+        tuples for the keep-ratio "Resize"; crop_size (h, w), cat_max_ratio, ignore_index: RandomCrop's; flip_prob: RandomFlip's
+        (horizontal); photometric: True (PhotoMetricDistortion's defaults), a dictionary of its arguments, or None / False;
+        reduce_zero_label: LoadAnnotations'; mean, std, bgr_to_rgb, pad_val, seg_pad_val: SegDataPreProcessor's (its `size` is
+        crop_size).  batch_size images of at most max_source_pixels pixels each fit the staging buffers (4 bytes per pixel: the
+        picture and its annotation).  rank: the data-parallel rank the generator is seeded with next to `seed` (default: the
+        process group's, else $RANK, else 0)."""
+        self.scales, self.resize_type, self.max_size = None, None, None
+        if scales is not None:
+            if scale is not None:
+                raise ValueError("one resize rule: scale (RandomResize) or scales (RandomChoiceResize), not both; with scales, "
+                                 "say scale=None")
+            if resize_type not in ("ResizeShortestEdge", "Resize"):
+                raise ValueError(f"resize_type {resize_type!r}: 'ResizeShortestEdge' or 'Resize'")
+            pairs_only = resize_type == "Resize"
+            self.scales = tuple(_checked_scale(s, pairs_only) for s in scales)
+            if not self.scales:
+                raise ValueError("scales is a non-empty list")
+            self.resize_type = resize_type
+            if pairs_only and max_size is not None:
+                raise ValueError("max_size is ResizeShortestEdge's: resize_type 'Resize' takes none")
+            if not pairs_only:
+                if not _is_int(max_size) or max_size <= 0:
+                    raise ValueError(f"resize_type 'ResizeShortestEdge' needs a positive int max_size, got {max_size!r}")
+                self.max_size = int(max_size)
         self.scale = None if scale is None else (int(scale[0]), int(scale[1]))
         self.ratio_range = None if ratio_range is None else (float(ratio_range[0]), float(ratio_range[1]))
         self.crop_size = (int(crop_size), int(crop_size)) if isinstance(crop_size, int) else (int(crop_size[0]), int(crop_size[1]))
@@ -202,10 +272,13 @@ class TrainAugment(_Staged):
     # ------------------------------------------------------------------------------------------------ configuration
     @classmethod
     def from_cfg(cls, train_pipeline, data_preprocessor, **kwargs):
-        """train_pipeline: the list of transform dictionaries of an mmseg config (LoadImageFromFile, LoadAnnotations, RandomResize,
+        """train_pipeline: the list of transform dictionaries of an mmseg config (LoadImageFromFile, LoadAnnotations, a resize,
         RandomCrop, RandomFlip, PhotoMetricDistortion, PackSegInputs, in this order; LoadImageFromFile only marks where the caller's
-        decoded pictures enter); data_preprocessor: the model's SegDataPreProcessor dictionary.  Any other transform, order or option
-        raises NotImplementedError.  kwargs: batch_size, max_source_pixels, device, seed, rank."""
+        decoded pictures enter); data_preprocessor: the model's SegDataPreProcessor dictionary.  The resize is at most one of
+        RandomResize(scale, ratio_range, keep_ratio=True) (the _base_ data sets' pipeline: the VOC and FPN configs),
+        RandomChoiceResize(scales, resize_type, max_size | keep_ratio=True) (with resize_type='ResizeShortestEdge': the ADE20K,
+        Cityscapes and COCO-Stuff MaskFormer configs' own pipeline) and a stand-alone ResizeShortestEdge(scale, max_size).  Any other
+        transform, order or option raises NotImplementedError.  kwargs: batch_size, max_source_pixels, device, seed, rank."""
         who = "TrainAugment"
         a = dict(scale=None, ratio_range=None, cat_max_ratio=1.0, flip_prob=0.0, photometric=None)
         for kind, t in _in_order(((t.get("type"), t) for t in train_pipeline), _PIPELINE_ORDER, who):
@@ -220,6 +293,26 @@ class TrainAugment(_Staged):
                         or not all(isinstance(v, int) for v in t["scale"]):
                     raise NotImplementedError("TrainAugment: RandomResize needs keep_ratio=True and one (long, short) scale")
                 a["scale"], a["ratio_range"] = tuple(t["scale"]), t.get("ratio_range")
+            elif kind == "RandomChoiceResize":          # (mmcv: every option but `scales` goes to the transform `resize_type` names)
+                _only(t, ("scales", "resize_type", "max_size", "keep_ratio"), kind, who)
+                rtype = t.get("resize_type", "Resize")
+                if rtype not in ("Resize", "ResizeShortestEdge"):
+                    raise NotImplementedError(f"TrainAugment: RandomChoiceResize resize_type={rtype!r} is not implemented on the "
+                                              f"device")
+                if not t.get("scales"):
+                    raise NotImplementedError("TrainAugment: RandomChoiceResize needs scales")
+                if rtype == "Resize" and (not t.get("keep_ratio", False) or "max_size" in t):
+                    raise NotImplementedError("TrainAugment: RandomChoiceResize with resize_type='Resize' needs keep_ratio=True "
+                                              "and takes no max_size")
+                if rtype == "ResizeShortestEdge" and ("keep_ratio" in t or "max_size" not in t):
+                    raise NotImplementedError("TrainAugment: RandomChoiceResize with resize_type='ResizeShortestEdge' needs "
+                                              "max_size and takes no keep_ratio")
+                a.update(scales=list(t["scales"]), resize_type=rtype, max_size=t.get("max_size"))
+            elif kind == "ResizeShortestEdge":
+                _only(t, ("scale", "max_size"), kind, who)
+                if "scale" not in t or "max_size" not in t:
+                    raise NotImplementedError("TrainAugment: ResizeShortestEdge needs scale and max_size")
+                a.update(scales=[t["scale"]], resize_type=kind, max_size=t["max_size"])
             elif kind == "RandomCrop":
                 _only(t, ("crop_size", "cat_max_ratio", "ignore_index"), kind, who)
                 a["crop_size"] = t["crop_size"]
@@ -253,7 +346,10 @@ class TrainAugment(_Staged):
         for p, (h0, w0) in zip(params, shapes):
             u = self.rng.random(VARIATES_PER_IMAGE)
             h0, w0 = int(h0), int(w0)
-            if self.scale is None:
+            if self.scales is not None:          # RandomChoiceResize._random_select: numpy.random.randint(len(scales))
+                s = self.scales[_pick(u[0], len(self.scales))]
+                H, W = resized_size(h0, w0, s, 1.0) if self.resize_type == "Resize" else shortest_edge_size(h0, w0, s, self.max_size)
+            elif self.scale is None:
                 H, W = h0, w0
             else:
                 lo, hi = self.ratio_range or (1.0, 1.0)
