@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 40
+#define S2F_ABI_VERSION 41
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -769,7 +769,10 @@ int s2f_lsa_tables_ex(const float* cost, const float* count_full, int64_t* tgt_l
  * 2^24 ulps -- the result is then independent of summation order and equals the reference's bit for bit. */
 int s2f_sdsa_fwd(const float* q, const float* k, const float* v, float* o, float* kv_save, int TB, int heads, int d,
                  int Nq, int Nk, float scale, void* stream);
-/* gq = scale * go kv^T ; gkv = scale * q^T go ; gk = v gkv^T ; gv = k gkv.   gkv_ws: [TB, heads, d, d] scratch. */
+/* gq = scale * go kv^T ; gkv = scale * q^T go ; gk = v gkv^T ; gv = k gkv.   gkv_ws: [TB, heads, d, d] scratch.
+ * Launches (here and in s2f_sdsa_bwd_bf16): the outer product gkv (after its clear when the token axis is split), then the three
+ * applies gq, gk, gv -- independent of one another once gkv exists -- as ONE sdsa_apply_jobs_kernel launch where they take the same
+ * workgroup shape, else gk + gv as one launch and gq as another (100 queries against 4 096 or more keys). */
 int s2f_sdsa_bwd(const float* q, const float* k, const float* v, const float* kv_save, const float* go, float* gq,
                  float* gk, float* gv, float* gkv_ws, int TB, int heads, int d, int Nq, int Nk, float scale,
                  void* stream);
@@ -779,6 +782,18 @@ int s2f_sdsa_bwd(const float* q, const float* k, const float* v, const float* kv
 int s2f_sdsa_kv(const float* k, const float* v, float* kv, int TB, int heads, int d, int N, float alpha, void* stream);
 int s2f_sdsa_apply(const float* x, const float* m, float* y, int TB, int heads, int d, int N, float alpha,
                    int transpose_m, void* stream);
+/* One to three INDEPENDENT applies (no job reads what another writes) of one TB, heads, d; each keeps the workgroup shape it
+ * would have as a launch of its own, jobs that agree on it share one launch (grid z = job), and every output element is computed
+ * as by that launch of its own, bit for bit.  `jobs`: njobs * S2F_SDSA_JOB_WORDS int64 words in HOST memory, per job
+ *   [0] x, device pointer             [1] batch stride of x, in elements      [2] type of x: 0 = fp32, 1 = bf16 spikes
+ *   [3] straight-through mask of x?, device pointer or 0 (layout of s2f_lif_mask_words over the contiguous [TB, C, N]: the
+ *       operand is then bit ? x / D : 0, as `go_mask` of s2f_sdsa_bwd_bf16)   [4] D (1..255; read with a mask only)
+ *   [5] m [TB, heads, d, d] fp32      [6] y, fp32                             [7] batch stride of y, in elements
+ *   [8] N                             [9] alpha: the bits of the float in the low 32 bits      [10] transpose_m
+ * bf16 operands need N and the batch stride to be multiples of 4 and an 8-byte aligned pointer (as s2f_sdsa_fwd_bf16).  Every job
+ * is checked before anything is launched: a malformed job returns S2F_EINVAL / S2F_EALIGN and nothing is written. */
+#define S2F_SDSA_JOB_WORDS 11
+int s2f_sdsa_apply_jobs(const int64_t* jobs, int njobs, int TB, int heads, int d, void* stream);
 
 /* The same core on bf16 spike operands (uint16_t storage; what the neuron kernels write with y_bf16): exact, half the bytes.
  * q / k / v may be channel ranges of ONE tensor (the stacked q|k|v map [TB, 3C, N] of the batched projection chain): each

@@ -139,6 +139,7 @@ SIGNATURES = {
     "s2f_sdsa_lif_fwd_bf16_nomask": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p]),
     "s2f_sdsa_kv": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "s2f_sdsa_apply": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _i, _p]),
+    "s2f_sdsa_apply_jobs": (_i, [_p, _i, _i, _i, _i, _p]),
     "s2f_dcnv3_fwd": (_i, [_p] * 4 + [_i] * 13 + [_f, _p]),
     "s2f_dcnv3_bwd": (_i, [_p] * 7 + [_i] * 13 + [_f, _p]),
     "s2f_grad_sqnorm_parts": (_i64, [_i64]),

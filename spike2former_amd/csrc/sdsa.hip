@@ -13,7 +13,9 @@
 // while it stays below 2^24 ulps: the result is independent of summation order (atomics included) and identical to
 // the reference's fp32 matmuls.  The tests assert that bound instead of a tolerance.
 #include "gemm_common.h"
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 #pragma clang fp contract(fast)
 
@@ -172,18 +174,20 @@ struct LifOut {
   float vth, Df, inv_d;
 };
 
-template <bool TRANS, int JC, typename TX, int NW, bool LO>
-__global__ __launch_bounds__(64 * NW) void apply_kernel(Operand<TX> OX, const float* __restrict__ M, float* __restrict__ Y,
-                                                        int64_t y_batch_stride, int heads, int d, int N, float alpha, LifOut lo) {
+// The workgroup's work, shared by apply_kernel and sdsa_apply_jobs_kernel: `sm` is the kernel's kDMax * NW * JC floats of LDS, `trans`
+// is uniform over the workgroup (a template constant in apply_kernel).
+template <int JC, typename TX, int NW, bool LO, int GB>
+__device__ __forceinline__ void apply_body(float* sm, const bool trans, Operand<TX> OX, const float* __restrict__ M,
+                                           float* __restrict__ Y, int64_t y_batch_stride, int heads, int d, int N, float alpha,
+                                           LifOut lo) {
   constexpr int LD = NW * JC;
-  __shared__ __attribute__((aligned(16))) float sm[kDMax * LD];
   const int bh = blockIdx.y;
   const int tb = bh / heads, h = bh % heads;
   const int C = heads * d;
   const float* m = M + (int64_t)bh * d * d;
   for (int e = threadIdx.x; e < d * LD; e += 64 * NW) {
     const int i = e / LD, j = e % LD;
-    sm[e] = j < d ? (TRANS ? m[j * d + i] : m[i * d + j]) : 0.f;
+    sm[e] = j < d ? (trans ? m[j * d + i] : m[i * d + j]) : 0.f;
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -199,9 +203,9 @@ __global__ __launch_bounds__(64 * NW) void apply_kernel(Operand<TX> OX, const fl
   for (int j = 0; j < JC; ++j) acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0.f;
   // rows of X in groups with all loads of a group issued before the first use: one dependent L2 round trip per row made the
   // loop latency-bound (17.9 us for a 16.8 MB launch).  bf16 rows are held raw (2 registers per row and lane), so a whole
-  // head of d <= 32 rows is ONE group; fp32 rows (4 registers) go 8 at a time.
+  // head of d <= 32 rows is ONE group (GB = 32; sdsa_apply_jobs_kernel: 8, for its registers); fp32 rows (4 registers) go 8 at a time.
   constexpr bool kRaw16 = sizeof(TX) == 2;
-  constexpr int G = kRaw16 ? 32 : 8;
+  constexpr int G = kRaw16 ? GB : 8;
   const bool masked = OX.mask != nullptr;
   for (int i0 = 0; i0 < d; i0 += G) {
     float xv[kRaw16 ? 1 : G][4];
@@ -302,6 +306,57 @@ __global__ __launch_bounds__(64 * NW) void apply_kernel(Operand<TX> OX, const fl
   }
 }
 
+template <bool TRANS, int JC, typename TX, int NW, bool LO>
+__global__ __launch_bounds__(64 * NW) void apply_kernel(Operand<TX> OX, const float* __restrict__ M, float* __restrict__ Y,
+                                                        int64_t y_batch_stride, int heads, int d, int N, float alpha, LifOut lo) {
+  __shared__ __attribute__((aligned(16))) float sm[kDMax * NW * JC];
+  apply_body<JC, TX, NW, LO, 32>(sm, TRANS, OX, M, Y, y_batch_stride, heads, d, N, alpha, lo);
+}
+
+// Up to three INDEPENDENT applies of one workgroup shape as one launch: grid (max ceil(N / 256), TB*heads, jobs), the job is
+// blockIdx.z.  The backward's gq, gk and gv are such a triple once gkv exists; each alone leaves two thirds or more of the wave
+// slots empty (64 - 256 workgroups on 256 CUs), and one after the other they cost three times the latency of one.  A job is what
+// apply_kernel<TRANS, JC, TX, NW, false> takes as arguments, with TX and TRANS as run-time values that are uniform over the
+// workgroup: the body, and with it every load, multiply-add and store of an output element, is that kernel's.  No job may read
+// what another job of the launch writes.
+struct ApplyJob {
+  const void* x;                     // Operand<float> or Operand<unsigned short> (bf16 != 0)
+  int64_t x_batch_stride;
+  const uint64_t* mask;
+  float inv_d;
+  int bf16;
+  const float* m;
+  float* y;
+  int64_t y_batch_stride;
+  int N;
+  float alpha;
+  int trans;
+};
+struct ApplyJobs {
+  ApplyJob j[3];
+};
+
+// bf16 rows are loaded 8 per group here, not a head at once as in apply_kernel (GB): with 32 raw rows in registers the {4, 8} shape
+// takes 116 VGPRs -- two eight-wave workgroups per CU, so the 768 workgroups of three 1 024-token jobs run in two rounds (30.0 us);
+// with 8 it takes 78, three workgroups per CU, all resident at once (24.9 us; the three launches it replaces: 3 x 14.7 us).
+constexpr int kJobRows = 8;
+
+template <int JC, int NW>
+__global__ __launch_bounds__(64 * NW) void sdsa_apply_jobs_kernel(ApplyJobs jobs, int heads, int d) {
+  __shared__ __attribute__((aligned(16))) float sm[kDMax * NW * JC];
+  const ApplyJob& J = jobs.j[blockIdx.z];
+  if ((int64_t)blockIdx.x * 256 >= J.N) return;            // a job with fewer column chunks than the launch: nothing is touched
+  const LifOut none{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f};
+  if (J.bf16)
+    apply_body<JC, unsigned short, NW, false, kJobRows>(
+        sm, J.trans != 0, Operand<unsigned short>{static_cast<const unsigned short*>(J.x), J.x_batch_stride, J.mask, J.inv_d}, J.m, J.y,
+        J.y_batch_stride, heads, d, J.N, J.alpha, none);
+  else
+    apply_body<JC, float, NW, false, kJobRows>(sm, J.trans != 0,
+                                               Operand<float>{static_cast<const float*>(J.x), J.x_batch_stride, J.mask, J.inv_d}, J.m, J.y,
+                                               J.y_batch_stride, heads, d, J.N, J.alpha, none);
+}
+
 // Workgroup shapes of apply_kernel: JC rows per wave (a multiple of 4 that covers d / NW) on NW waves.
 struct ApplyShape {
   int jc, nw;
@@ -311,22 +366,55 @@ constexpr ApplyShape kApplyShapes[] = {
     {4, 4}, {8, 4}, {12, 4}, {16, 4},  // four waves: d <= 16, 32, 48, 64
 };
 
+// The entry of kApplyShapes for a launch of `workgroups` four-wave workgroups: eight waves when the launch cannot fill the chip with
+// four-wave workgroups anyway; the last shape of a wave count takes every larger d as well (the callers bound d).
+int pick_apply_shape(int64_t workgroups, int d) {
+  const bool wide = workgroups <= 1024 && d > 8;
+  const int nw = wide ? 8 : 4;
+  const int jc = ((d + nw - 1) / nw + 3) / 4 * 4;     // rows per wave, rounded up to a multiple of 4
+  int i = 0;
+  while (!(kApplyShapes[i].nw == nw && (jc <= kApplyShapes[i].jc || kApplyShapes[i].jc == (wide ? 8 : 16)))) ++i;
+  return i;
+}
+
 template <bool TRANS, typename TX, bool LO = false>
 void launch_apply(Operand<TX> x, const float* m, float* y, int64_t y_batch_stride, int TB, int heads, int d, int N, float alpha,
                   hipStream_t s, LifOut lo = LifOut{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f}) {
   dim3 grid((N + 255) / 256, TB * heads);
-  // eight waves when the launch cannot fill the chip with four-wave workgroups anyway
-  const bool wide = (int64_t)grid.x * grid.y <= 1024 && d > 8;
-  const int nw = wide ? 8 : 4;
-  const int jc = ((d + nw - 1) / nw + 3) / 4 * 4;     // rows per wave, rounded up to a multiple of 4
-  // the last shape of a wave count takes every larger d as well (the callers bound d)
-  s2f_dispatch<kApplyShapes>([&](const ApplyShape& e) { return e.nw == nw && (jc <= e.jc || e.jc == (wide ? 8 : 16)); }, [&](auto i) {
+  const ApplyShape* shape = &kApplyShapes[pick_apply_shape((int64_t)grid.x * grid.y, d)];
+  s2f_dispatch<kApplyShapes>([&](const ApplyShape& e) { return &e == shape; }, [&](auto i) {
     constexpr ApplyShape A = kApplyShapes[i];
     hipLaunchKernelGGL((apply_kernel<TRANS, A.jc, TX, A.nw, LO>), grid, dim3(64 * A.nw), 0, s, x, m, y, y_batch_stride, heads, d, N,
                        alpha, lo);
   });
 }
 
+// Independent applies, each in the workgroup shape launch_apply would give it alone; those that agree on the shape share a launch.
+void launch_apply_jobs(const ApplyJob* jobs, int njobs, int TB, int heads, int d, hipStream_t s) {
+  int shape[3];
+  for (int a = 0; a < njobs; ++a) shape[a] = pick_apply_shape((int64_t)((jobs[a].N + 255) / 256) * TB * heads, d);
+  for (int a = 0; a < njobs; ++a) {
+    if (shape[a] < 0) continue;                      // went with an earlier job
+    ApplyJobs t{};
+    int n = 0, gx = 0;
+    const int sa = shape[a];
+    for (int b = a; b < njobs; ++b)
+      if (shape[b] == sa) {
+        t.j[n++] = jobs[b];
+        gx = std::max(gx, (jobs[b].N + 255) / 256);
+        shape[b] = -1;
+      }
+    s2f_dispatch<kApplyShapes>([&](const ApplyShape& e) { return &e == &kApplyShapes[sa]; }, [&](auto i) {
+      constexpr ApplyShape A = kApplyShapes[i];
+      hipLaunchKernelGGL((sdsa_apply_jobs_kernel<A.jc, A.nw>), dim3(gx, TB * heads, n), dim3(64 * A.nw), 0, s, t, heads, d);
+    });
+  }
+}
+
+template <typename TX>
+ApplyJob apply_job(Operand<TX> x, const float* m, float* y, int64_t y_batch_stride, int N, float alpha, bool trans) {
+  return ApplyJob{x.base, x.batch_stride, x.mask, x.inv_d, sizeof(TX) == 2, m, y, y_batch_stride, N, alpha, trans};
+}
 
 // Workgroups per (tb, head): the kernel walks its columns in 64-wide steps, each a global -> LDS -> FMA round trip with no
 // prefetch, so a workgroup should own ONE step when there are columns to spare (26 us with 4 steps per workgroup at
@@ -614,16 +702,23 @@ extern "C" int s2f_sdsa_bwd(const float* q, const float* k, const float* v, cons
                             float* gq, float* gk, float* gv, float* gkv_ws, int TB, int heads, int d, int Nq, int Nk,
                             float scale, void* stream) {
   S2F_REQUIRE(q && k && v && kv_save && go && gq && gk && gv && gkv_ws, S2F_EINVAL, "s2f_sdsa_bwd: null pointer");
-  // gq[i][n] = scale * sum_j go[j][n] kv[i][j]
-  int rc = s2f_sdsa_apply(go, kv_save, gq, TB, heads, d, Nq, scale, 1, stream);
+  int rc = check("s2f_sdsa_bwd", TB, heads, d, Nq);
   if (rc) return rc;
+  rc = check("s2f_sdsa_bwd", TB, heads, d, Nk);
+  if (rc) return rc;
+  S2F_REQUIRE(s2f_aligned16(go) && s2f_aligned16(gq) && s2f_aligned16(v) && s2f_aligned16(gk) && s2f_aligned16(k) && s2f_aligned16(gv),
+              S2F_EALIGN, "s2f_sdsa_bwd: go / gq / v / gk / k / gv must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t qs = (int64_t)heads * d * Nq, ks = (int64_t)heads * d * Nk;
   // gkv[i][j] = scale * sum_n q[i][n] go[j][n]
   rc = s2f_sdsa_kv(q, go, gkv_ws, TB, heads, d, Nq, scale, stream);
   if (rc) return rc;
-  // gk[i][n] = sum_j v[j][n] gkv[i][j] ;  gv[j][n] = sum_i k[i][n] gkv[i][j]
-  rc = s2f_sdsa_apply(v, gkv_ws, gk, TB, heads, d, Nk, 1.0f, 1, stream);
-  if (rc) return rc;
-  return s2f_sdsa_apply(k, gkv_ws, gv, TB, heads, d, Nk, 1.0f, 0, stream);
+  // gq[i][n] = scale * sum_j go[j][n] kv[i][j] ;  gk[i][n] = sum_j v[j][n] gkv[i][j] ;  gv[j][n] = sum_i k[i][n] gkv[i][j]
+  const ApplyJob jobs[3] = {apply_job(Operand<float>{go, qs, nullptr, 0.f}, kv_save, gq, qs, Nq, scale, true),
+                            apply_job(Operand<float>{v, ks, nullptr, 0.f}, gkv_ws, gk, ks, Nk, 1.0f, true),
+                            apply_job(Operand<float>{k, ks, nullptr, 0.f}, gkv_ws, gv, ks, Nk, 1.0f, false)};
+  launch_apply_jobs(jobs, 3, TB, heads, d, s);
+  return s2f_check_launch("s2f_sdsa_bwd");
 }
 
 // ---- bf16 spike operands --------------------------------------------------------------------------------------------
@@ -668,12 +763,48 @@ extern "C" int s2f_sdsa_bwd_bf16(const uint16_t* q, const uint16_t* k, const uin
   const int64_t obs = (int64_t)heads * d * Nq;
   // the incoming gradient: of o, or -- with go_mask -- of the spikes y = Q_IFNode(o): straight-through inside the loaders
   const Operand<float> G{go, obs, go_mask, go_mask ? 1.0f / (float)D : 0.f};
-  launch_apply<true>(G, kv_save, gq, gq_batch_stride, TB, heads, d, Nq, scale, s);
   rc = launch_outer_spikes_general(q, q_batch_stride, G, gkv_ws, TB, heads, d, Nq, scale, s);
   if (rc) return rc;
-  launch_apply<true>(Operand<unsigned short>{v, v_batch_stride, nullptr, 0.f}, gkv_ws, gk, gk_batch_stride, TB, heads, d, Nk, 1.0f, s);
-  launch_apply<false>(Operand<unsigned short>{k, k_batch_stride, nullptr, 0.f}, gkv_ws, gv, gv_batch_stride, TB, heads, d, Nk, 1.0f, s);
+  // gq needs kv_save and go only, gk and gv need gkv: three independent applies once gkv exists
+  const ApplyJob jobs[3] = {apply_job(G, kv_save, gq, gq_batch_stride, Nq, scale, true),
+                            apply_job(Operand<unsigned short>{v, v_batch_stride, nullptr, 0.f}, gkv_ws, gk, gk_batch_stride, Nk, 1.0f, true),
+                            apply_job(Operand<unsigned short>{k, k_batch_stride, nullptr, 0.f}, gkv_ws, gv, gv_batch_stride, Nk, 1.0f, false)};
+  launch_apply_jobs(jobs, 3, TB, heads, d, s);
   return s2f_check_launch("s2f_sdsa_bwd_bf16");
+}
+
+extern "C" int s2f_sdsa_apply_jobs(const int64_t* jobs, int njobs, int TB, int heads, int d, void* stream) {
+  S2F_REQUIRE(jobs && njobs >= 1 && njobs <= 3, S2F_EINVAL, "s2f_sdsa_apply_jobs: need 1 to 3 jobs, got %d", njobs);
+  ApplyJob t[3];
+  for (int a = 0; a < njobs; ++a) {                  // every job is checked before the first launch
+    const int64_t* w = jobs + (size_t)a * S2F_SDSA_JOB_WORDS;
+    const void* x = reinterpret_cast<const void*>(static_cast<uintptr_t>(w[0]));
+    const uint64_t* mask = reinterpret_cast<const uint64_t*>(static_cast<uintptr_t>(w[3]));
+    const float* m = reinterpret_cast<const float*>(static_cast<uintptr_t>(w[5]));
+    float* y = reinterpret_cast<float*>(static_cast<uintptr_t>(w[6]));
+    S2F_REQUIRE(x && m && y, S2F_EINVAL, "s2f_sdsa_apply_jobs: job %d: null pointer", a);
+    S2F_REQUIRE(w[8] > 0 && w[8] <= INT32_MAX, S2F_EINVAL, "s2f_sdsa_apply_jobs: job %d: bad N", a);
+    const int N = (int)w[8];
+    int rc = check("s2f_sdsa_apply_jobs", TB, heads, d, N);
+    if (rc) return rc;
+    S2F_REQUIRE(w[2] == 0 || w[2] == 1, S2F_EINVAL, "s2f_sdsa_apply_jobs: job %d: operand type %lld is neither fp32 (0) nor bf16 (1)", a,
+                (long long)w[2]);
+    if (w[2] == 1) {
+      rc = check_bf16("s2f_sdsa_apply_jobs", x, x, x, w[1], w[1], w[1], N, N);
+      if (rc) return rc;
+    } else {
+      S2F_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3u) == 0, S2F_EALIGN, "s2f_sdsa_apply_jobs: job %d: misaligned fp32 operand", a);
+    }
+    S2F_REQUIRE((reinterpret_cast<uintptr_t>(y) & 3u) == 0 && (reinterpret_cast<uintptr_t>(m) & 3u) == 0, S2F_EALIGN,
+                "s2f_sdsa_apply_jobs: job %d: misaligned m / y", a);
+    S2F_REQUIRE(mask == nullptr || (w[4] >= 1 && w[4] <= 255), S2F_EINVAL, "s2f_sdsa_apply_jobs: job %d: bad D", a);
+    float alpha;
+    const uint32_t bits = (uint32_t)w[9];
+    memcpy(&alpha, &bits, sizeof(alpha));
+    t[a] = ApplyJob{x, w[1], mask, mask ? 1.0f / (float)w[4] : 0.f, (int)w[2], m, y, w[7], N, alpha, w[10] != 0};
+  }
+  launch_apply_jobs(t, njobs, TB, heads, d, (hipStream_t)stream);
+  return s2f_check_launch("s2f_sdsa_apply_jobs");
 }
 
 // The same pair WITHOUT the in-range mask (inference: no backward) for any token counts Nq, Nk % 4 == 0 -- the decoder's 100-query
