@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 41
+#define S2F_ABI_VERSION 42
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -428,6 +428,16 @@ int s2f_dense_gemm_bn_lif_fwd(const uint16_t* const* w_packs, int groups, const 
 int s2f_pgemm_dx_f32_grouped(const uint16_t* const* w_packs, int groups, const float* G, int64_t g_batch_stride,
                              int64_t g_group_stride, float* DX, int64_t dx_batch_stride, int64_t dx_group_stride, float* bn_partials,
                              int64_t partials_group_stride, int batch, int Mo, int Ki, int N, void* stream);
+/* Up to four sibling products of s2f_pgemm_nn_bf16 (no bias, three weight terms) in ONE launch (blockIdx.z = group): a_packs and Xs
+ * are HOST arrays of `groups` device pointers (copied into the kernel arguments) -- the packed weight [M][K] and the contiguous bf16
+ * spike map [batch][K][N] of each group; two groups may read one map.  Y [groups][batch][M][N] at y_group_stride elements.  Each
+ * group runs the tile s2f_pgemm_nn_bf16 picks for ONE such product: bit-identical to `groups` single calls.  Only the shapes that
+ * take the register-staged activation rows there (s2f_pgemm_nn_grouped_ok = 1: every N % 8 != 0, and the short contractions);
+ * anything else is S2F_EINVAL before any launch.  The q / k / v projections of the decoder's self-attention
+ * (mmcv_spike/transformer.py:196-361). */
+int s2f_pgemm_nn_grouped_ok(int batch, int M, int N, int K);
+int s2f_pgemm_nn_bf16_grouped(const uint16_t* const* a_packs, const uint16_t* const* Xs, int groups, float* Y, int64_t y_group_stride,
+                              int batch, int M, int N, int K, void* stream);
 /* Implicit 3x3 convolution (stride 1, padding 1) on the same pipeline: Y[b] (M x H W) = A (M x 9 C, the TAP-MAJOR pack of the
  * weight: s2f_pack_bf16x3 mode 1) @ im2col(X[b]), the column matrix never formed.  _bf16: X [batch][C][H][W] bf16 spikes, 3 passes
  * (forward; replaces s2f_spike_conv3x3_fwd_bf16, bit-identical).  _f32: X fp32, split in the kernel, 6 passes -- the INPUT
@@ -457,6 +467,19 @@ int s2f_pgemm_dx_f32_stats(const uint16_t* w_pack, const float* G, int64_t g_bat
                            float* bn_partials, int batch, int Mo, int Ki, int N, void* stream);
 int s2f_bn_partials_finalize(const float* partials, int64_t P, const float* conv_bias, double* sums_out, int64_t N, int64_t C,
                              int64_t L, void* stream);
+/* Up to four sibling train-mode BatchNorms [-> Q_IFNode from rest] of one SHORT-ROW shape (s2f_bn_grouped_ok = 1: L % 4 == 0,
+ * L % 256 != 0, 8 <= N L <= 2048, C >= 32 -- the one-wavefront-per-channel kernels of s2f_bn_act_fwd / _bwd) in ONE launch
+ * (blockIdx.y = group).  z, u_out?, y_out?, g_u?, g_y?, gz [groups][N][C][L]; conv_bias?, running_mean?, running_var?, gamma,
+ * beta, dgamma, dbeta [groups C]; stat [groups][3 C]; mask groups x s2f_bn_mask_words(N, C, L) words.  No residual, membrane,
+ * firing counters or second gradient port; num_batches_tracked is the caller's to count.  Bit-identical to `groups` single calls
+ * on the slices; any other shape is S2F_EINVAL. */
+int s2f_bn_grouped_ok(int64_t N, int64_t C, int64_t L);
+int s2f_bn_act_fwd_grouped(const float* z, const float* conv_bias, float* stat_out, float* running_mean, float* running_var,
+                           const float* gamma, const float* beta, float* u_out, void* y_out, uint64_t* mask, int groups, int64_t N,
+                           int64_t C, int64_t L, float momentum, float eps, float vth, int D, int y_bf16, void* stream);
+int s2f_bn_act_bwd_grouped(const float* z, const float* conv_bias, const float* stat, const float* gamma, const float* g_u,
+                           const float* g_y, const uint64_t* mask, float* gz, float* dgamma, float* dbeta, int groups, int64_t N,
+                           int64_t C, int64_t L, float vth, int D, void* stream);
 /* s2f_bn_act_bwd with a SECOND gradient of the spike map (g_y2?, NULL = absent): the neuron fused into this BatchNorm has two
  * readers (the backbone taps feed the next stage and the pixel decoder's lateral convolution, mask2former's pixel_decoder.py:316-472;
  * DCNv3's offset and mask convolutions share offset_spike, dcnv3.py:209-214), and g_y + g_y2 is formed where g_y is read instead of

@@ -116,6 +116,11 @@ SIGNATURES = {
     "s2f_pgemm_nn_bf16_stats": (_i, [_p] * 4 + [_i] * 4 + [_p]),
     "s2f_pgemm_conv3x3_bf16_stats": (_i, [_p] * 4 + [_i] * 5 + [_p]),
     "s2f_pgemm_dx_f32_grouped": (_i, [_p, _i, _p, _i64, _i64, _p, _i64, _i64, _p, _i64] + [_i] * 4 + [_p]),
+    "s2f_pgemm_nn_grouped_ok": (_i, [_i] * 4),
+    "s2f_pgemm_nn_bf16_grouped": (_i, [_p, _p, _i, _p, _i64] + [_i] * 4 + [_p]),
+    "s2f_bn_grouped_ok": (_i, [_i64] * 3),
+    "s2f_bn_act_fwd_grouped": (_i, [_p] * 10 + [_i] + [_i64] * 3 + [_f, _f, _f, _i, _i, _p]),
+    "s2f_bn_act_bwd_grouped": (_i, [_p] * 10 + [_i] + [_i64] * 3 + [_f, _i, _p]),
     "s2f_dense_gemm_bn_lif_fwd": (_i, [_p, _i, _p, _i64, _i64, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p]),
     "s2f_pgemm_dx_f32_stats": (_i, [_p, _p, _i64, _p, _i64, _p] + [_i] * 4 + [_p]),
     "s2f_bn_partials_finalize": (_i, [_p, _i64, _p, _p, _i64, _i64, _i64, _p]),

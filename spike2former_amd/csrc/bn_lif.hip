@@ -1360,13 +1360,28 @@ inline bool small_rows_ok(int64_t N, int64_t C, int64_t L) {
   return (L & 3) == 0 && (L & 255) != 0 && N * L <= 64 * 4 * kSmallIters && N * L >= 8 && C >= 32;
 }
 
-template <bool LIF, bool HAS_V, bool YB>
+// GROUPED: blockIdx.y selects one of the sibling BatchNorms of one shape (the q / k / v chains of the decoder's self-attention) --
+// maps group-outermost [groups][N][C][L], per-channel vectors [groups C], stat [groups][3 C], mask [groups][C kSmallIters 4]:
+// every pointer moves to its group's slice and the body below is that of ONE BatchNorm.  No residual, membrane or firing counters.
+template <bool LIF, bool HAS_V, bool YB, bool GROUPED = false>
 __global__ __launch_bounds__(64) void bn_small_fwd_kernel(
     const float* __restrict__ z, const float* __restrict__ bias, float* __restrict__ stat, float* __restrict__ running_mean,
     float* __restrict__ running_var, long long* __restrict__ num_batches, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ res, float* __restrict__ u_out, const float* __restrict__ v_in,
     float* __restrict__ y, float* __restrict__ v_out, uint64_t* __restrict__ mask, unsigned long long* __restrict__ stats,
     int N, int C, int L, double inv_count, float unbias, float momentum, float eps, float vth, float Df) {
+  if constexpr (GROUPED) {
+    static_assert(!HAS_V, "grouped form: neurons from rest");
+    const int64_t g = blockIdx.y, map = g * N * C * L, vec = g * C;
+    z += map;
+    if (bias) bias += vec;
+    stat += 3 * vec;
+    if (running_mean) running_mean += vec, running_var += vec;
+    gamma += vec, beta += vec;
+    if (u_out) u_out += map;
+    if (LIF) y = YB ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(y) + map) : y + map;
+    if (mask) mask += vec * kSmallIters * 4;
+  }
   const int c = blockIdx.x, lane = threadIdx.x;
   const int per_row = L >> 2, groups = N * per_row;
   const float b = bias ? bias[c] : 0.f;
@@ -1463,12 +1478,25 @@ __global__ __launch_bounds__(64) void bn_small_fwd_kernel(
   }
 }
 
-template <bool GU, bool GY, bool GV>
+template <bool GU, bool GY, bool GV, bool GROUPED = false>
 __global__ __launch_bounds__(64) void bn_small_bwd_kernel(
     const float* __restrict__ z, const float* __restrict__ bias, const float* __restrict__ stat,
     const float* __restrict__ gamma, const float* __restrict__ g_u, const float* __restrict__ g_y,
     const float* __restrict__ g_v, const uint64_t* __restrict__ mask, float* __restrict__ gz, float* __restrict__ g_res,
     float* __restrict__ dgamma, float* __restrict__ dbeta, int N, int C, int L, double inv_count, float vth, float Df) {
+  if constexpr (GROUPED) {          // the layout of the grouped forward (above)
+    static_assert(!GV, "grouped form: no membrane gradient");
+    const int64_t g = blockIdx.y, map = g * N * C * L, vec = g * C;
+    z += map;
+    if (bias) bias += vec;
+    stat += 3 * vec;
+    gamma += vec;
+    if (GU) g_u += map;
+    if (GY) g_y += map;
+    if (GY) mask += vec * kSmallIters * 4;
+    gz += map;
+    dgamma += vec, dbeta += vec;
+  }
   const int c = blockIdx.x, lane = threadIdx.x;
   const int per_row = L >> 2, groups = N * per_row;
   const float b = bias ? bias[c] : 0.f, mean = stat[c], rstd = stat[C + c], g_ = gamma[c];
@@ -2155,4 +2183,65 @@ extern "C" int s2f_bn2_act_bwd(const float* z, const float* conv_bias, const flo
   S2F_REQUIRE(gz && gamma2, S2F_EINVAL, "s2f_bn2_act_bwd: null gz / second BatchNorm");
   return bn_act_bwd_impl(z, conv_bias, stat, gamma, g_u, g_y, g_v, mask, nullptr, gz, g_residual, dgamma, dbeta, N, C, L, 1, vth, D,
                          stream, nullptr, Bn2Bwd{gamma2, dgamma2, dbeta2, eps2});
+}
+
+// ---- the sibling BatchNorms of one stage as ONE launch (train mode, short rows) -------------------------------------------------------
+extern "C" int s2f_bn_grouped_ok(int64_t N, int64_t C, int64_t L) {
+  return (N > 0 && C > 0 && L > 0 && C <= 5120 && small_rows_ok(N, C, L)) ? 1 : 0;
+}
+
+// `groups` (1..4) train-mode BatchNorms [-> Q_IFNode from rest] of one shape (s2f_bn_grouped_ok: the one-wavefront-per-channel kernel of
+// s2f_bn_act_fwd): z, u_out, y [groups][N][C][L]; conv_bias, running_mean, running_var, gamma, beta [groups C]; stat_out
+// [groups][3 C]; mask groups x s2f_bn_mask_words(N, C, L) words.  Bit-identical to `groups` calls of s2f_bn_act_fwd on the slices;
+// num_batches_tracked is the caller's to count.
+extern "C" int s2f_bn_act_fwd_grouped(const float* z, const float* conv_bias, float* stat_out, float* running_mean,
+                                      float* running_var, const float* gamma, const float* beta, float* u_out, void* y_out,
+                                      uint64_t* mask, int groups, int64_t N, int64_t C, int64_t L, float momentum, float eps,
+                                      float vth, int D, int y_bf16, void* stream) {
+  float* y = reinterpret_cast<float*>(y_out);
+  S2F_REQUIRE(z && stat_out && gamma && beta && groups >= 1 && groups <= 4, S2F_EINVAL,
+              "s2f_bn_act_fwd_grouped: null z/stat/gamma/beta / 1..4 groups");
+  S2F_REQUIRE((running_mean == nullptr) == (running_var == nullptr), S2F_EINVAL, "s2f_bn_act_fwd_grouped: one running statistic only");
+  S2F_REQUIRE(u_out || y, S2F_EINVAL, "s2f_bn_act_fwd_grouped: neither u_out nor y requested");
+  S2F_REQUIRE(!(y && y_bf16) || s2f_bf16_spikes_exact(D), S2F_EINVAL,
+              "s2f_bn_act_fwd_grouped: bf16 spikes need D a power of two <= 128 (D=%d)", D);
+  S2F_REQUIRE(s2f_bn_grouped_ok(N, C, L), S2F_EINVAL,
+              "s2f_bn_act_fwd_grouped: N=%lld C=%lld L=%lld is no short-row shape (L %% 4 == 0, 8 <= N L <= 2048, C >= 32)",
+              (long long)N, (long long)C, (long long)L);
+  S2F_REQUIRE(s2f_aligned16(z) && s2f_aligned16(u_out) && s2f_aligned16(y), S2F_EALIGN,
+              "s2f_bn_act_fwd_grouped: tensors must be 16-byte aligned");
+  const double count = (double)N * (double)L;
+  const float unbias = count > 1 ? (float)(count / (count - 1.0)) : 1.0f;
+  for_fwd_variant(y, nullptr, y_bf16, [&](auto i) {
+    constexpr FwdVariant V = kFwdVariants[i];
+    if constexpr (!V.has_v)
+      S2F_LAUNCH(true, true, (bn_small_fwd_kernel<V.lif, V.has_v, V.yb, true>), dim3((unsigned)C, (unsigned)groups), dim3(64), 0,
+                 (hipStream_t)stream, z, conv_bias, stat_out, running_mean, running_var, (long long*)nullptr, gamma, beta,
+                 (const float*)nullptr, u_out, (const float*)nullptr, y, (float*)nullptr, mask, (unsigned long long*)nullptr, (int)N,
+                 (int)C, (int)L, 1.0 / count, unbias, momentum, eps, vth, (float)D);
+  });
+  return s2f_check_launch("s2f_bn_act_fwd_grouped");
+}
+
+// The backward of s2f_bn_act_fwd_grouped: g_u / g_y, gz [groups][N][C][L]; dgamma, dbeta [groups C]; stat and mask as written there.
+extern "C" int s2f_bn_act_bwd_grouped(const float* z, const float* conv_bias, const float* stat, const float* gamma,
+                                      const float* g_u, const float* g_y, const uint64_t* mask, float* gz, float* dgamma,
+                                      float* dbeta, int groups, int64_t N, int64_t C, int64_t L, float vth, int D, void* stream) {
+  S2F_REQUIRE(z && stat && gamma && gz && dgamma && dbeta && groups >= 1 && groups <= 4, S2F_EINVAL,
+              "s2f_bn_act_bwd_grouped: null pointer / 1..4 groups");
+  S2F_REQUIRE(g_u || g_y, S2F_EINVAL, "s2f_bn_act_bwd_grouped: no incoming gradient");
+  S2F_REQUIRE(!g_y || mask, S2F_EINVAL, "s2f_bn_act_bwd_grouped: spike gradients need the in-range mask");
+  S2F_REQUIRE(s2f_bn_grouped_ok(N, C, L), S2F_EINVAL,
+              "s2f_bn_act_bwd_grouped: N=%lld C=%lld L=%lld is no short-row shape (L %% 4 == 0, 8 <= N L <= 2048, C >= 32)",
+              (long long)N, (long long)C, (long long)L);
+  S2F_REQUIRE(s2f_aligned16(z) && s2f_aligned16(g_u) && s2f_aligned16(g_y) && s2f_aligned16(gz), S2F_EALIGN,
+              "s2f_bn_act_bwd_grouped: tensors must be 16-byte aligned");
+  for_bwd_grads(g_u, g_y, nullptr, [&](auto i) {
+    constexpr BwdGrads G = kBwdGrads[i];
+    if constexpr (!G.gv)
+      S2F_LAUNCH(true, true, (bn_small_bwd_kernel<G.gu, G.gy, G.gv, true>), dim3((unsigned)C, (unsigned)groups), dim3(64), 0,
+                 (hipStream_t)stream, z, conv_bias, stat, gamma, g_u, g_y, (const float*)nullptr, mask, gz, (float*)nullptr, dgamma,
+                 dbeta, (int)N, (int)C, (int)L, 1.0 / ((double)N * (double)L), vth, (float)D);
+  });
+  return s2f_check_launch("s2f_bn_act_bwd_grouped");
 }

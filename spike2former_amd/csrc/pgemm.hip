@@ -984,11 +984,28 @@ __device__ __forceinline__ f32x4 convp_fix(f32x4 v, ConvPredB p) {
 // G: K steps per barrier ("super-step": G consecutive 32-wide steps staged, waited for and multiplied together; Kb % G == 0).  The
 // short products of the 32x32 stage (K = 256 .. 1 024, one workgroup per CU) spend each step waiting for the activation rows loaded
 // ONE step earlier: half as many, twice as long steps halve the exposed round trips (the input-gradient kernel's KS, round 5).
-template <int MI, int NJ, int WMW, int WNW, int BT, bool CONV = true, bool STATS = false, int EPI = 0, int G = 1>
+// GROUPED (plain product, bf16 rows, plain store): blockIdx.z selects one of up to four independent products of the same shape -- the
+// sibling q / k / v projections of the decoder's self-attention, each with its own packed weight and its own activation map (q and
+// k read one spike map, v another), Y group-outermost [groups][batch][M][N].  Three 64-workgroup launches become one of 192.
+struct ConvGroups {
+  const unsigned short* ap[4];
+  const void* x[4];
+  int64_t y_stride;          // elements between the outputs of consecutive groups
+};
+
+template <int MI, int NJ, int WMW, int WNW, int BT, bool CONV = true, bool STATS = false, int EPI = 0, int G = 1, bool GROUPED = false>
 __global__ __launch_bounds__(64 * WMW * WNW) void pg_conv_kernel(const unsigned short* __restrict__ Ap, const void* __restrict__ Xv,
                                                                 const float* __restrict__ bias, float* __restrict__ Y, int M,
                                                                 int N, int K, int Kb, int n_tiles, int m_tiles, Conv3 geo,
-                                                                float* __restrict__ part = nullptr, BnLifEpi ep = BnLifEpi{}) {
+                                                                float* __restrict__ part = nullptr, BnLifEpi ep = BnLifEpi{},
+                                                                ConvGroups grp = ConvGroups{}) {
+  if constexpr (GROUPED) {
+    static_assert(!CONV && !STATS && EPI == 0 && BT == 1, "grouped form: the plain product of bf16 rows, plain store");
+    const int g = blockIdx.z;
+    Ap = grp.ap[g];
+    Xv = grp.x[g];
+    Y += g * grp.y_stride;
+  }
   constexpr int BM = 32 * MI * WMW, BN = 32 * NJ * WNW, NW = WMW * WNW, T = 64 * NW;
   static_assert(BN == 128, "the activation tile is 128 pixels wide");
   constexpr int A_BYTES = 3 * BM * 64, B_TERM = 32 * BN * 2, B_BYTES = BT * B_TERM, STAGE = A_BYTES + B_BYTES;
@@ -1298,16 +1315,19 @@ struct ConvForm {
   int bt, epi;  // bf16 terms of the activation (3: fp32 input); 1: the BatchNorm -> neuron epilogue
   bool stats;
   int g;        // K steps per barrier
+  bool grouped;
   unsigned cfgs;
 };
 constexpr ConvForm kConvForms[] = {
-    {3, 0, false, 1, cfg_set(1, 2, 3, 4)},           // fp32 activation (3x3 only)
-    {1, 0, false, 1, cfg_set(1, 2, 3, 4, 6, 7, 8)},  // plain
-    {1, 0, true, 1, cfg_set(1, 2, 3, 4, 6, 7, 8)},   // + statistics
-    {1, 0, false, 2, cfg_set(1, 2, 3, 4, 7, 8)},     // two steps per barrier (not on the four-wavefront rows tile)
-    {1, 0, true, 2, cfg_set(1, 2, 3, 4, 7, 8)},
-    {1, 1, false, 1, cfg_set(2, 3, 4, 6, 7, 8)},     // inference epilogue
-    {1, 1, false, 2, cfg_set(2, 3, 4, 7, 8)},
+    {3, 0, false, 1, false, cfg_set(1, 2, 3, 4)},           // fp32 activation (3x3 only)
+    {1, 0, false, 1, false, cfg_set(1, 2, 3, 4, 6, 7, 8)},  // plain
+    {1, 0, true, 1, false, cfg_set(1, 2, 3, 4, 6, 7, 8)},   // + statistics
+    {1, 0, false, 2, false, cfg_set(1, 2, 3, 4, 7, 8)},     // two steps per barrier (not on the four-wavefront rows tile)
+    {1, 0, true, 2, false, cfg_set(1, 2, 3, 4, 7, 8)},
+    {1, 1, false, 1, false, cfg_set(2, 3, 4, 6, 7, 8)},     // inference epilogue
+    {1, 1, false, 2, false, cfg_set(2, 3, 4, 7, 8)},
+    {1, 0, false, 1, true, cfg_set(6, 7, 8)},               // 1..4 sibling products (gridDim.z): the rows tiles only
+    {1, 0, false, 2, true, cfg_set(7, 8)},
 };
 
 constexpr bool conv_g2_built(int cfg) {
@@ -1373,9 +1393,11 @@ bool launch_pg_nn(int cfg, int terms, int epi, bool ex_form, hipStream_t s, cons
 }
 
 // One launch of pg_conv_kernel; two_steps(workgroups) says whether this launch wants two K steps per barrier where that is built.
+// groups > 0: the grouped form (gridDim.z = groups, operands from grp); the tile and the steps per barrier are those of ONE product.
 template <class TwoSteps>
 bool launch_pg_conv(int cfg, bool conv, int bt, int epi, const TwoSteps& two_steps, hipStream_t s, const uint16_t* a_pack, const void* X,
-                    const float* bias, float* Y, int batch, int M, int N, int K, int Kb, Conv3 geo, float* part, const BnLifEpi& ep) {
+                    const float* bias, float* Y, int batch, int M, int N, int K, int Kb, Conv3 geo, float* part, const BnLifEpi& ep,
+                    int groups = 0, const ConvGroups& grp = ConvGroups{}) {
   const int n_tiles = (N + 127) / 128;
   bool ok = false;
   s2f_dispatch<kConvTiles>([&](const PgTile& e) { return e.cfg == cfg && (e.extra != 0) == conv; }, [&](auto i) {
@@ -1384,12 +1406,15 @@ bool launch_pg_conv(int cfg, bool conv, int bt, int epi, const TwoSteps& two_ste
     const bool stats = part != nullptr && bt == 1;
     const int g = (conv_g2_built(T.cfg) && two_steps((int64_t)n_tiles * m_tiles * batch)) ? 2 : 1;
     ok = s2f_dispatch<kConvForms>(
-        [&](const ConvForm& e) { return e.bt == bt && e.epi == epi && e.stats == stats && e.g == g && (e.cfgs >> T.cfg & 1); }, [&](auto f) {
+        [&](const ConvForm& e) {
+          return e.bt == bt && e.epi == epi && e.stats == stats && e.g == g && e.grouped == (groups > 0) && (e.cfgs >> T.cfg & 1);
+        },
+        [&](auto f) {
           constexpr ConvForm F = kConvForms[f];
           if constexpr (F.cfgs >> T.cfg & 1)
-            S2F_LAUNCH(true, true, (pg_conv_kernel<T.MI, T.NJ, T.WMW, T.WNW, F.bt, T.extra != 0, F.stats, F.epi, F.g>),
-                       dim3(n_tiles * m_tiles, batch), dim3(T.threads()), 0, s, a_pack, X, bias, Y, M, N, K, Kb, n_tiles, m_tiles, geo,
-                       part, ep);
+            S2F_LAUNCH(true, true, (pg_conv_kernel<T.MI, T.NJ, T.WMW, T.WNW, F.bt, T.extra != 0, F.stats, F.epi, F.g, F.grouped>),
+                       dim3(n_tiles * m_tiles, batch, groups > 0 ? groups : 1), dim3(T.threads()), 0, s, a_pack, X, bias, Y, M, N, K, Kb,
+                       n_tiles, m_tiles, geo, part, ep, grp);
         });
   });
   return ok;
@@ -1483,6 +1508,49 @@ extern "C" int s2f_pgemm_nn_bf16_ex(const uint16_t* a_pack, int64_t a_batch_stri
 extern "C" int s2f_pgemm_nn_bf16(const uint16_t* a_pack, const uint16_t* X, const float* bias, float* Y, int batch, int M,
                                  int N, int K, int terms, int cfg, void* stream) {
   return pgemm_nn_impl(a_pack, X, bias, Y, batch, M, N, K, terms, cfg, nullptr, stream);
+}
+
+// What s2f_pgemm_nn_bf16 would run for this shape, if that is the register-staged form: the tile configuration (6 / 7 / 8), else 0.
+static int nn_rows_cfg(int batch, int M, int N, int K) {
+  if (!(batch > 0 && batch < 65536 && M > 0 && N >= 8 && (N & 3) == 0 && K > 0)) return 0;
+  static const char* force = getenv("S2F_PG_CFG");
+  const int c = pick_cfg_nn(M, N, K, batch, force ? atoi(force) : 0);
+  if (c == 7 || c == 8) return c;
+  return (c == 6 || (N & 7) != 0) ? 6 : 0;
+}
+
+extern "C" int s2f_pgemm_nn_grouped_ok(int batch, int M, int N, int K) { return nn_rows_cfg(batch, M, N, K) != 0 ? 1 : 0; }
+
+// `groups` (1..4) sibling products  Y[g][b] = A_g @ X_g[b]  of one shape as ONE launch: a_packs[g] = s2f_pack_bf16x3 of the weight
+// [M][K], Xs[g] a contiguous bf16 spike map [batch][K][N] (two groups may read the same map), Y [groups][batch][M][N] at
+// y_group_stride elements.  No bias, all three weight terms.  Each group runs the tile, and the steps per barrier, that
+// s2f_pgemm_nn_bf16 picks for ONE such product: the results are bit-identical to `groups` single calls.  Only shapes that take
+// the register-staged activation rows there (s2f_pgemm_nn_grouped_ok); anything else is S2F_EINVAL before any launch.
+extern "C" int s2f_pgemm_nn_bf16_grouped(const uint16_t* const* a_packs, const uint16_t* const* Xs, int groups, float* Y,
+                                         int64_t y_group_stride, int batch, int M, int N, int K, void* stream) {
+  S2F_REQUIRE(a_packs && Xs && Y && groups >= 1 && groups <= 4, S2F_EINVAL, "s2f_pgemm_nn_bf16_grouped: null pointer / 1..4 groups");
+  S2F_REQUIRE(batch > 0 && batch < 65536 && M > 0 && N >= 8 && K > 0, S2F_EINVAL, "s2f_pgemm_nn_bf16_grouped: bad sizes");
+  S2F_REQUIRE((N & 3) == 0, S2F_EINVAL, "s2f_pgemm_nn_bf16_grouped: N=%d must be a multiple of 4", N);
+  S2F_REQUIRE(y_group_stride >= (int64_t)batch * M * N, S2F_EINVAL, "s2f_pgemm_nn_bf16_grouped: the outputs of two groups overlap");
+  const int c = nn_rows_cfg(batch, M, N, K);
+  S2F_REQUIRE(c != 0, S2F_EINVAL, "s2f_pgemm_nn_bf16_grouped: [%d x %d] @ [%d x %d x %d] does not run on the register-staged form", M,
+              K, batch, K, N);
+  ConvGroups grp{};
+  for (int g = 0; g < groups; ++g) {
+    S2F_REQUIRE(a_packs[g] && Xs[g], S2F_EINVAL, "s2f_pgemm_nn_bf16_grouped: null pack / activation map %d", g);
+    S2F_REQUIRE(s2f_aligned16(a_packs[g]) && s2f_aligned16(Xs[g]), S2F_EALIGN,
+                "s2f_pgemm_nn_bf16_grouped: pack / activation map %d must be 16-byte aligned", g);
+    grp.ap[g] = a_packs[g];
+    grp.x[g] = Xs[g];
+  }
+  S2F_REQUIRE(s2f_aligned16(Y) && (y_group_stride & 3) == 0, S2F_EALIGN,
+              "s2f_pgemm_nn_bf16_grouped: Y and its group stride must keep 16-byte alignment");
+  grp.y_stride = y_group_stride;
+  const int Kb = (K + PK - 1) / PK;
+  const bool ok = launch_pg_conv(c, false, 1, 0, [&](int64_t wgs) { return nn_super_steps(Kb, wgs); }, (hipStream_t)stream, grp.ap[0],
+                                 grp.x[0], nullptr, Y, batch, M, N, K, Kb, Conv3{0, 0, 0}, nullptr, BnLifEpi{}, groups, grp);
+  S2F_REQUIRE(ok, S2F_EINVAL, "s2f_pgemm_nn_bf16_grouped: no kernel instance for cfg %d", c);
+  return s2f_check_launch("s2f_pgemm_nn_bf16_grouped");
 }
 
 extern "C" int64_t s2f_bn_partials_count(int batch, int N) { return (int64_t)batch * ((N + 127) / 128); }

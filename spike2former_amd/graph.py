@@ -66,14 +66,14 @@ class _Captured:
         # eager forward after an optimiser step re-converts INTO the same buffers, ops/wcache.py, and replaces tables)
         self._converted = ops.conversion_state()
         # ... and the launch structure the op-layer switches selected (ops.cfg): see _begin
-        self._settings = ops.cfg.snapshot()
+        self._settings = ops.cfg.launch_snapshot()
         return graphs
 
     def _begin(self, x):
         """Before a replay.  Replaying under other op-layer settings than the captured ones would mix two configurations
         silently -- e.g. eager steps of a comparison running with a switch flipped while the graph still replays the old
         kernels.  The optimizer's per-parameter (lr, weight_decay) table is uploaded (a scheduler may have rewritten it)."""
-        now = ops.cfg.snapshot()
+        now = ops.cfg.launch_snapshot()
         if now != self._settings:
             diff = {k: (self._settings[k], now[k]) for k in now if now[k] != self._settings.get(k)}
             raise RuntimeError(f"this hipGraph was captured under different op-layer settings (captured, now): {diff}; re-capture")

@@ -278,6 +278,64 @@ class MultiHeadAttentionBlock(nn.Module):
         self.attn_spike = _lif()
         self.out_conv = proj()
         spikes_in(self.q_conv[0], self.k_conv[0], self.v_conv[0], self.out_conv[0])
+        self._flatten_qkv()
+
+    # ---- q / k / v as sibling chains of ONE launch per stage (ops.cfg.DECODER_SIBLINGS) ---------------------------------------------
+    # On the decoder's 100-query maps each of conv1x1 -> BatchNorm -> neuron is a latency-bound launch of one workgroup round or less,
+    # and the three chains of the self-attention are independent copies of it.  They run group-outermost in one [3, t*b, dim, n]
+    # buffer: one grouped GEMM, one grouped BatchNorm + neuron, the attention core reading the three slices in place; backward
+    # likewise.  The parameters stay the reference's separate tensors (state_dict keys unchanged); `_flatten_qkv` lays the
+    # BatchNorm twins and conv biases out back to back so that their concatenations exist without copies.
+    def _flatten_qkv(self):
+        chains = (self.q_conv, self.k_conv, self.v_conv)
+        for name in ("weight", "bias", "running_mean", "running_var"):
+            ops.flatten_together([getattr(c[1], name) for c in chains])
+        ops.flatten_together([c[0].bias for c in chains])
+
+    def _apply(self, fn, *a, **k):
+        super()._apply(fn, *a, **k)            # .to() / .cuda() re-allocate every tensor: lay the twins out again
+        self._flatten_qkv()
+        return self
+
+    def siblings_ok(self, q_spikes, k_spikes, v_spikes):
+        """The three projection chains can run as sibling launches: switch on, the self-attention's operands (q and k read ONE spike
+        map), train-mode BatchNorms that agree in momentum and eps, pure output neurons with the same parameters, bf16 spike maps
+        [t, b, dim, n] of a shape the grouped kernels take."""
+        chains = (self.q_conv, self.k_conv, self.v_conv)
+        bns = [c[1] for c in chains]
+        lifs = (self.q_spike, self.k_spike, self.v_spike)
+        xs = (q_spikes, k_spikes, v_spikes)
+        if not (ops.cfg.DECODER_SIBLINGS and not ops.cfg.BN_PARTIALS_SINGLE
+                and all(isinstance(x, ops.Spikes) and x.data.dim() == 4 for x in xs)
+                and q_spikes.data.data_ptr() == k_spikes.data.data_ptr()
+                and all(b.training and b.affine and b.running_mean is not None and b.momentum is not None for b in bns)
+                and len({(b.momentum, b.eps) for b in bns}) == 1
+                and all(isinstance(n.v, float) and not n.keep_membrane and n.stats is None and not n._forward_hooks
+                        and not n._forward_pre_hooks for n in lifs)
+                and len({(n.D, n.v_threshold) for n in lifs}) == 1 and ops.spikes_bf16_ok(lifs[0].D)
+                and all(c[0].bias is not None for c in chains)):
+            return False
+        t, b, dim, n = q_spikes.shape
+        return (ops.spike_gemm_siblings_ok([x.flatten(0, 1) for x in xs], [c[0].weight.view(dim, -1) for c in chains])
+                and bool(ops.lib.s2f_bn_grouped_ok(t * b, dim, n)))
+
+    def _project_siblings(self, q_spikes, k_spikes, v_spikes):
+        """-> the q | k | v spikes as one bf16 ops.Spikes [3, t*b, dim, n] (siblings_ok): two launches forward, two backward"""
+        chains = (self.q_conv, self.k_conv, self.v_conv)
+        bns = [c[1] for c in chains]
+        dim = q_spikes.shape[2]
+        z = ops.spike_gemm_siblings([x.flatten(0, 1) for x in (q_spikes, k_spikes, v_spikes)], [c[0].weight.view(dim, -1) for c in chains])
+        rm, wb1 = ops.cat_buffers([b.running_mean for b in bns])
+        rv, wb2 = ops.cat_buffers([b.running_var for b in bns])
+        n0 = self.q_spike
+        _, y = ops.bn_act_siblings(z, ops.cat_params([c[0].bias.detach() for c in chains]), ops.cat_params([b.weight for b in bns]),
+                                   ops.cat_params([b.bias for b in bns]), rm, rv, bns[0].momentum, bns[0].eps, lif=True, want_pre=False,
+                                   D=n0.D, vth=n0.v_threshold)
+        wb1(); wb2()
+        torch._foreach_add_([b.num_batches_tracked for b in bns], 1)
+        for m in (self.q_spike, self.k_spike, self.v_spike):
+            m.v = 0.0
+        return y
 
     @staticmethod
     def _proj(spike_in, conv, spike_out, x, channel_major=False, fired=None):
@@ -332,7 +390,12 @@ class MultiHeadAttentionBlock(nn.Module):
             t, b, nq, dim = query.shape
         qcm = query_channel_major
 
-        if kv_projected is not None:
+        qkv = None
+        if (kv_projected is None and kv_spikes is not None and q_spikes is not None and attn_mask is None
+                and self.siblings_ok(q_spikes, *kv_spikes)):
+            # the self-attention's three chains as sibling launches, group-outermost (ops.cfg.DECODER_SIBLINGS)
+            qkv = self._project_siblings(q_spikes, *kv_spikes)
+        elif kv_projected is not None:
             # keys / values do not depend on the query: the head projected them for every layer ahead of the query chain
             q = self._proj(self.q_conv_spike, self.q_conv, self.q_spike, query, qcm, q_spikes)
             k, v, handle = kv_projected
@@ -345,7 +408,9 @@ class MultiHeadAttentionBlock(nn.Module):
                 lambda: self._proj(self.v_conv_spike, self.v_conv, self.v_spike, value, cm, fv),
                 lambda: self._proj(self.q_conv_spike, self.q_conv, self.q_spike, query, qcm, q_spikes)],
                 inputs=(query, key, value, fk, fv))
-        if attn_mask is not None:
+        if qkv is not None:
+            o = ops.sdsa_siblings(qkv, self.num_heads, 1.0 / (self.embed_dim ** 0.5), lif=self.attn_spike)
+        elif attn_mask is not None:
             # scores.masked_fill(mask, 0) (transformer.py:266-269, 349-352): the explicit O(nq nk d) form (ops.sdsa_masked); never
             # taken by the MaskFormerHead path, whose cross_attn_mask is None (dense_heads/maskformer_head.py:554-564)
             o = self.attn_spike.fire(ops.sdsa_masked(q, k, v, attn_mask, self.num_heads, 1.0 / (self.embed_dim ** 0.5), b))

@@ -24,12 +24,12 @@ class _OpsModule(types.ModuleType):
     """module attribute access for the switches forwards to ops.cfg (they are not module attributes)"""
 
     def __getattr__(self, name):
-        if name in config.Config.FIELDS:
+        if name in config.Config.FIELDS or name in config.Config.LAUNCH_FIELDS:
             return getattr(cfg, name)
         raise AttributeError(f"module 'spike2former_amd.ops' has no attribute {name!r}")
 
     def __setattr__(self, name, value):
-        if name in config.Config.FIELDS:
+        if name in config.Config.FIELDS or name in config.Config.LAUNCH_FIELDS:
             setattr(cfg, name, value)
         elif name.isupper() and name not in self.__dict__:
             raise AttributeError(f"module 'spike2former_amd.ops' has no switch {name!r}: the switches live in ops.cfg "

@@ -42,13 +42,21 @@ class _SDSASpikes(torch.autograd.Function):
     """The attention core on bf16 spike operands (s2f.h s2f_sdsa_*_bf16), optionally fused with the neuron that follows it
     (s2f_sdsa_lif_fwd_bf16: kv on the matrix cores, o never written, spikes + mask + counters from the epilogue).
     packed: `qd` is the stacked q|k|v map [TB, 3C, N] of the batched projection chain (one autograd handle `qt`, one
-    [TB, 3C, N] gradient -- no split / stack copies); otherwise three [TB, C, N*] tensors with a handle each."""
+    [TB, 3C, N] gradient -- no split / stack copies); packed == 2: `qd` is the group-outermost buffer [3, TB, C, N] of the decoder's
+    sibling projection chains (q, k, v = its three contiguous slices; one handle, one [3, TB, C, N] gradient); otherwise three
+    [TB, C, N*] tensors with a handle each."""
 
     @staticmethod
     def forward(ctx, qd, kd, vd, qt, kt, vt, heads, scale, packed, fuse, D, vth, stats):
         qd = qd.contiguous()
         TB = qd.shape[0]
-        if packed:
+        if packed == 2:
+            _, TB, C, Nq = qd.shape
+            Nk = Nq
+            qs = ks = vs = C * Nq
+            qp = qd.data_ptr()
+            kp, vp = qp + 2 * TB * C * Nq, qp + 4 * TB * C * Nq
+        elif packed:
             C, Nq = qd.shape[1] // 3, qd.shape[2]
             Nk = Nq
             qs = ks = vs = 3 * C * Nq
@@ -93,7 +101,13 @@ class _SDSASpikes(torch.autograd.Function):
         g = g.contiguous()
         dev = g.device
         qp = qd.data_ptr()
-        if packed:
+        if packed == 2:
+            G = torch.empty(3, TB, C, Nq, dtype=torch.float32, device=dev)
+            gq, gk, gv = G.data_ptr(), G.data_ptr() + 4 * TB * C * Nq, G.data_ptr() + 8 * TB * C * Nq
+            gs = (C * Nq,) * 3
+            kp, vp = qp + ctx.ptrs_of[0], qp + ctx.ptrs_of[1]
+            out = (G, None, None)
+        elif packed:
             G = torch.empty(TB, 3 * C, Nq, dtype=torch.float32, device=dev)
             gq, gk, gv = G.data_ptr(), G.data_ptr() + 4 * C * Nq, G.data_ptr() + 8 * C * Nq
             gs = (3 * C * Nq,) * 3
@@ -179,9 +193,18 @@ def sdsa_packed(y, heads, scale, lif=None):
     return _sdsa_spikes(y.data, None, None, y.tok, None, None, heads, scale, True, lif)
 
 
+def sdsa_siblings(y, heads, scale, lif=None):
+    """The same with q, k, v = the three [TB, C, N] slices of one group-outermost bf16 spike map y [3, TB, C, N] (the decoder's
+    sibling projection chains, ops.bn_act_siblings): read in place, one [3, TB, C, N] gradient."""
+    if not (isinstance(y, Spikes) and y.tok is not None and y.data.dim() == 4 and y.shape[0] == 3 and y.shape[3] % 4 == 0
+            and y.shape[2] // heads <= 64):
+        raise RuntimeError("sdsa_siblings: a bf16 spike map [3, TB, C, N] with N % 4 == 0 and heads of at most 64 channels wanted")
+    return _sdsa_spikes(y.data, None, None, y.tok, None, None, heads, scale, 2, lif)
+
+
 def _sdsa_spikes(qd, kd, vd, qt, kt, vt, heads, scale, packed, lif):
-    C = qd.shape[1] // 3 if packed else qd.shape[1]
-    Nq = qd.shape[2]
+    C = qd.shape[2] if packed == 2 else qd.shape[1] // 3 if packed else qd.shape[1]
+    Nq = qd.shape[-1]
     Nk = Nq if packed else kd.shape[2]
     pure = (lif is not None and isinstance(lif.v, float) and not lif.keep_membrane
             and not lif._forward_hooks and not lif._forward_pre_hooks)          # hooks want the module call
@@ -204,7 +227,7 @@ def _sdsa_spikes(qd, kd, vd, qt, kt, vt, heads, scale, packed, lif):
         lif.v = 0.0
         return Spikes(y, _new_tok(y))
     if fuse and lif.stats is not None:
-        lif.stats_elems += qd.shape[0] * C * Nq
+        lif.stats_elems += (qd.shape[1] if packed == 2 else qd.shape[0]) * C * Nq
     o, ydata = _SDSASpikes.apply(qd, kd, vd, qt, kt, vt, heads, scale, packed, fuse, lif.D if fuse else 8,
                                  lif.v_threshold if fuse else 1.0, lif.stats if fuse else None)
     if fuse:

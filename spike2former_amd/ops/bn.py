@@ -11,12 +11,20 @@ class _BNAct(torch.autograd.Function):
     (statistics, apply) and two backward (reduce, apply).  Returns (u, y, v_out); unrequested ones are empty.
     up_lo: the residual given as the low-resolution map [N, C, H/2, W/2] whose exact-2x bilinear up-sampling is added -- formed inside
     the apply kernel (s2f_bn_act_up_fwd; the caller has asked s2f_bn_up_ok), its gradient returned through the up-sampling's adjoint.
-    up_skip: also hand up_lo back as a pass-through for a second reader, whose gradient that adjoint sums (as ops.upsample_bilinear)."""
+    up_skip: also hand up_lo back as a pass-through for a second reader, whose gradient that adjoint sums (as ops.upsample_bilinear).
+    groups > 1: z is the group-outermost buffer [G, N, C, *] of G sibling BatchNorms of one short-row shape (bn_siblings_ok), the
+    per-channel vectors and running buffers their concatenations [G C]: ONE launch forward, one backward (s2f_bn_act_*_grouped),
+    u / y / gz in z's layout.  Train mode, neurons from rest; no residual, firing counters or num_batches_tracked (the caller counts)."""
 
     @staticmethod
     def forward(ctx, z, conv_bias, gamma, beta, residual, v_in, running_mean, running_var, nbt, training, momentum,
-                eps, lif_on, want_pre, keep_v, D, vth, stats, bf16, partials=None, up_lo=None, up_skip=False):
+                eps, lif_on, want_pre, keep_v, D, vth, stats, bf16, partials=None, up_lo=None, up_skip=False, groups=1):
         _need_cuda(z, conv_bias, gamma, beta, residual, v_in, up_lo)
+        ctx.groups = groups
+        if groups > 1:
+            return _BNAct._forward_siblings(ctx, z, conv_bias, gamma, beta, running_mean, running_var, momentum, eps, lif_on, want_pre,
+                                            D, vth, bf16, groups, plain=(residual is None and v_in is None and nbt is None and training
+                                                                         and not keep_v and stats is None and up_lo is None))
         up_in = up_lo
         z = z.contiguous()
         N, C = z.shape[0], z.shape[1]
@@ -93,6 +101,39 @@ class _BNAct(torch.autograd.Function):
         return tuple(outs) + (border, ydata, tok2, through)
 
     @staticmethod
+    def _forward_siblings(ctx, z, conv_bias, gamma, beta, running_mean, running_var, momentum, eps, lif_on, want_pre, D, vth, bf16,
+                          G, plain):
+        z = z.contiguous()
+        N, C = z.shape[1], z.shape[2]
+        L = z.numel() // (G * N * C)
+        if not (plain and z.shape[0] == G and gamma.numel() == G * C and lib.s2f_bn_grouped_ok(N, C, L)):
+            raise RuntimeError(f"bn_act(groups={G}): train-mode sibling BatchNorms of one short-row shape only; got z {tuple(z.shape)}")
+        dev = z.device
+        stat = torch.empty(G, 3 * C, dtype=torch.float32, device=dev)      # per group: mean, rstd, BN(0) border (s2f.h)
+        bf16 = bool(bf16) and lif_on
+        u = torch.empty_like(z) if want_pre else None
+        y = torch.empty(z.shape, dtype=torch.bfloat16 if bf16 else torch.float32, device=dev) if lif_on else None
+        need_grad = any(ctx.needs_input_grad[:4])
+        mask = torch.empty(G * int(lib.s2f_bn_mask_words(N, C, L)), dtype=torch.int64, device=dev) if (lif_on and need_grad) else None
+        n = z.numel()
+        alg = 4 * n * (1 + bool(want_pre) + bool(lif_on))
+        _time_next("bn_lif_fwd" if lif_on else "bn_fwd", alg, moved=alg - (2 * n if bf16 else 0))
+        check(lib.s2f_bn_act_fwd_grouped(_ptr(z), _ptr(conv_bias), _ptr(stat), _ptr(running_mean), _ptr(running_var), _ptr(gamma),
+                                         _ptr(beta), _ptr(u), _ptr(y), _ptr(mask), G, N, C, L, momentum, eps, vth, D, int(bf16),
+                                         _stream()), "s2f_bn_act_fwd_grouped")
+        ctx.save_for_backward(z, conv_bias, gamma, stat, mask)
+        ctx.cfg = (N, C, L, True, D, vth, False, conv_bias is not None)
+        ctx.up = None
+        ctx.set_materialize_grads(False)
+        border = stat.view(G, 3, C)[:, 2]
+        ydata, tok2, through = z.new_empty(0), z.new_empty(0), z.new_empty(0)
+        if bf16:
+            ydata, y = y, _new_tok(z)
+        outs = [t if t is not None else z.new_empty(0) for t in (u, y, None)]
+        ctx.mark_non_differentiable(border, ydata, tok2, through, *[o for o, t in zip(outs, (u, y, None)) if t is None])
+        return tuple(outs) + (border, ydata, tok2, through)
+
+    @staticmethod
     def backward(ctx, g_u, g_y, g_v, g_border, _g_ydata, g_y2, g_through=None):
         z, conv_bias, gamma, stat, mask = ctx.saved_tensors
         N, C, L, training, D, vth, has_res, has_bias = ctx.cfg
@@ -100,12 +141,25 @@ class _BNAct(torch.autograd.Function):
         def prep(g):
             return None if (g is None or g.numel() == 0) else g.contiguous()
         g_u, g_y, g_v, g_y2 = prep(g_u), prep(g_y), prep(g_v), prep(g_y2)
+        if ctx.groups > 1:
+            if g_u is None and g_y is None:
+                return (None,) * 23
+            G = ctx.groups
+            gz = torch.empty_like(z)
+            dgamma = torch.empty(G * C, dtype=torch.float32, device=z.device)
+            dbeta = torch.empty(G * C, dtype=torch.float32, device=z.device)
+            alg = 4 * z.numel() * (2 + (g_u is not None) + (g_y is not None))
+            _time_next("bn_lif_bwd" if g_y is not None else "bn_bwd", alg)
+            check(lib.s2f_bn_act_bwd_grouped(_ptr(z), _ptr(conv_bias), _ptr(stat), _ptr(gamma), _ptr(g_u), _ptr(g_y), _ptr(mask),
+                                             _ptr(gz), _ptr(dgamma), _ptr(dbeta), G, N, C, L, vth, D, _stream()),
+                  "s2f_bn_act_bwd_grouped")
+            return (gz, None, dgamma, dbeta) + (None,) * 19          # (train mode: the conv bias has no gradient, as below)
         if g_y is None:
             g_y, g_y2 = g_y2, None
         if g_y2 is not None and not lib.s2f_bn_bwd_ports_ok(N, C, L, int(training), D):
             g_y, g_y2 = g_y + g_y2, None          # (a kernel form without the second port: the add the autograd engine would have made)
         if g_u is None and g_y is None and g_v is None:
-            return (None,) * 20 + (g_through, None)
+            return (None,) * 20 + (g_through, None, None)
         dev = z.device
         gz = torch.empty_like(z)
         g_res = torch.empty_like(z) if ((has_res and ctx.needs_input_grad[4]) or (ctx.up is not None and ctx.needs_input_grad[20])) else None
@@ -133,8 +187,8 @@ class _BNAct(torch.autograd.Function):
                 g_lo = torch.empty(N, C, h, w, dtype=torch.float32, device=dev)
                 check(lib.s2f_upsample2x_bwd_add(_ptr(g_res), _ptr(None if g_through is None else g_through.contiguous()), _ptr(g_lo),
                                                  N * C, h, w, _stream()), "s2f_upsample2x_bwd_add")
-            return (gz, g_bias, dgamma, dbeta, None) + (None,) * 15 + (g_lo, None)
-        return (gz, g_bias, dgamma, dbeta, g_res) + (None,) * 17
+            return (gz, g_bias, dgamma, dbeta, None) + (None,) * 15 + (g_lo, None, None)
+        return (gz, g_bias, dgamma, dbeta, g_res) + (None,) * 18
 
 
 def _partial_slots(z):
@@ -154,6 +208,26 @@ def bn_up_ok(z, lo, training, D=8):
             and z.numel() and lo.shape[:2] == z.shape[:2] and (2 * lo.shape[2], 2 * lo.shape[3]) == tuple(z.shape[2:])):
         return False
     return bool(lib.s2f_bn_up_ok(z.shape[0], z.shape[1], z.shape[2], z.shape[3], 1, D))
+
+
+def bn_siblings_ok(z):
+    """z [G, N, C, L] fp32: the G train-mode BatchNorms (+ neurons) of its slices can run as one launch (bn_act_siblings)"""
+    return bool(z.dim() == 4 and 1 < z.shape[0] <= 4 and z.is_cuda and z.dtype == torch.float32 and z.numel()
+                and lib.s2f_bn_grouped_ok(z.shape[1], z.shape[2], z.shape[3]))
+
+
+def bn_act_siblings(z, conv_bias, gamma, beta, running_mean, running_var, momentum, eps, lif=False, want_pre=True, D=8, vth=1.0):
+    """The train-mode BatchNorms [-> Q_IFNode from rest] of G sibling chains as ONE launch forward and one backward: z [G, N, C, L]
+    (bn_siblings_ok), conv_bias / gamma / beta / running_mean / running_var their concatenations [G C] (ops.cat_params,
+    ops.cat_buffers); the running statistics are updated in place, num_batches_tracked is the caller's to count.
+    -> (u [G, N, C, L] or None, y as Spikes [G, N, C, L] or None); slice g is what bn_act gives for z[g], bit for bit."""
+    bf16 = bool(lif) and spikes_bf16_ok(D) and z[0].numel() % 4 == 0
+    u, y, _v, _border, ydata, _tok2, _thr = _BNAct.apply(z, conv_bias, gamma, beta, None, None, running_mean, running_var, None, True,
+                                                         momentum, eps, lif, want_pre, False, D, vth, None, bf16, None, None, False,
+                                                         int(z.shape[0]))
+    if lif:
+        y = Spikes(ydata, y) if bf16 else Spikes(y, None)
+    return (u if want_pre else None), (y if lif else None)
 
 
 def bn_act(z, conv_bias, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, residual=None,

@@ -13,9 +13,12 @@ class Config:
               "CONV3X3_DX_IMPLICIT", "DEFER_DW", "DW_PIPE", "BN_PARTIALS", "BN_PARTIALS_SINGLE", "DENSE_GROUPED", "RESPLIT_IN_GRAPH",
               "FANOUT_PORTS", "GLUE_MODE", "STRICT_GLUE", "STRICT", "GENERAL_RESIZE")
     RUNTIME = ("KERNEL_EVENTS", "GRAD_SINKS", "WGRAD_STREAM", "BRANCH_STREAMS", "LONG_STREAMS")          # objects, not settings
+    # A/B switches of changes whose comparison is still on record as open or fresh: part of what a captured graph depends on
+    # (launch_snapshot) next to the settled list above, which tests/test_host_logic.py pins name by name
+    LAUNCH_FIELDS = ("DECODER_SIBLINGS",)
 
     def __setattr__(self, name, value):
-        if name not in self.FIELDS:
+        if name not in self.FIELDS and name not in self.LAUNCH_FIELDS:
             raise AttributeError(f"ops.cfg has no switch {name!r} (the switches are ops.cfg.FIELDS)")
         object.__setattr__(self, name, value)
 
@@ -57,10 +60,17 @@ class Config:
         # GENERAL_RESIZE: bilinear resizes that are not the exact-2x even-width case (the predict path at image sizes that are not
         # multiples of 32) run on csrc/resize.hip; False sends them to ATen through the `upsample_bilinear` fall-back site (A/B runs)
         self.GENERAL_RESIZE = True
+        # DECODER_SIBLINGS: the q / k / v projection chains of the decoder's self-attention (conv1x1 -> BatchNorm -> neuron on the
+        # 100-token maps) run as ONE grouped launch per stage, forward and backward, instead of three (S2F_DEC_SIBLINGS=0: one by one)
+        self.DECODER_SIBLINGS = os.environ.get("S2F_DEC_SIBLINGS", "1") != "0"
 
     def snapshot(self):
         """the settings a captured hipGraph depends on (scalars only)"""
         return {n: getattr(self, n) for n in self.FIELDS if n not in self.RUNTIME and n not in ("STRICT", "STRICT_GLUE")}          # (STRICT selects no launch)
+
+    def launch_snapshot(self):
+        """snapshot() plus the LAUNCH_FIELDS: everything that selects the launches a captured hipGraph bakes in"""
+        return dict(self.snapshot(), **{n: getattr(self, n) for n in self.LAUNCH_FIELDS})
 
 
 cfg = Config()

@@ -303,6 +303,80 @@ class _SpikeGemm(torch.autograd.Function):
         return _grad_pair(ctx.has_tok, gx) + (gw, gb, None)
 
 
+def spike_gemm_siblings_ok(xs, ws):
+    """The G sibling products  ws[g] [M, K] @ xs[g] [B, K, L]  can run as ONE launch (spike_gemm_siblings): 1..4 bf16 spike maps of
+    one shape with their autograd handles, contiguous and 16-byte aligned, on a shape s2f_pgemm_nn_bf16 runs with register-staged
+    activation rows (every L % 8 != 0, and the short contractions), M >= 16 for the matrix-core weight gradient."""
+    if not (1 <= len(xs) <= 4 and len(xs) == len(ws) and cfg.SPIKE_GEMM_ENABLED and cfg.SPIKE_GEMM_TERMS == 3):
+        return False
+    x0, w0 = xs[0], ws[0]
+    if not (isinstance(x0, Spikes) and x0.data.dim() == 3 and w0.dim() == 2):
+        return False
+    B, K, L = x0.shape
+    M = w0.shape[0]
+    for x, w in zip(xs, ws):
+        if not (isinstance(x, Spikes) and x.tok is not None and x.data.dtype == torch.bfloat16 and x.data.is_cuda
+                and x.data.is_contiguous() and x.data.data_ptr() % 16 == 0 and tuple(x.shape) == (B, K, L)
+                and w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == (M, K)):
+            return False
+    return M >= 16 and bool(lib.s2f_pgemm_nn_grouped_ok(B, M, L, K))
+
+
+class _SpikeGemmSiblings(torch.autograd.Function):
+    """Y[g][b] = W_g @ X_g[b] for G sibling 1x1 convolutions of one shape, each on its own bf16 spike map (two may read the same
+    map) -- the q / k / v projections of the decoder's self-attention -- as ONE launch forward (s2f_pgemm_nn_bf16_grouped) into a
+    group-outermost [G, B, M, L] buffer, and backward as one grouped input-gradient launch (s2f_pgemm_dx_f32_grouped) plus G weight
+    gradients in the deferred queue.  Bit-identical to G _SpikeGemm calls; every group's map gets its own gradient.
+    args: G x (data, handle, weight [M, K])."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        G = len(args) // 3
+        xs, ws = [args[3 * g] for g in range(G)], [args[3 * g + 2] for g in range(G)]
+        _need_cuda(*ws)
+        B, K, L = xs[0].shape
+        M = ws[0].shape[0]
+        if cfg.SPIKE_GEMM_CHECK:
+            assert all(_is_spike_grid(x) for x in xs), "not a spike tensor"
+        y = torch.empty(G, B, M, L, dtype=torch.float32, device=xs[0].device)
+        packs = (ctypes.c_void_p * G)(*[pack_weight(w).data_ptr() for w in ws])
+        maps = (ctypes.c_void_p * G)(*[x.data_ptr() for x in xs])
+        _time_next("spike_gemm_fwd", 4 * G * B * L * (K + M), 2 * G * B * M * L * K, moved=G * B * L * (2 * K + 4 * M))
+        check(lib.s2f_pgemm_nn_bf16_grouped(packs, maps, G, _ptr(y), B * M * L, B, M, L, K, _stream()), "s2f_pgemm_nn_bf16_grouped")
+        ctx.save_for_backward(*xs, *ws)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        G = len(ctx.saved_tensors) // 2
+        xs, ws = ctx.saved_tensors[:G], ctx.saved_tensors[G:]
+        if gy is None:
+            return (None,) * (3 * G)
+        gy = gy.contiguous()
+        B, K, L = xs[0].shape
+        M = ws[0].shape[0]
+        gx = None
+        if any(ctx.needs_input_grad[3 * g + 1] for g in range(G)):
+            gx = torch.empty(G, B, K, L, dtype=torch.float32, device=gy.device)
+            packs = (ctypes.c_void_p * G)(*[pack_weight(w).data_ptr() for w in ws])
+            _time_next("dx_gemm", 4 * G * B * L * (K + M), 2 * G * B * M * L * K)
+            check(lib.s2f_pgemm_dx_f32_grouped(packs, G, _ptr(gy), M * L, B * M * L, _ptr(gx), K * L, B * K * L, 0, 0, B, M, K, L,
+                                               _stream()), "s2f_pgemm_dx_f32_grouped")
+        out = []
+        for g in range(G):
+            gw = _spike_dw(gy[g], xs[g], ws[g], B, M, K, L, pipe=True) if ctx.needs_input_grad[3 * g + 2] else None
+            out += [None, gx[g] if (gx is not None and ctx.needs_input_grad[3 * g + 1]) else None, gw]
+        return tuple(out)
+
+
+def spike_gemm_siblings(xs, ws):
+    """xs: G bf16 Spikes [B, K, L], ws: G weights [M, K] (spike_gemm_siblings_ok) -> fp32 [G, B, M, L], one launch."""
+    args = []
+    for x, w in zip(xs, ws):
+        args += [x.data, x.tok, w]
+    return _SpikeGemmSiblings.apply(*args)
+
+
 def dx_gemm(w2d, gy):
     """Input gradient of a 1x1 convolution: gx[b] = W^T @ gy[b]  (two general fp32 operands): the transposed product on the
     forward pack of W with gy split hi + mid + lo in the kernel (s2f_pgemm_dx_f32, 6 passes)."""
