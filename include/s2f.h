@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 42
+#define S2F_ABI_VERSION 43
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -41,7 +41,7 @@ const char* s2f_last_error(void);
  * (hipExtLaunchKernelGGL start/stop events = the dispatch packet's own begin/end timestamps, what rocprofv3 reports).
  *   s2f_event_create/destroy: a hipEvent_t as void*.
  *   s2f_time_next_call(start, stop): arms THIS thread; the next s2f_lif_fwd / s2f_lif_bwd / s2f_bn_stats /
- *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist / s2f_seg_confusion call stamps `start` with the begin of
+ *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist / s2f_seg_confusion / s2f_seg_draw call stamps `start` with the begin of
  *       its first kernel and `stop` with the end of its last one, then disarms.  Not valid during stream capture.
  *   s2f_event_elapsed_us: stop - start in microseconds (both must have completed: synchronise first). */
 void* s2f_event_create(void);
@@ -612,6 +612,33 @@ int s2f_seg_hist(const void* pred, int pred_dtype, const void* label, int label_
 #define S2F_SEG_CONF_GLOBAL 2
 int s2f_seg_confusion(const void* pred, int pred_dtype, const void* label, int label_dtype, int64_t label_row_stride,
                       int64_t label_pixel_stride, int W, int64_t HW, int K, int ignore_index, int flags, int64_t* matrix, void* stream);
+
+/* ---- visualisation: the panel SegLocalVisualizer draws (csrc/segdraw.hip, ABI 43) -------------------------------------------------
+ * SegLocalVisualizer._draw_sem_seg and add_datasample's np.concatenate((gt, pred), axis=1) (mmseg/visualization/
+ * local_visualizer.py:79-118, 218-219: np.unique, one full-image masked write per class present, a float64 blend, a truncation, on
+ * the host) as ONE launch per image.
+ * image: uint8 [H, W, 3].  gt: NULL, or a contiguous [H, W] map, S2F_SEG_LABEL_U8 or S2F_SEG_LABEL_I64.  pred: NULL, or a contiguous
+ * [H, W] map, S2F_SEG_PRED_I64 or S2F_SEG_PRED_F32 (at least one of the two; the dtype code of a NULL map is ignored).  palette:
+ * uint8 [K, 3] RGB in device memory.  out: uint8 [H, P W, 3] RGB, P the number of maps given: with both, the ground truth is the
+ * left half of every row and the prediction the right half.
+ * For map value l and source channel value v:  c = palette[l][ch] when 0 <= l < K, else 0;  the output byte is
+ *     (uint8) trunc( fl64(v * (1 - alpha)) + fl64(c * alpha) )
+ * with 1 - alpha formed once in double on the host -- exactly (image * (1 - alpha) + mask * alpha).astype(np.uint8).  The two
+ * products and the sum are three separately rounded fp64 operations (a contracted evaluation differs at hundreds of (v, c) pairs).
+ * A float pred paints class c iff it equals c exactly (-0.0 is class 0; NaN, +-inf and non-integers paint nothing), an int64 value
+ * is compared as 64 bits (2^40 + 3 is not class 3).  Stated deviation: a NEGATIVE label paints nothing, where the reference would
+ * index palette[-1]; no arg-max produces one.
+ * flags: S2F_SEG_DRAW_BGR -- image is BGR (as mmcv decodes and TestAugment stages it) and is swapped on read; the palette and out
+ * stay RGB.  S2F_SEG_REDUCE_ZERO_LABEL -- gt only: the raw annotation is mapped first (0 -> 255, 255 -> 255, else - 1), exactly as
+ * in s2f_seg_hist.  Any other bit is S2F_EINVAL.
+ * Bounds (S2F_EINVAL before any launch): H, W > 0, H W < 2^31 - 8, 0 < K <= S2F_SEG_HIST_MAX_CLASSES (the palette in LDS),
+ * 0 <= alpha <= 1, gt or pred, non-null image, palette and out.  image, gt as uint8, palette and out may start at ANY byte (picture
+ * b of a staged batch starts at byte 3 h0 w0 b, the right panel of a row at byte 3 W): the kernel moves whole aligned 32-bit words
+ * and peels the bytes at the ends of its pieces; an int64 / fp32 map is aligned to its element (S2F_EALIGN).  Only the 3 H P W
+ * bytes of out are written.  Nothing is allocated and nothing synchronises: capturable in a hipGraph. */
+#define S2F_SEG_DRAW_BGR 4
+int s2f_seg_draw(const uint8_t* image, const void* gt, int gt_dtype, const void* pred, int pred_dtype, const uint8_t* palette, int K,
+                 double alpha, int flags, int H, int W, uint8_t* out, void* stream);
 
 /* ---- training augmentation: the configs' train_pipeline + SegDataPreProcessor on the device (csrc/augment.hip, ABI 37) ------------
  * RandomResize(keep_ratio) -> RandomCrop(cat_max_ratio) -> RandomFlip -> PhotoMetricDistortion (mmseg datasets/transforms/

@@ -13,12 +13,13 @@ from .loss import MaskFormerLoss, seg_to_instances  # noqa: F401
 from .maskformer_head import MaskFormerHead  # noqa: F401
 from .neuron import LIFNode, Q_IFNode, Quant, reset_net, set_keep_membrane  # noqa: F401
 from .pixel_decoder import DCNTransformerEncoderPixelDecoder  # noqa: F401
-from .registry import HOOKS, METRICS, MODELS, ConfigDict, register_upstream  # noqa: F401
+from .registry import HOOKS, METRICS, MODELS, VISUALIZERS, ConfigDict, register_upstream  # noqa: F401
 from . import reparam  # noqa: F401
 from .segmentor import EncoderDecoder, ResetModelHook, headline_loss  # noqa: F401
 from .tta import SegTTAModel  # noqa: F401
 from .metrics import ConfusionMatrix, IoUMetric, evaluate  # noqa: F401
 from .augment import TestAugment, TrainAugment  # noqa: F401
+from .visualization import SegLocalVisualizer, SegVisualizationHook  # noqa: F401
 from .train import LinearThenPoly, OptimWrapper, parse_losses, train_step  # noqa: F401
 
 __version__ = "0.1.0"

@@ -72,6 +72,7 @@ SIGNATURES = {
     "s2f_tta_finish": (_i, [_p, _p, _p, _i, _i64, _i, _f, _p]),
     "s2f_seg_hist": (_i, [_p, _i, _p, _i, _i64, _i64, _i, _i64, _i, _i, _i, _p, _p]),
     "s2f_seg_confusion": (_i, [_p, _i, _p, _i, _i64, _i64, _i, _i64, _i, _i, _i, _p, _p]),
+    "s2f_seg_draw": (_i, [_p, _p, _i, _p, _i, _p, _i, ctypes.c_double, _i, _i, _i, _p, _p]),
     "s2f_aug_param_bytes": (_i, []),
     "s2f_aug_crop_stats": (_i, [_p, _i64, _p, _i, _i, _i, _i, _i, ctypes.c_double, _p, _p]),
     "s2f_aug_apply": (_i, [_p, _i64, _p, _p, _i, _i, _i] + [_f] * 6 + [_i, _f, _i, _i, _p, _p, _p]),

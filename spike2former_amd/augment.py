@@ -668,6 +668,17 @@ class TestAugment(_Staged):
             return dict(inputs=inputs, data_samples=samples, preprocessed=[True] * len(inputs))
         return dict(inputs=inputs[0], data_samples=samples[0], preprocessed=True)
 
+    def sources(self):
+        """-> the pictures `stage` last copied as they lie in device memory: a uint8 [B, h0, w0, 3] BGR view of the staging twin
+        (`is_bgr` is True on it), valid until the next `stage` -- what a SegVisualizationHook(source=aug) draws into."""
+        st = self._staged
+        if st is None or self._dev is None:
+            raise RuntimeError("TestAugment.sources before stage")
+        d0, (h0, w0) = self._table_cap, st["shape"]
+        pictures = self._dev[d0:d0 + st["n_img"]].view(st["B"], h0, w0, 3)
+        pictures.is_bgr = True
+        return pictures
+
     def __call__(self, images, segs=None, img_paths=None, views=None):
         self.stage(images, segs, img_paths, views)
         return self.launch()

@@ -25,6 +25,7 @@
 //     no larger than the resident slots and no workgroup gets fewer than SEG_CONF_MIN_TRIPS trips of the pixel loop;
 //   * global: 64-bit atomics straight into the matrix after the same peeling (every larger K, or S2F_SEG_CONF_GLOBAL).
 #include "s2f_common.h"
+#include "seg_label.h"
 
 namespace {
 
@@ -38,14 +39,10 @@ struct alignas(16) I64x2 {
   int64_t v[2];
 };
 
-__device__ __forceinline__ int pred_class(int64_t p, int K) { return (p >= 0 && p < (int64_t)K) ? (int)p : -1; }
-// a float map counts where it holds a class index exactly (the 0 / 1 maps of a one-class head); NaN fails every comparison
-__device__ __forceinline__ int pred_class(float p, int K) { return (p >= 0.0f && p < (float)K && p == truncf(p)) ? (int)p : -1; }
-
 // -> key = (pred class + 1) | (label class + 1) << 16, 0 in a half = "counts nowhere"; active: the pixel has something to count
 template <typename PredT>
 __device__ __forceinline__ uint32_t seg_key(PredT p, int64_t l, int K, int64_t ignore, int rzl, bool& active) {
-  if (rzl) l = (l == 0 || l == 255) ? 255 : l - 1;          // LoadAnnotations(reduce_zero_label=True) on the raw annotation
+  if (rzl) l = seg_reduce_zero_label(l);
   const int pc = pred_class(p, K);
   const int lc = (l >= 0 && l < (int64_t)K) ? (int)l : -1;
   const uint32_t key = (uint32_t)(pc + 1) | ((uint32_t)(lc + 1) << 16);
@@ -289,13 +286,6 @@ int seg_check_args(const char* fn, const void* pred, int pred_dtype, const void*
   S2F_REQUIRE(pa % (pred_dtype == S2F_SEG_PRED_I64 ? 8 : 4) == 0 && (label_dtype == S2F_SEG_LABEL_U8 || la % 8 == 0) && ta % 8 == 0,
               S2F_EALIGN, "%s: a pointer is not aligned to its element size", fn);
   return S2F_OK;
-}
-
-// f(PredT(), LabelT()) for the (checked) dtype codes
-template <class F>
-int seg_by_types(int pred_dtype, int label_dtype, const F& f) {
-  if (pred_dtype == S2F_SEG_PRED_I64) return label_dtype == S2F_SEG_LABEL_U8 ? f(int64_t(), uint8_t()) : f(int64_t(), int64_t());
-  return label_dtype == S2F_SEG_LABEL_U8 ? f(float(), uint8_t()) : f(float(), int64_t());
 }
 
 }  // namespace

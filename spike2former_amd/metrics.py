@@ -289,12 +289,15 @@ def _is_main_process():
     return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
 
 
-def evaluate(model, batches, metric, *, rank=0, world_size=1):
+def evaluate(model, batches, metric, *, rank=0, world_size=1, hooks=()):
     """mmengine's TestLoop with ResetModelHook.before_test_iter for one rank: every `world_size`-th batch starting at `rank` (no
     padding: see the module docstring) -- membranes reset, `model.test_step(batch)` (an EncoderDecoder or a SegTTAModel),
     `metric.process` -- then `metric.evaluate()`.  Nothing inside the loop reads the device back.  `metric` may be a list or tuple
-    of metrics: each processes every batch's samples, and their dictionaries are merged in order."""
+    of metrics: each processes every batch's samples, and their dictionaries are merged in order.  `hooks`: after the metrics have
+    processed a batch, every hook's `after_test_iter(i_local, batch, samples)` runs (a SegVisualizationHook), i_local counting the
+    batches THIS rank ran, from 0."""
     metrics = list(metric) if isinstance(metric, (list, tuple)) else [metric]
+    hooks, i_local = tuple(hooks), 0
     model.eval()
     with torch.no_grad():
         for i, batch in enumerate(batches):
@@ -304,6 +307,9 @@ def evaluate(model, batches, metric, *, rank=0, world_size=1):
             samples = model.test_step(batch)
             for m in metrics:
                 m.process(batch, samples)
+            for h in hooks:
+                h.after_test_iter(i_local, batch, samples)
+            i_local += 1
     if not isinstance(metric, (list, tuple)):
         return metric.evaluate()
     out = OrderedDict()

@@ -654,6 +654,83 @@ def seg_confusion(pred, label, matrix, ignore_index=255, reduce_zero_label=False
     return matrix
 
 
+# ------------------------------------------------------------------------------------------------ visualisation
+_SEG_DRAW_BGR = 4                    # include/s2f.h S2F_SEG_DRAW_BGR
+
+
+def _seg_class_numpy(m, K, reduce_zero_label=False):
+    """a label map as numpy -> int64 class indices, -1 where the value is no class (the rules of s2f_seg_hist / s2f_seg_draw)"""
+    if m.dtype.kind == "f":
+        with _np.errstate(invalid="ignore"):
+            ok = (m >= 0) & (m < K) & (m == _np.trunc(m))
+        return _np.where(ok, _np.where(ok, m, 0).astype(_np.int64), -1)
+    m = m.astype(_np.int64)
+    if reduce_zero_label:
+        m = _np.where((m == 0) | (m == 255), 255, m - 1)
+    return _np.where((m >= 0) & (m < K), m, -1)
+
+
+def _seg_draw_numpy(image, palette, gt, pred, alpha, bgr, reduce_zero_label, out):
+    """the semantics of s2f_seg_draw in numpy float64, one rounding per operation (CPU tensors)"""
+    img, pal = image.numpy(), palette.numpy()
+    K = pal.shape[0]
+    kept = (img[..., ::-1] if bgr else img).astype(_np.float64) * (1.0 - alpha)
+    W = img.shape[1]
+    for q, (m, rzl) in enumerate((m, rzl) for m, rzl in ((gt, reduce_zero_label), (pred, False)) if m is not None):
+        cls = _seg_class_numpy(m.numpy(), K, rzl)
+        colour = _np.where((cls >= 0)[..., None], pal[_np.clip(cls, 0, K - 1)], 0).astype(_np.float64)
+        out[:, q * W:(q + 1) * W] = torch.from_numpy((kept + colour * alpha).astype(_np.uint8))
+    return out
+
+
+def seg_draw(image, palette, gt=None, pred=None, alpha=0.8, bgr=False, reduce_zero_label=False, out=None):
+    """-> uint8 [H, P W, 3] RGB: the class colours of the P given maps blended into `image`, the ground truth left of the prediction
+    (s2f_seg_draw; SegLocalVisualizer._draw_sem_seg and add_datasample's concatenation, mmseg local_visualizer.py:79-118, as one
+    launch).  image uint8 [H, W, 3], RGB or (`bgr`) BGR; palette uint8 [K, 3] RGB on the image's device; gt [H, W] or [1, H, W], uint8
+    or int64, `reduce_zero_label` maps it as a raw annotation first; pred alike, int64 or float32.  Every byte is
+    uint8(fl64(v * (1 - alpha)) + fl64(c * alpha)), c the palette entry of the pixel's class or 0 where its value is no class (a
+    negative label, too: a stated deviation).  CUDA tensors run the kernel; CPU tensors the same arithmetic in numpy (the package's
+    CPU implementation of this op).  A tensor on another device than the image raises; a non-contiguous one is copied."""
+    maps = []
+    for m, what, dtypes in ((gt, "gt", _SEG_LABEL_CODES), (pred, "pred", _SEG_PRED_CODES)):
+        if m is not None:
+            m = m[0] if m.dim() == 3 and m.shape[0] == 1 else m
+            if m.dtype not in dtypes:
+                raise TypeError(f"seg_draw: {what} is {m.dtype}, not one of {[str(d) for d in dtypes]}")
+            if m.dim() != 2 or tuple(m.shape) != tuple(image.shape[:2]):
+                raise ValueError(f"seg_draw: {what} {tuple(m.shape)} does not fit the picture {tuple(image.shape)}")
+            m = m.contiguous()
+        maps.append(m)
+    gt, pred = maps
+    if gt is None and pred is None:
+        raise ValueError("seg_draw: neither a ground-truth map nor a prediction to draw")
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or image.numel() == 0:
+        raise ValueError("seg_draw: image is uint8 [H, W, 3]")
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3:
+        raise ValueError("seg_draw: palette is uint8 [K, 3]")
+    H, W, K, P = image.shape[0], image.shape[1], palette.shape[0], sum(m is not None for m in maps)
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"seg_draw: alpha {alpha} outside 0 .. 1")
+    if not 0 < K <= SEG_HIST_MAX_CLASSES or not H * W < 2 ** 31 - 8:
+        raise ValueError(f"seg_draw: {K} classes (1 .. {SEG_HIST_MAX_CLASSES}) on {H} x {W} pixels (fewer than 2^31 - 8)")
+    if out is None:
+        out = torch.empty(H, P * W, 3, dtype=torch.uint8, device=image.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (H, P * W, 3) or not out.is_contiguous():
+        raise ValueError(f"seg_draw: out is one contiguous uint8 [{H}, {P * W}, 3]")
+    for t in (palette, gt, pred, out):
+        if t is not None and t.device != image.device:
+            raise RuntimeError(f"seg_draw: a tensor on {t.device}, the image on {image.device}")
+    image, palette = image.contiguous(), palette.contiguous()
+    if not image.is_cuda:
+        return _seg_draw_numpy(image, palette, gt, pred, alpha, bool(bgr), bool(reduce_zero_label), out)
+    flags = (_SEG_DRAW_BGR if bgr else 0) | int(bool(reduce_zero_label))
+    check(lib.s2f_seg_draw(_ptr(image), _ptr(gt), _SEG_LABEL_CODES[gt.dtype] if gt is not None else 0, _ptr(pred),
+                           _SEG_PRED_CODES[pred.dtype] if pred is not None else 0, _ptr(palette), K, alpha, flags, H, W, _ptr(out),
+                           _stream()), "s2f_seg_draw")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ mask losses (row f1)
 class _MaskLossSums(torch.autograd.Function):
     """sums[p] = {sum s t, sum s, sum t, sum focal} over the 2x up-sampled logits of matched prediction p against its binary

@@ -75,6 +75,7 @@ class Registry:
 MODELS = Registry("spike2former_amd.MODELS")
 HOOKS = Registry("spike2former_amd.HOOKS")
 METRICS = Registry("spike2former_amd.METRICS")
+VISUALIZERS = Registry("spike2former_amd.VISUALIZERS")
 
 
 def register_upstream():
