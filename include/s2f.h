@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 43
+#define S2F_ABI_VERSION 44
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -41,7 +41,7 @@ const char* s2f_last_error(void);
  * (hipExtLaunchKernelGGL start/stop events = the dispatch packet's own begin/end timestamps, what rocprofv3 reports).
  *   s2f_event_create/destroy: a hipEvent_t as void*.
  *   s2f_time_next_call(start, stop): arms THIS thread; the next s2f_lif_fwd / s2f_lif_bwd / s2f_bn_stats /
- *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist / s2f_seg_confusion / s2f_seg_draw call stamps `start` with the begin of
+ *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist / s2f_seg_confusion / s2f_seg_draw / s2f_state_copy call stamps `start` with the begin of
  *       its first kernel and `stop` with the end of its last one, then disarms.  Not valid during stream capture.
  *   s2f_event_elapsed_us: stop - start in microseconds (both must have completed: synchronise first). */
 void* s2f_event_create(void);
@@ -913,6 +913,30 @@ int s2f_adamw_prepare(const double* partials, int nparts, float max_norm, double
 int s2f_adamw_chunk_elems(void);
 int s2f_adamw_step(const int64_t* slots, const float* hyper, const int32_t* chunks, int nchunks, const float* g, float* m, float* v,
                    const float* state, double beta1, double beta2, float eps, void* stream);
+
+/* ---- training loop: device-side log and one-launch state snapshot (csrc/trainstate.hip, ABI 44) ----------------------------------
+ * What mmengine's IterBasedTrainLoop + LoggerHook + CheckpointHook need from a step that never waits for the GPU
+ * (configs/_base_/schedules/schedule_160k.py, configs/_base_/default_runtime.py): the scalars of every iteration, and the weights.
+ *   s2f_state_copy         one launch copies every tensor of a pointer table into `flat` (to_params = 0) or back (to_params = 1).
+ *                          slots int64 [nslots][3] = {tensor pointer, slot offset in flat, length}, chunks int32 [nchunks][2] =
+ *                          {slot, first word} covering every slot in runs of s2f_adamw_chunk_elems() -- the tables of
+ *                          s2f_adamw_step, but offsets and lengths count 32-BIT WORDS: the kernel copies bits and knows no dtype
+ *                          (an int64 tensor is two words per element).  A tensor pointer is 4-byte aligned at least; slot offsets
+ *                          are multiples of 4 words, so that a slot of the 16-byte-aligned `flat` is 16-byte aligned.  Where a
+ *                          chunk's two addresses are both 16-byte aligned it moves 16 bytes per access, else word by word.
+ *                          Words of `flat` between and behind the slots are never written.  Plain vector loads and stores.
+ *                          S2F_EINVAL: null pointer, nchunks <= 0, to_params not 0 / 1; S2F_EALIGN: flat not 16-byte aligned.
+ *   s2f_train_log_append   srcs: DEVICE table of n device pointers to fp32 scalars; ring float [window][stride]; head int64 [2] on
+ *                          the device: head[0] = rows appended so far, head[1] = the value of head[0] at the first row that held
+ *                          a non-finite value, or -1 (the caller initialises {0, -1}; sticky, survives the ring's wrap).  One
+ *                          workgroup writes the n values into row head[0] % window (columns n .. stride - 1 are not written),
+ *                          then advances head[0].  Appends are ordered by the stream; nothing else writes head.
+ *                          S2F_EINVAL: null pointer, n outside 1 .. S2F_TRAIN_LOG_MAX_TERMS, stride < n, window < 1;
+ *                          S2F_EALIGN: srcs / head not 8-byte, ring not 4-byte aligned.
+ * All tables are DEVICE memory; neither call allocates, synchronises or uses atomics: both can be captured into the step's hipGraph. */
+#define S2F_TRAIN_LOG_MAX_TERMS 256
+int s2f_state_copy(const int64_t* slots, const int32_t* chunks, int nchunks, void* flat, int to_params, void* stream);
+int s2f_train_log_append(const float* const* srcs, int n, float* ring, int window, int stride, int64_t* head, void* stream);
 
 /* ---- general strided fp32 product on the vector ALUs (csrc/bmm.hip, round 6) -----------------------------------------------
  * C[b][m][n] = sum_k A[b][m][k] B[b][k][n], every operand with explicit ELEMENT strides (a transposed or broadcast operand is a

@@ -32,7 +32,7 @@ def _process_group():
 class _Captured:
     """A step with static input `static_in`, recorded as one hipGraph per stage.  `red`: the flat gradient buffer
     (dist.FlatGradAllReduce) of the steps that pack into one; `optimizer`: a train.FlatAdamW captured behind the packing."""
-    optimizer = None
+    optimizer = log = None
 
     def _capture(self, warm, warmup, stages, context=None):
         """`warmup` calls of `warm` on a side stream (allocator pools, lazy inits, caches), then each callable of `stages`
@@ -90,6 +90,25 @@ class _Captured:
         if self.optimizer is not None:
             self.optimizer.mark_updated()
 
+    def _record_log(self, terms):
+        """while the LAST stage is recorded, behind the optimizer's update: one row of `terms` ({name: static scalar}, plus this
+        iteration's grad_norm and clip_coef of a captured optimizer) per replay into `self.log` (runner.TrainLog).  The launch
+        reads the scalars through a pointer table that `_bind_log` fills once the capture has ended."""
+        if self.optimizer is not None:
+            terms = {**terms, "grad_norm": self.optimizer.grad_norm, "clip_coef": self.optimizer.clip_coef}
+        self.log_terms = terms
+        # at world size > 1 the all-reduce and the update follow the replay eagerly: the row is appended behind them, by the caller
+        # (runner.TrainLoop), who also binds the optimizer's terms
+        import torch.distributed as dist
+        self.log_captured = not (_process_group() and dist.get_world_size() > 1)
+        if self.log_captured:
+            self.log.declare(terms.keys())
+            self.log.append()
+
+    def _bind_log(self):
+        if self.log is not None and self.log_captured:
+            self.log.bind(self.log_terms)
+
     def _forward(self):
         reset_net(self.model)
         self.red.zero()
@@ -104,10 +123,11 @@ class _Captured:
 class GraphedStep(_Captured):
     """`optimizer` (train.FlatAdamW over `grad_buffer`): the parameter update -- clip + AdamW, three launches -- is captured behind
     the gradient packing, so one replay is one training ITERATION (single process; with N > 1 the all-reduce sits between the step
-    and the update, which the caller then runs eagerly: `step(); grad_buffer.reduce(); optimizer.step()`)."""
+    and the update, which the caller then runs eagerly: `step(); grad_buffer.reduce(); optimizer.step()`).  `log` (runner.TrainLog):
+    every replay appends {loss, grad_norm, clip_coef} to it, at the end of the graph; None: the capture holds no such launch."""
 
-    def __init__(self, model, loss_fn, example_input, grad_buffer=None, warmup=3, optimizer=None):
-        self.model, self.loss_fn = model, loss_fn
+    def __init__(self, model, loss_fn, example_input, grad_buffer=None, warmup=3, optimizer=None, log=None):
+        self.model, self.loss_fn, self.log = model, loss_fn, log
         self.static_in = example_input.clone()
         self.grad_buffer = grad_buffer
         self.optimizer = optimizer
@@ -116,9 +136,12 @@ class GraphedStep(_Captured):
 
         def record():
             self.static_loss = self._eager_step()
+            if self.log is not None:
+                self._record_log({"loss": self.static_loss})
         # ops.GLUE_MODE: the residual aten calls of the step (autograd's gradient accumulation, scalar multiples, copies, fills, small
         # sums) are routed to csrc/glue.hip while the step is RECORDED -- the replay then consists of this package's kernels only
         self.graph, = self._capture(self._eager_step, warmup, [record], context=ops.glue_mode if ops.GLUE_MODE else None)
+        self._bind_log()
 
     def _eager_step(self):
         reset_net(self.model)
@@ -212,15 +235,21 @@ class GraphedHungarianStep(_Captured):
     before it touches the static inputs, when the word an earlier replay left has landed (a copy still in flight is seen on a
     later call or by `check()`).  Raising clears the word (the error path waits for the stream).  A step with a set status has NaN
     losses (the kernel writes num_masks = NaN), never quietly wrong ones -- and, with a captured optimizer, has already applied
-    them: validate label maps before training on them."""
+    them: validate label maps before training on them.
 
-    def __init__(self, model, example_input, example_seg, grad_buffer, warmup=3, ignore_index=None, optimizer=None, assign="host"):
+    `log` (runner.TrainLog): the last graph ends with one more launch that appends every entry of the loss dictionary, their sum
+    `loss` and, with a captured optimizer, its grad_norm and clip_coef to a ring on the device -- the record of EVERY iteration,
+    and of the first one with a non-finite term, that runner.LoggerHook reads once per log interval.  None: the capture is the
+    one without it."""
+
+    def __init__(self, model, example_input, example_seg, grad_buffer, warmup=3, ignore_index=None, optimizer=None, assign="host",
+                 log=None):
         if assign not in ("host", "device"):
             raise ValueError(f"assign must be 'host' or 'device', got {assign!r}")
         if assign == "device" and not (example_input.is_cuda and example_seg.is_cuda):
             raise RuntimeError("GraphedHungarianStep(assign='device') needs CUDA tensors: the device assignment is a HIP kernel and "
                                "has no host fall-back")
-        self.assign = assign
+        self.assign, self.log = assign, log
         head = model.decode_head
         self.optimizer = optimizer
         if optimizer is not None:
@@ -262,10 +291,13 @@ class GraphedHungarianStep(_Captured):
 
         def tail():
             losses = self._losses(self.outs)
-            self.red.pack(self._grads(sum(losses.values())))
+            total = sum(losses.values())
+            self.red.pack(self._grads(total))
             if self.optimizer is not None:
                 self.optimizer.step(sync_hyper=False)
             self.losses = {k: v.detach() for k, v in losses.items()}
+            if self.log is not None:          # behind the update: grad_norm is this iteration's
+                self._record_log({**self.losses, "loss": total.detach()})
             if assign == "device":
                 self.sticky.bitwise_or_(self.status)
                 self.host_status.copy_(self.sticky, non_blocking=True)
@@ -274,6 +306,7 @@ class GraphedHungarianStep(_Captured):
             head()
             tail()
         self._graphs = self._capture(warm, warmup, [head, tail] if self.two_graphs else [whole])
+        self._bind_log()
         for name, graph in zip(("graph", "graph_tail") if assign == "device" else ("graph_a", "graph_b"), self._graphs):
             setattr(self, name, graph)
         if assign == "device":

@@ -1,0 +1,110 @@
+"""The two launches a training loop adds to the captured step (csrc/trainstate.hip): `state_copy`, every tensor of a pointer table
+into one flat buffer or back, and `train_log_append`, one row of per-iteration scalars into a ring on the device.  CUDA tensors run
+the kernels on the current stream; CPU tensors run the same semantics in torch (the package's CPU implementation of these two ops,
+as the numpy route of `seg_draw`), so the classes of runner.py can be driven without a GPU."""
+import torch
+
+from .core import _ptr, _stream, check, lib
+
+TRAIN_LOG_MAX_TERMS = 256          # include/s2f.h S2F_TRAIN_LOG_MAX_TERMS
+
+
+def _words(t):
+    """a contiguous tensor of 4- or 8-byte elements as its flat int32 bit view (shares the storage)"""
+    if t.element_size() % 4 != 0:
+        raise TypeError(f"state_copy moves 32-bit words: a {t.dtype} tensor has {t.element_size()}-byte elements")
+    if not t.is_contiguous():
+        raise RuntimeError("state_copy: tensors must be contiguous")
+    return t.detach().reshape(-1).view(torch.int32)
+
+
+def state_table(tensors, device=None):
+    """-> (slots int64 [n][3], chunks int32 [nchunks][2], words): the tables of s2f_state_copy over `tensors` (contiguous, 4- or
+    8-byte elements, at least one element in all), on `device` (default: the tensors'), and the length of the flat int32 buffer they
+    address.  Slot offsets are multiples of 4 words: every slot of a 16-byte-aligned flat buffer is 16-byte aligned; the words
+    between two slots are pads that no copy writes.  Empty tensors get a slot and no chunk."""
+    tensors = list(tensors)
+    chunk = int(lib.s2f_adamw_chunk_elems())
+    slots, chunks, off = [], [], 0
+    for i, t in enumerate(tensors):
+        n = _words(t).numel()
+        slots.append((t.data_ptr(), off, n))
+        chunks += [(i, s) for s in range(0, n, chunk)]
+        off += (n + 3) // 4 * 4
+    if not chunks:
+        raise ValueError("state_table: nothing to copy")
+    device = tensors[0].device if device is None else device
+    return (torch.tensor(slots, dtype=torch.int64).reshape(-1, 3).to(device), torch.tensor(chunks, dtype=torch.int32).to(device), off)
+
+
+def state_copy(tensors, slots, chunks, flat, to_params=False):
+    """Every tensor of the table <-> its slot of `flat` (int32, contiguous, 16-byte aligned) in ONE launch: tensors -> flat, or
+    (`to_params`) flat -> tensors.  Bits, not values: NaN payloads, denormals and int64 counters pass unchanged; pad words of `flat`
+    are not written.  `slots`, `chunks`: `state_table(tensors)` -- the kernel reads the pointers baked into `slots` (rebuild the
+    table when a tensor's storage moves); `tensors` itself is read by the CPU route only.  Nothing synchronises; capturable."""
+    if flat.dtype != torch.int32 or not flat.is_contiguous():
+        raise ValueError("state_copy: flat is one contiguous int32 buffer")
+    if slots.dtype != torch.int64 or chunks.dtype != torch.int32 or slots.dim() != 2 or slots.shape[1] != 3 or chunks.dim() != 2 \
+            or chunks.shape[1] != 2 or not (slots.is_contiguous() and chunks.is_contiguous()):
+        raise ValueError("state_copy: slots is a contiguous int64 [n, 3], chunks a contiguous int32 [nchunks, 2] (state_table)")
+    if slots.device != flat.device or chunks.device != flat.device:
+        raise RuntimeError(f"state_copy: tables on {slots.device} / {chunks.device}, flat on {flat.device}")
+    if not flat.is_cuda:
+        tensors = list(tensors)
+        if len(tensors) != slots.shape[0]:
+            raise ValueError(f"state_copy: {len(tensors)} tensors for a table of {slots.shape[0]} slots")
+        for t, (_, off, n) in zip(tensors, slots.tolist()):
+            w = _words(t)
+            if w.numel() != n or off + n > flat.numel():
+                raise ValueError("state_copy: the table does not describe these tensors")
+            if to_params:
+                w.copy_(flat[off:off + n])
+            else:
+                flat[off:off + n].copy_(w)
+        return flat
+    check(lib.s2f_state_copy(_ptr(slots), _ptr(chunks), chunks.shape[0], _ptr(flat), int(bool(to_params)), _stream()), "s2f_state_copy")
+    return flat
+
+
+def train_log_table(srcs, device=None):
+    """-> int64 [n] on `device`: the addresses of the fp32 scalars `srcs` (one-element CUDA tensors that outlive the table's use:
+    static tensors of a captured step), the `table` of `train_log_append`.  One host-to-device copy: build it once, outside a capture."""
+    srcs = list(srcs)
+    for t in srcs:
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise ValueError(f"train_log_append records fp32 scalars; got {t.dtype} {tuple(t.shape)}")
+    device = srcs[0].device if device is None else device
+    return torch.tensor([t.data_ptr() for t in srcs], dtype=torch.int64).to(device)
+
+
+def train_log_append(srcs, ring, head, table=None, n=None):
+    """Row head[0] % window of `ring` (fp32 [window, stride]) <- the scalars `srcs`; a non-finite value among them latches head[1]
+    (int64 [2] = {rows appended, first row with a non-finite value or -1}); head[0] += 1.  One launch of one wave on the current
+    stream, capturable: the CUDA route reads the scalars through `table` (`train_log_table(srcs)`; built here, with a host-to-device
+    copy, when not given -- not under capture) and may be called with `srcs=None` and the count `n` of the table's entries in use.
+    Columns n .. stride - 1 of the row are not written."""
+    if ring.dtype != torch.float32 or ring.dim() != 2 or not ring.is_contiguous():
+        raise ValueError("train_log_append: ring is a contiguous fp32 [window, stride]")
+    if head.dtype != torch.int64 or tuple(head.shape) != (2,) or not head.is_contiguous() or head.device != ring.device:
+        raise ValueError("train_log_append: head is a contiguous int64 [2] on the ring's device")
+    window, stride = ring.shape
+    n = len(srcs) if n is None else int(n)
+    if not 1 <= n <= TRAIN_LOG_MAX_TERMS or stride < n or window < 1:
+        raise ValueError(f"train_log_append: {n} terms (1 .. {TRAIN_LOG_MAX_TERMS}) into a ring of {window} rows of {stride}")
+    if not ring.is_cuda:
+        count = int(head[0])
+        vals = torch.stack([t.detach().reshape(()).to(torch.float32) for t in srcs])
+        ring[count % window, :n] = vals
+        if int(head[1]) < 0 and not bool(torch.isfinite(vals).all()):
+            head[1] = count
+        head[0] = count + 1
+        return ring
+    if table is None:
+        table = train_log_table(srcs, ring.device)
+    if table.dtype != torch.int64 or table.dim() != 1 or table.numel() < n or table.device != ring.device or not table.is_contiguous():
+        raise ValueError(f"train_log_append: table is a contiguous int64 [>= {n}] on the ring's device")
+    check(lib.s2f_train_log_append(_ptr(table), n, _ptr(ring), window, stride, _ptr(head), _stream()), "s2f_train_log_append")
+    return ring
+
+
+__all__ = ["TRAIN_LOG_MAX_TERMS", "state_table", "state_copy", "train_log_table", "train_log_append"]

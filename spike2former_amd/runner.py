@@ -1,0 +1,666 @@
+"""The training LOOP around the captured step -- what mmengine's runner does between iterations for the Spike2Former configs:
+
+    train_cfg = dict(type='IterBasedTrainLoop', max_iters=160000, val_interval=2500)       configs/_base_/schedules/schedule_160k.py
+    default_hooks = dict(logger=dict(type='LoggerHook', interval=50, log_metric_by_epoch=False),
+                         param_scheduler=dict(type='ParamSchedulerHook'),
+                         checkpoint=dict(type='CheckpointHook', by_epoch=False, interval=10000, save_best='mIoU'), ...)
+    load_from = None; resume = False                                                         configs/_base_/default_runtime.py
+
+`graph.GraphedHungarianStep(assign="device", optimizer=FlatAdamW(...))` is a whole iteration that never waits for the GPU; three
+things a loop needs would each put a host stop back into it, and each has a device-side piece here instead:
+
+  * the losses `step()` returns are static tensors, valid until the next call: `TrainLog` is a ring ON THE DEVICE that the step's
+    last graph appends one row to per replay (ops.train_log_append); the host reads it back once per log interval, one copy;
+  * a checkpoint of ~1 000 parameter and buffer tensors behind a pointer table: `TrainState.snapshot()` is ONE launch into a staging
+    buffer (ops.state_copy) plus three device-to-device copies, all queued on the step's stream -- the next replay may start at
+    once; the copy to pinned memory runs on a side stream, `torch.save` in a writer thread;
+  * a step whose status word is set has NaN losses and has applied them: the ring's head latches the FIRST row that held a
+    non-finite value, `LoggerHook` raises `FloatingPointError` naming that iteration, and no checkpoint is written past it.
+
+mmengine (0.8.4) is not part of the reference tree: `LoggerHook`, `CheckpointHook` and the loop are restated from its published
+behaviour, and like the schedulers of train.py their parity is UNPINNED (DESIGN.md section 7 lists the deviations).  Iterations are
+named as mmengine names them in file names and log lines: "iteration n" is the n-th, counted from 1.
+
+    log = TrainLog(window=50)
+    step = GraphedHungarianStep(model, example_in, example_seg, red, optimizer=optim, assign="device", log=log)
+    loop = TrainLoop(step, optim, sched, aug, batches, max_iters=160000, val_interval=2500, validate=lambda: evaluate(...),
+                     hooks=[dict(type='LoggerHook', interval=50), dict(type='CheckpointHook', interval=10000, save_best='mIoU')],
+                     work_dir='work_dirs/run')
+    loop.run()
+"""
+import collections
+import concurrent.futures
+import copy
+import datetime
+import json
+import logging
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import ops
+from .registry import HOOKS
+
+logger = logging.getLogger("spike2former_amd")
+
+LogRead = collections.namedtuple("LogRead", "names rows count first_nonfinite")
+
+
+def _rank_world():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+class TrainLog:
+    """A ring of the last `window` iterations' scalars on the device.  `terms`: ordered {name: one-element fp32 tensor}, static
+    tensors of a captured step (its losses, their sum, the optimizer's grad_norm and clip_coef).  `append()` is one launch
+    (capturable) that copies them into the next row; `read()` is one device-to-host copy.
+
+    A captured step knows its static tensors only while it is being recorded, where nothing may be uploaded: build the log without
+    terms (`TrainLog(window=..., device=...)`, at most `capacity` of them), hand it to the step (`log=`), and the step `declare`s the
+    names while recording -- the recorded launch reads a pointer table that `bind` fills after the capture."""
+
+    def __init__(self, terms=None, window=64, device=None, capacity=64):
+        if window < 1:
+            raise ValueError(f"TrainLog: window {window} below 1")
+        if terms is not None:
+            capacity = len(terms)
+            device = next(iter(terms.values())).device if device is None else device
+        if not 1 <= capacity <= ops.TRAIN_LOG_MAX_TERMS:
+            raise ValueError(f"TrainLog: {capacity} terms outside 1 .. {ops.TRAIN_LOG_MAX_TERMS}")
+        self.device = torch.device("cuda" if device is None else device)
+        self.window, self.stride = int(window), int(capacity)
+        # head (int64 [2], four words) and ring in ONE allocation: read() is one copy
+        self._buf = torch.zeros(4 + self.window * self.stride, dtype=torch.float32, device=self.device)
+        self.head, self.ring = self._buf[:4].view(torch.int64), self._buf[4:].view(self.window, self.stride)
+        self.head[1] = -1
+        self._host = torch.zeros_like(self._buf, device="cpu")
+        self._table = self._event = None
+        if self.device.type == "cuda":
+            self._host = self._host.pin_memory()
+            self._table = torch.zeros(self.stride, dtype=torch.int64, device=self.device)
+            self._event = torch.cuda.Event()
+        self.names, self._srcs = None, None
+        self.base = 0          # the iterations that ran before row 0 (a resumed run)
+        if terms is not None:
+            self.bind(terms)
+
+    def declare(self, names):
+        """the names of the terms, before their tensors can be bound (host only: legal while a capture records)"""
+        names = list(names)
+        if not 1 <= len(names) <= self.stride:
+            raise ValueError(f"TrainLog: {len(names)} terms for a capacity of {self.stride}")
+        self.names = names
+
+    def bind(self, terms):
+        """the tensors behind the names: uploads their addresses into the pointer table (not under capture)"""
+        self.declare(terms.keys())
+        self._srcs = list(terms.values())
+        if self._table is not None:
+            self._table[:len(self._srcs)].copy_(ops.train_log_table(self._srcs, "cpu"))
+
+    def append(self):
+        if self.names is None:
+            raise RuntimeError("TrainLog.append before its terms are declared")
+        if self._table is None and self._srcs is None:
+            raise RuntimeError("TrainLog.append on the CPU before its terms are bound")
+        ops.train_log_append(self._srcs, self.ring, self.head, table=self._table, n=len(self.names))
+
+    def read(self):
+        """-> LogRead(names, rows, count, first_nonfinite): the last min(count, window) rows, oldest first, as numpy fp32
+        [rows, terms]; the number of rows appended so far; the index (from 0) of the first row that held a non-finite value, or
+        None.  One device-to-host copy on the current stream, and a wait for that copy."""
+        if self._event is not None:
+            self._host.copy_(self._buf, non_blocking=True)
+            self._event.record()
+            self._event.synchronize()
+        else:
+            self._host.copy_(self._buf)
+        head = self._host[:4].view(torch.int64)
+        count, bad = int(head[0]), int(head[1])
+        n, k = len(self.names or ()), min(count, self.window)
+        ring = self._host[4:].view(self.window, self.stride).numpy()
+        rows = np.stack([ring[(count - k + i) % self.window, :n] for i in range(k)]) if k else np.zeros((0, n), np.float32)
+        return LogRead(list(self.names or ()), rows.copy(), count, None if bad < 0 else bad)
+
+
+class TrainState:
+    """Snapshot, file and resume of a run's whole state: every tensor of `model.state_dict()` (parameters and buffers, by name),
+    `optimizer`'s two moments and step count (a train.FlatAdamW), `scheduler.t`, `augment`'s generator.
+
+    `snapshot()` queues, on the current stream, one `ops.state_copy` of the model into a device staging buffer and the device-to-
+    device copies of the moments and the optimizer's state words; the copies into pinned memory follow on a side stream.  The next
+    replay of the step may be queued at once: it can overtake nothing, the stagings are written before it in stream order.
+    `write(path, meta)` hands the pinned buffers to ONE writer thread, which waits for the side stream's event and `torch.save`s
+    views of them; a following `snapshot()`, `load()` or `close()` joins a write still running (`async_write=False`: written by
+    the caller)."""
+
+    def __init__(self, model, optimizer, scheduler=None, augment=None, async_write=True):
+        self.model, self.optimizer, self.scheduler, self.augment = model, optimizer, scheduler, augment
+        self.async_write = bool(async_write)
+        self._ptrs = self._tag = self._host_side = None
+        self._pending = []
+        self._pool = None
+        self._staged = self._copied = self._side = None
+        self._build(self._tensors())
+        if optimizer is not None:
+            self._opt_dev = [torch.empty_like(t) for t in (optimizer.exp_avg, optimizer.exp_avg_sq, optimizer.state)]
+            self._opt_host = [self._pinned(torch.zeros_like(t, device="cpu")) for t in self._opt_dev]
+
+    # ------------------------------------------------------------------------------------------------ tables
+    def _tensors(self):
+        return self.model.state_dict(keep_vars=True)
+
+    def _pinned(self, t):
+        return t.pin_memory() if self.device.type == "cuda" else t
+
+    def _build(self, named):
+        self.names, self.tensors = list(named.keys()), list(named.values())
+        if not self.tensors:
+            raise ValueError("TrainState: the model has no state")
+        self.device = self.tensors[0].device
+        for n, t in named.items():
+            if not t.is_contiguous():
+                raise RuntimeError(f"TrainState: {n} is not contiguous")
+            if t.device != self.device:
+                raise RuntimeError(f"TrainState: {n} on {t.device}, the model on {self.device}")
+        self.slots, self.chunks, words = ops.state_table(self.tensors, self.device)
+        self._spans = [(off, n) for _, off, n in self.slots.tolist()]
+        self._ptrs = tuple(t.data_ptr() for t in self.tensors)
+        if getattr(self, "flat", None) is None or self.flat.numel() != words:
+            self.flat = torch.zeros(words, dtype=torch.int32, device=self.device)
+            self.host_flat = self._pinned(torch.zeros(words, dtype=torch.int32))
+
+    def _refresh(self):
+        """the table follows the model: rebuilt when a tensor's storage moved (model.to(...), a re-flattened sibling group)"""
+        named = self._tensors()
+        if list(named.keys()) != self.names or tuple(t.data_ptr() for t in named.values()) != self._ptrs:
+            self._build(named)
+
+    # ------------------------------------------------------------------------------------------------ snapshot and file
+    def join(self):
+        """wait for the writes still running; re-raises what a write raised"""
+        pending, self._pending = self._pending, []
+        for f in pending:
+            f.result()
+
+    def host_state(self):
+        """What of the state lives on the host and differs between the ranks: the augment generator's state.  A collective at
+        world size > 1 (every rank calls it) -> the states by rank, for the one rank that writes; a single process: its state."""
+        mine = None if self.augment is None else copy.deepcopy(self.augment.rng.bit_generator.state)
+        rank, world = _rank_world()
+        if world == 1:
+            return mine
+        import torch.distributed as dist
+        states = [None] * world
+        dist.all_gather_object(states, mine)
+        return states
+
+    def snapshot(self, tag=None, rng=None):
+        """Queue a copy of the whole state as it is in stream order NOW.  `tag`: a snapshot with the tag of the last one (not None)
+        is that one -- two files of one iteration share one copy.  `rng`: what `host_state()` returned (default: it is called
+        here, which at world size > 1 every rank has to do)."""
+        if tag is not None and tag == self._tag:
+            return
+        self.join()          # the views of the file being written alias the pinned buffers
+        self._refresh()
+        opt = self.optimizer
+        cuda = self.device.type == "cuda"
+        if cuda:
+            cur = torch.cuda.current_stream()
+            if self._copied is not None:
+                cur.wait_event(self._copied)          # the last snapshot's copies to the host still read the stagings
+        ops.state_copy(self.tensors, self.slots, self.chunks, self.flat)
+        if opt is not None:
+            if self._opt_dev[0].shape != opt.exp_avg.shape:
+                raise RuntimeError("TrainState: the optimizer's buffers were laid out again (FlatAdamW.rebuild()); build a new TrainState")
+            for dst, src in zip(self._opt_dev, (opt.exp_avg, opt.exp_avg_sq, opt.state)):
+                dst.copy_(src, non_blocking=True)
+        if cuda:
+            if self._side is None:
+                self._side, self._staged, self._copied = torch.cuda.Stream(), torch.cuda.Event(), torch.cuda.Event()
+            self._staged.record(cur)
+            with torch.cuda.stream(self._side):
+                self._side.wait_event(self._staged)
+                self.host_flat.copy_(self.flat, non_blocking=True)
+                if opt is not None:
+                    for dst, src in zip(self._opt_host, self._opt_dev):
+                        dst.copy_(src, non_blocking=True)
+                self._copied.record(self._side)
+        else:
+            self.host_flat.copy_(self.flat)
+            if opt is not None:
+                for dst, src in zip(self._opt_host, self._opt_dev):
+                    dst.copy_(src)
+        # what lives on the host is taken now: the loop moves both on while the file is written
+        self._host_side = dict(t=None if self.scheduler is None else int(self.scheduler.t),
+                               rng=self.host_state() if rng is None else rng,
+                               names=list(self.names), spans=list(self._spans),
+                               shapes=[(tuple(t.shape), t.dtype) for t in self.tensors],
+                               opt=None if opt is None else [(g["name"], off, tuple(p.shape))
+                                                             for g, p, off in zip(opt.param_groups, opt.params, opt.red.offsets)])
+        self._tag = tag
+
+    def _payload(self, meta, best):
+        s = self._host_side
+        sd = collections.OrderedDict()
+        for name, (off, n), (shape, dtype) in zip(s["names"], s["spans"], s["shapes"]):
+            t = self.host_flat[off:off + n].view(dtype).view(shape)
+            # (torch.save refuses views of ONE storage under two dtypes: the fp32 tensors alias the pinned buffer, the few others
+            # -- BatchNorm's int64 counters -- are copied out of it)
+            sd[name] = t if dtype == torch.float32 else t.clone()
+        out = dict(meta=dict(meta or {}), state_dict=sd)
+        if s["opt"] is not None:
+            m, v, st = self._opt_host
+            out["optimizer"] = dict(step=int(st[4]), state={name: {"exp_avg": m[off:off + int(np.prod(shape))].view(shape),
+                                                                   "exp_avg_sq": v[off:off + int(np.prod(shape))].view(shape)}
+                                                            for name, off, shape in s["opt"]})
+        out["param_schedulers"] = [] if s["t"] is None else [dict(t=s["t"])]
+        out["augment"] = s["rng"]
+        out["best"] = best
+        return out
+
+    def write(self, path, meta=None, best=None, done=None, async_write=None):
+        """The last snapshot -> `path` (torch.save; written under another name and renamed, so a file that exists is complete).
+        `done(path)` runs behind the file, in the thread that wrote it."""
+        if self._host_side is None:
+            raise RuntimeError("TrainState.write before snapshot")
+        meta, best = copy.deepcopy(meta), copy.deepcopy(best)
+
+        def job():
+            if self._copied is not None:
+                self._copied.synchronize()
+            tmp = f"{path}.tmp"
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            torch.save(self._payload(meta, best), tmp)
+            os.replace(tmp, path)
+            if done is not None:
+                done(path)
+        if self.async_write if async_write is None else async_write:
+            if self._pool is None:
+                self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="s2f-checkpoint")
+            self._pending.append(self._pool.submit(job))
+        else:
+            self.join()
+            job()
+
+    def close(self):
+        try:
+            self.join()
+        finally:
+            if self._pool is not None:
+                self._pool.shutdown(wait=True)
+                self._pool = None
+
+    # ------------------------------------------------------------------------------------------------ load and resume
+    def load(self, path, resume=False):
+        """`path`: a file of `write`, or any checkpoint whose 'state_dict' (or the file itself) maps this model's names to tensors
+        of its shapes -- strict: a RuntimeError lists what is missing, unexpected or mis-shaped.  The values go through the pinned
+        and the device staging buffers and ONE `ops.state_copy(to_params=True)`.  `resume`: also both moments, the step count, the
+        scheduler's `t` and the augment generator.  -> the file's dictionary without its tensors (meta, best, ...)."""
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        sd = ck["state_dict"] if isinstance(ck, dict) and "state_dict" in ck else ck
+        self.join()
+        self._refresh()
+        missing = [n for n in self.names if n not in sd]
+        have = set(self.names)
+        unexpected = [n for n in sd if n not in have]
+        shapes = [f"{n}: {tuple(sd[n].shape)} in the file, {tuple(t.shape)} in the model" for n, t in zip(self.names, self.tensors)
+                  if n in sd and tuple(sd[n].shape) != tuple(t.shape)]
+        opt, om = self.optimizer, None
+        if resume:
+            if not isinstance(ck, dict) or "optimizer" not in ck or "meta" not in ck:
+                raise RuntimeError(f"{path} holds no optimizer state to resume from")
+            if opt is None:
+                raise RuntimeError("TrainState.load(resume=True) needs the optimizer")
+            om = ck["optimizer"]["state"]
+            missing += [f"optimizer:{g['name']}" for g in opt.param_groups if g["name"] not in om]
+            unexpected += [f"optimizer:{n}" for n in om if n not in {g["name"] for g in opt.param_groups}]
+            shapes += [f"optimizer:{g['name']}: {tuple(om[g['name']][k].shape)} in the file, {tuple(p.shape)} in the model"
+                       for g, p in zip(opt.param_groups, opt.params) if g["name"] in om
+                       for k in ("exp_avg", "exp_avg_sq") if tuple(om[g["name"]][k].shape) != tuple(p.shape)]
+        if missing or unexpected or shapes:
+            raise RuntimeError(f"{path} does not fit the model -- missing: {missing}; unexpected: {unexpected}; mis-shaped: {shapes}")
+        if self._copied is not None:
+            self._copied.synchronize()
+        for name, t, (off, n) in zip(self.names, self.tensors, self._spans):
+            self.host_flat[off:off + n].copy_(sd[name].to(t.dtype).contiguous().reshape(-1).view(torch.int32))
+        self.flat.copy_(self.host_flat, non_blocking=True)
+        ops.state_copy(self.tensors, self.slots, self.chunks, self.flat, to_params=True)
+        if resume:
+            m, v, _ = self._opt_host
+            m.zero_(), v.zero_()
+            for g, p, off in zip(opt.param_groups, opt.params, opt.red.offsets):
+                m[off:off + p.numel()].copy_(om[g["name"]]["exp_avg"].reshape(-1))
+                v[off:off + p.numel()].copy_(om[g["name"]]["exp_avg_sq"].reshape(-1))
+            opt.exp_avg.copy_(m, non_blocking=True)
+            opt.exp_avg_sq.copy_(v, non_blocking=True)
+            opt.state[4:5].fill_(float(ck["optimizer"]["step"]))
+            sched = ck.get("param_schedulers") or []
+            if self.scheduler is not None and sched:
+                self.scheduler.t = int(sched[0]["t"])
+                self.scheduler._apply()
+            if self.augment is not None and ck.get("augment") is not None:
+                rng, (rank, world) = ck["augment"], _rank_world()
+                if isinstance(rng, list):          # a run of several ranks: one generator each
+                    if len(rng) != world:
+                        raise RuntimeError(f"{path} was written by a run of {len(rng)} ranks; this one has {world}")
+                    rng = rng[rank]
+                elif world > 1:
+                    raise RuntimeError(f"{path} was written by a single process; this run has {world} ranks")
+                self.augment.rng.bit_generator.state = rng
+        # the weights changed behind autograd's back, as after a replayed update: every cache keyed on a tensor's version
+        # re-converts; the graph's own (lr, weight_decay) table is uploaded again
+        torch.autograd.graph.increment_version(self.tensors)
+        if opt is not None:
+            opt.mark_updated()
+            opt._hyper_last = None
+        if self.device.type == "cuda":
+            torch.cuda.current_stream().synchronize()          # the pinned buffers are free again
+        self._tag = None
+        return {k: v for k, v in ck.items() if k not in ("state_dict", "optimizer")} if isinstance(ck, dict) and "state_dict" in ck else {}
+
+
+# ---------------------------------------------------------------------------------------------------- hooks
+class _Hook:
+    priority = 50          # mmengine's NORMAL; a loop runs its hooks in ascending order of it
+
+    def before_run(self, loop):
+        pass
+
+    def after_train_iter(self, loop):
+        pass
+
+    def after_val(self, loop, metrics):
+        pass
+
+    def after_run(self, loop):
+        pass
+
+
+@HOOKS.register_module()
+class ParamSchedulerHook(_Hook):
+    """Accepted for the configs' `default_hooks`; `TrainLoop` steps the scheduler itself, after every iteration."""
+    priority = 70
+
+
+@HOOKS.register_module()
+class LoggerHook(_Hook):
+    """mmengine's LoggerHook + LogProcessor(window_size=10, by_epoch=False) for the train loop: at iteration n with n % interval ==
+    0, and at the last one, ONE `TrainLog.read()`; the mean of the last `window_size` rows of every term, the learning rate of
+    parameter group 0 in that iteration, seconds per iteration since the last line, the time left at that rate and the peak of
+    allocated device memory in MiB -- one line on the `spike2former_amd` logger and one JSON line in {work_dir}/vis_data/scalars.json.
+    A non-finite value in ANY iteration since the last check raises FloatingPointError naming the first (TrainLoop.check_finite)."""
+    priority = 60
+    HIDDEN = ("clip_coef",)
+
+    def __init__(self, interval=50, window_size=10, log_metric_by_epoch=False, **unused):
+        if log_metric_by_epoch:
+            raise NotImplementedError("LoggerHook(log_metric_by_epoch=True): the loop counts iterations")
+        if interval < 1 or window_size < 1:
+            raise ValueError("LoggerHook: interval and window_size are at least 1")
+        self.interval, self.window_size = int(interval), int(window_size)
+
+    def before_run(self, loop):
+        if loop.log is None:
+            raise ValueError("LoggerHook needs a step built with log=TrainLog(...)")
+        if loop.log.window < self.window_size:
+            raise ValueError(f"LoggerHook(window_size={self.window_size}) over a TrainLog of {loop.log.window} rows")
+        self._clock, self._last = time.perf_counter(), loop.iter
+
+    def _emit(self, loop, record, line):
+        logger.info(line)
+        if loop.work_dir is not None and loop.rank == 0:
+            path = os.path.join(loop.work_dir, "vis_data", "scalars.json")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "a") as f:
+                f.write(json.dumps(record) + "\n")
+
+    def after_train_iter(self, loop):
+        n = loop.iter + 1
+        if n % self.interval and n != loop.max_iters:
+            return
+        read = loop.check_finite()
+        rows = read.rows[-self.window_size:]
+        now = time.perf_counter()
+        per_iter = (now - self._clock) / max(n - self._last, 1)
+        self._clock, self._last = now, n
+        record = dict(lr=float(loop.lr), time=per_iter, eta=per_iter * (loop.max_iters - n),
+                      memory=int(torch.cuda.max_memory_allocated() // 2 ** 20) if torch.cuda.is_available() else 0)
+        for j, name in enumerate(read.names):
+            if name not in self.HIDDEN and len(rows):
+                record[name] = float(np.mean(np.ascontiguousarray(rows[:, j])))          # fp32, in the rows' order
+        record.update(iter=n, step=n)
+        eta = str(datetime.timedelta(seconds=int(record["eta"])))
+        terms = "  ".join(f"{k}: {v:.4f}" for k, v in record.items() if k not in ("lr", "time", "eta", "memory", "iter", "step"))
+        self._emit(loop, record, f"Iter(train) [{n:>{len(str(loop.max_iters))}}/{loop.max_iters}]  lr: {record['lr']:.4e}  eta: {eta}  "
+                                 f"time: {per_iter:.4f}  memory: {record['memory']}  {terms}")
+
+    def after_val(self, loop, metrics):
+        n = loop.iter + 1
+        scalars = {k: float(v) for k, v in metrics.items() if np.isscalar(v) or getattr(v, "ndim", 1) == 0}
+        self._emit(loop, dict(scalars, step=n), f"Iter(val) [{n}]  " + "  ".join(f"{k}: {v:.4f}" for k, v in scalars.items()))
+
+
+@HOOKS.register_module()
+class CheckpointHook(_Hook):
+    """mmengine's CheckpointHook by iteration: `iter_{n}.pth` every `interval` iterations (and, `save_last`, after the last),
+    `last_checkpoint` naming the newest complete file, at most `max_keep_ckpts` of them kept (-1: all); `save_best='mIoU'`:
+    after each validation the key is compared by `rule` ('greater' / 'less'; None: by mmengine's key lists, 'less' for keys that
+    contain 'loss') and `best_{key}_iter_{n}.pth` replaces the previous best file.  Rank 0 alone writes.  Every file is a
+    `TrainState` snapshot; none is written for an iteration at or behind a non-finite loss."""
+    priority = 90
+    GREATER = ("acc", "top", "AR@", "auc", "precision", "mAP", "mDice", "mIoU", "mAcc", "aAcc")
+    LESS = ("loss",)
+
+    def __init__(self, interval=-1, by_epoch=False, save_last=True, max_keep_ckpts=-1, save_best=None, rule=None, **unused):
+        if by_epoch:
+            raise NotImplementedError("CheckpointHook(by_epoch=True): the loop counts iterations")
+        if save_best is not None and not isinstance(save_best, str):
+            raise NotImplementedError("CheckpointHook: save_best is one key")
+        if rule is None and save_best is not None:
+            low = save_best.lower()
+            if any(k.lower() in low for k in self.LESS):
+                rule = "less"
+            elif any(k.lower() in low for k in self.GREATER):
+                rule = "greater"
+            else:
+                raise ValueError(f"CheckpointHook: no rule can be inferred for save_best={save_best!r}; pass rule='greater' or 'less'")
+        if rule not in (None, "greater", "less"):
+            raise ValueError(f"CheckpointHook: rule {rule!r} is neither 'greater' nor 'less'")
+        self.interval, self.save_last, self.max_keep = int(interval), bool(save_last), int(max_keep_ckpts)
+        self.save_best, self.rule = save_best, rule
+        self.kept, self.best_score, self.best_path = [], None, None
+
+    def before_run(self, loop):
+        if loop.work_dir is None:
+            raise ValueError("CheckpointHook needs the loop's work_dir")
+        best = (loop.resumed or {}).get("best") or {}
+        if self.save_best is not None and best.get("key") == self.save_best:
+            self.best_score, self.best_path = best.get("score"), best.get("path")
+
+    def _best(self):
+        return dict(key=self.save_best, score=self.best_score, path=self.best_path)
+
+    def _published(self, loop, path):
+        """behind a complete iter_{n}.pth (in the writer's thread): last_checkpoint, then the files beyond max_keep_ckpts"""
+        with open(os.path.join(loop.work_dir, "last_checkpoint"), "w") as f:
+            f.write(path)
+        self.kept.append(path)
+        while 0 < self.max_keep < len(self.kept):
+            old = self.kept.pop(0)
+            if os.path.exists(old):
+                os.remove(old)
+
+    def after_train_iter(self, loop):
+        n = loop.iter + 1
+        if not ((self.interval > 0 and n % self.interval == 0) or (self.save_last and n == loop.max_iters)):
+            return
+        loop.check_finite()          # on every rank: the error is everybody's
+        rng = loop.state.host_state()          # (a collective)
+        if loop.rank != 0:
+            return
+        loop.state.snapshot(tag=n, rng=rng)
+        loop.state.write(os.path.join(loop.work_dir, f"iter_{n}.pth"), meta=loop.meta(), best=self._best(),
+                         done=lambda path: self._published(loop, path))
+
+    def after_val(self, loop, metrics):
+        if self.save_best is None:
+            return
+        if self.save_best not in metrics:
+            raise KeyError(f"CheckpointHook(save_best={self.save_best!r}): validation returned {sorted(metrics)}")
+        score = float(metrics[self.save_best])
+        better = self.best_score is None or (score > self.best_score if self.rule == "greater" else score < self.best_score)
+        rng = loop.state.host_state() if loop.world > 1 else None          # (a collective: before any rank turns back)
+        if not better or loop.rank != 0:
+            return
+        n, old = loop.iter + 1, self.best_path
+        self.best_score, self.best_path = score, os.path.join(loop.work_dir, f"best_{self.save_best}_iter_{n}.pth")
+
+        def replaced(path):
+            if old is not None and old != path and os.path.exists(old):
+                os.remove(old)
+        loop.state.snapshot(tag=n, rng=rng)
+        loop.state.write(self.best_path, meta=loop.meta(), best=self._best(), done=replaced)
+
+
+# ---------------------------------------------------------------------------------------------------- the loop
+def _cycle(batches, skip):
+    """the batches, restarted when exhausted, from the `skip`-th on (a resumed run continues where the data stood)"""
+    if hasattr(batches, "__len__") and hasattr(batches, "__getitem__"):
+        if len(batches) == 0:
+            raise ValueError("TrainLoop: no batches")
+        i = skip
+        while True:
+            yield batches[i % len(batches)]
+            i += 1
+    while True:
+        got = False
+        for b in batches:
+            got = True
+            if skip:
+                skip -= 1
+                continue
+            yield b
+        if not got:
+            raise ValueError("TrainLoop: no batches")
+
+
+class TrainLoop:
+    """mmengine's IterBasedTrainLoop for a captured step: per iteration the next (images, segs) of `batches` (decoded uint8
+    pictures and annotations; an iterable that is restarted when exhausted) -> `augment(images, segs, out=(step.static_in,
+    step.static_seg))` -> `step()` (at world size > 1, where the step holds no optimizer: -> `step.red.reduce()` ->
+    `optimizer.step()` -> `log.append()`) -> `scheduler.step()` -> the hooks.  Nothing in an iteration reads the device; the log,
+    validation and checkpoint iterations do (one `TrainLog.read()`, `step.check()`).  Every `val_interval` iterations and after the
+    last, `validate()` -> a metric dictionary (a closure over `evaluate(...)`), handed to the hooks' `after_val`.
+
+    `hooks`: objects or the configs' dictionaries (`dict(type='LoggerHook', interval=50)`), run in ascending `priority`.
+    `load_from`: a checkpoint whose weights are loaded before the first iteration; with `resume` also the optimizer, the scheduler,
+    the augment generator and the iteration count (`resume=True` alone: the file `{work_dir}/last_checkpoint` names)."""
+
+    def __init__(self, step, optimizer, scheduler, augment, batches, max_iters, val_interval=None, validate=None, hooks=(),
+                 work_dir=None, load_from=None, resume=False, async_write=True):
+        self.step, self.optimizer, self.scheduler, self.augment, self.batches = step, optimizer, scheduler, augment, batches
+        self.max_iters, self.val_interval, self.validate = int(max_iters), val_interval, validate
+        self.work_dir, self.load_from, self.resume = work_dir, load_from, bool(resume)
+        self.rank, self.world = _rank_world()
+        self.log = getattr(step, "log", None)
+        # a step that does not hold the optimizer (world size > 1: the all-reduce lies between the replay and the update) is
+        # followed by `step.red.reduce()` and `optimizer.step()` here, and the log's row by an eager append behind them
+        self.eager_update = hasattr(step, "red") and getattr(step, "optimizer", None) is None
+        self.eager_append = self.log is not None and not getattr(step, "log_captured", True)
+        if self.eager_append:
+            self.log.bind({**step.log_terms, "grad_norm": optimizer.grad_norm, "clip_coef": optimizer.clip_coef})
+        self.state = TrainState(step.model, optimizer, scheduler, augment, async_write=async_write)
+        built = [HOOKS.build(h) if isinstance(h, dict) else h for h in hooks]
+        self.hooks = sorted(built, key=lambda h: getattr(h, "priority", 50))
+        self.iter, self.lr, self.resumed, self.val_metrics = 0, None, None, None
+        self._read = (None, None)
+
+    def _call(self, name, *args):
+        for h in self.hooks:
+            fn = getattr(h, name, None)
+            if fn is not None:
+                fn(self, *args)
+
+    def meta(self):
+        return dict(iter=self.iter + 1, max_iters=self.max_iters)
+
+    def check_finite(self):
+        """-> the log as of this iteration (read once per iteration, whoever asks), after raising for what went wrong on the device
+        since the last look: FloatingPointError naming the FIRST iteration with a non-finite term, carrying the step's own status
+        error (`step.check()`: a label outside the classes, non-finite matching costs) where that is the cause."""
+        if self._read[0] == self.iter:
+            return self._read[1]
+        read = self.log.read() if self.log is not None else None
+        bad = None if read is None or read.first_nonfinite is None else self.log.base + read.first_nonfinite + 1
+        try:
+            if hasattr(self.step, "check"):
+                self.step.check()
+        except Exception as e:
+            if bad is None:
+                raise
+            raise FloatingPointError(f"non-finite training terms first at iteration {bad}: {e}") from e
+        if bad is not None:
+            row = self.log.base + read.count - len(read.rows)
+            seen = ""
+            if row < bad <= row + len(read.rows):
+                vals = read.rows[bad - 1 - row]
+                seen = ": " + ", ".join(f"{k} = {v}" for k, v in zip(read.names, vals) if not np.isfinite(v))
+            raise FloatingPointError(f"non-finite training terms first at iteration {bad}{seen}; checkpoints up to iteration "
+                                     f"{bad - 1} predate it")
+        self._read = (self.iter, read)
+        return read
+
+    def _validate(self):
+        self.check_finite()
+        model = self.step.model
+        training = getattr(model, "training", None)
+        metrics = self.validate()
+        if training:
+            model.train()
+        self.val_metrics = metrics
+        self._call("after_val", metrics)
+
+    def run(self):
+        start = 0
+        try:
+            path = self.load_from
+            if self.resume and path is None:
+                with open(os.path.join(self.work_dir, "last_checkpoint")) as f:
+                    path = f.read().strip()
+            if path is not None:
+                self.resumed = self.state.load(path, resume=self.resume)
+                if self.resume:
+                    start = int(self.resumed["meta"]["iter"])
+            self.iter = start
+            if self.log is not None:
+                self.log.base = start - self.log.read().count          # row 0 of a fresh log is iteration start + 1
+            self._call("before_run")
+            batches = _cycle(self.batches, start)
+            out = (self.step.static_in, self.step.static_seg)
+            for it in range(start, self.max_iters):
+                self.iter = it
+                images, segs = next(batches)
+                self.augment(images, segs, out=out)
+                self.step()
+                if self.eager_update:
+                    self.step.red.reduce()
+                    self.step.red.wait()
+                    self.optimizer.step()
+                if self.eager_append:
+                    self.log.append()
+                self.lr = self.optimizer.param_groups[0]["lr"]          # this iteration's: the scheduler moves on below
+                self.scheduler.step()
+                self._call("after_train_iter")
+                n = it + 1
+                if self.validate is not None and ((self.val_interval and n % self.val_interval == 0) or n == self.max_iters):
+                    self._validate()
+            self._call("after_run")
+        finally:
+            self.state.close()
+        return self.val_metrics
