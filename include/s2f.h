@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 44
+#define S2F_ABI_VERSION 45
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -937,6 +937,29 @@ int s2f_adamw_step(const int64_t* slots, const float* hyper, const int32_t* chun
 #define S2F_TRAIN_LOG_MAX_TERMS 256
 int s2f_state_copy(const int64_t* slots, const int32_t* chunks, int nchunks, void* flat, int to_params, void* stream);
 int s2f_train_log_append(const float* const* srcs, int n, float* ring, int window, int stride, int64_t* head, void* stream);
+
+/* ---- firing log: per-neuron firing rows from inside the captured step (csrc/firinglog.hip, ABI 45) -------------------------------
+ * The neuron kernels count into `stats` (above: uint64[S2F_STAT_SLOTS][2] per neuron); this launch is the device-side path from those
+ * counters to a log that the host reads once per interval (tools/cal_firing_num.py reads its hooks' sums on the host, per image).
+ *   s2f_firing_log_append  counters uint64 [n][S2F_STAT_SLOTS][2], ONE allocation: neuron i's `stats` is the slice i.  ring int64
+ *                          [window][n][2]; silent int32 [n]; head int64 [4], initialised by the caller to {0, -1, 0, 0}.  One launch,
+ *                          one wave per neuron i:
+ *                            {sum, nonzero} = the 64-bit sums of the neuron's 256 slots  ->  ring[head[0] % window][i];
+ *                            the neuron's 512 counter words are cleared (the next iteration counts from zero);
+ *                            silent[i] == -1 (not watched: a neuron the step never runs) stays -1; otherwise silent[i] becomes
+ *                            silent[i] + 1 where sum == 0, and 0 where it is not;
+ *                            where silent[i] REACHES `patience`, the event head[0] * 2^32 + i is offered to head[1], which keeps
+ *                            the minimum under UNSIGNED comparison (-1: none yet) -- the lowest neuron of the earliest row,
+ *                            whatever order the workgroups finish in; a later event never replaces it.
+ *                          head[0], the number of rows appended, advances exactly once per launch: every workgroup uses the value
+ *                          it had at entry.  head[2] is the launch's own workspace (the ticket of a last-workgroup-done scheme),
+ *                          0 at entry and on exit; head[3] is reserved.  Appends are ordered by their stream.
+ *                          S2F_EINVAL: null pointer, n < 1, window < 1, patience < 1; S2F_EALIGN: counters not 16-byte, ring / head
+ *                          not 8-byte, silent not 4-byte aligned.
+ * Plain vector loads and stores and ordinary global atomics (one add and at most one min per neuron); nothing allocates or
+ * synchronises: capturable behind the step's last launch. */
+int s2f_firing_log_append(uint64_t* counters, int n, int64_t* ring, int window, int32_t* silent, int patience, int64_t* head,
+                          void* stream);
 
 /* ---- general strided fp32 product on the vector ALUs (csrc/bmm.hip, round 6) -----------------------------------------------
  * C[b][m][n] = sum_k A[b][m][k] B[b][k][n], every operand with explicit ELEMENT strides (a transposed or broadcast operand is a

@@ -3,13 +3,15 @@
 The reference registers a forward hook on every Q_IFNode and accumulates mean(output * quant) / test_num per module
 name.  Here each neuron's kernel launch adds {sum of integer counts, number of non-zero counts} into a 2-word device
 counter (wave-level reduction inside s2f_lif_fwd), so recording costs no extra pass over the activations."""
+import collections
 import json
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from . import ops
-from .neuron import Q_IFNode
+from .neuron import LIFNode, Q_IFNode
 
 
 class FiringRecorder:
@@ -60,3 +62,138 @@ class FiringRecorder:
             f.write(",T\n")
             for n, v in self.result(test_num)["t0"].items():
                 f.write(f"{n},{v}\n")
+
+
+class FiringRead(collections.namedtuple("FiringRead", "names sums elems count silent first_dead scale")):
+    """What `FiringLog.read()` returns.  names: the neurons, in `named_modules()` order; sums: int64 [rows, n, 2] = {sum of counts,
+    non-zero counts} of the last min(count, window) rows, oldest first; elems: int64 [n], the elements each neuron fires over in
+    one forward (0: not watched); count: rows appended so far; silent: int32 [n], the rows in a row each neuron has now been
+    silent for (-1: not watched); first_dead: (row, name) of the first neuron whose streak reached the log's patience, or None;
+    scale: quant / D per neuron."""
+    __slots__ = ()
+
+    def _per_elem(self, k):
+        watched = self.elems > 0
+        out = np.full(self.sums.shape[:2], np.nan)
+        out[:, watched] = self.sums[:, watched, k] / self.elems[watched]
+        return out
+
+    def rates(self):
+        """float64 [rows, n]: mean(output * quant) of every neuron in every row (cal_firing_num.py:140-160; FiringRecorder's
+        number); NaN for a neuron that is not watched"""
+        return self._per_elem(0) * self.scale
+
+    def nonzero(self):
+        """float64 [rows, n]: the share of elements with a non-zero count; NaN for a neuron that is not watched"""
+        return self._per_elem(1)
+
+
+class FiringLog:
+    """Firing counters of every neuron for EVERY iteration of a captured step, without a host stop: the counters of all neurons
+    are slices of one allocation, `append()` is one launch (ops.firing_log_append, capturable) that adds each neuron's contention
+    slots up, writes the pair into the next row of a ring on the device, clears the counters and keeps a streak of silent rows per
+    neuron, latching the first neuron that stayed silent for `patience` rows.  `read()` is one device-to-host copy.
+
+        firing = FiringLog(model, window=50)
+        step = GraphedHungarianStep(..., firing=firing)        # attach, measure, append recorded as the step's last launch
+    or around eager forwards (a validation loop):
+        firing.attach(); firing.measure(lambda: model(x0)); firing.clear()
+        for x in images: model(x); firing.append()
+        read = firing.read(); firing.detach()
+
+    Attached counters change which kernels run: the memoised, pre-fired and fused-neuron routes test `stats is None` and step aside,
+    as they do for `FiringRecorder` (which stays the tool for an evaluation table in the reference's format)."""
+
+    def __init__(self, model, window=64, patience=200, quant=8, device=None):
+        if window < 1 or patience < 1:
+            raise ValueError(f"FiringLog: window {window} and patience {patience} are at least 1")
+        self.model, self.window, self.patience, self.quant = model, int(window), int(patience), quant
+        self.nodes = OrderedDict((n, m) for n, m in model.named_modules() if isinstance(m, (Q_IFNode, LIFNode)))
+        if not self.nodes:
+            raise ValueError("FiringLog: the model has no Q_IFNode or LIFNode")
+        if device is None:
+            p = next(model.parameters(), None)
+            device = p.device if p is not None else "cpu"
+        self.device = torch.device(device)
+        n = self.n = len(self.nodes)
+        self.names = list(self.nodes)
+        self.counters = torch.zeros(n, ops.STAT_SLOTS, 2, dtype=torch.int64, device=self.device)
+        # head (int64 [4]), silent (int32 [n], padded to whole int64 words) and ring in ONE allocation: read() is one copy
+        pad = (n + 1) // 2
+        self._buf = torch.zeros(4 + pad + self.window * n * 2, dtype=torch.int64, device=self.device)
+        self.head = self._buf[:4]
+        self.silent = self._buf[4:4 + pad].view(torch.int32)[:n]
+        self.ring = self._buf[4 + pad:].view(self.window, n, 2)
+        self.head[1] = -1
+        self._host = torch.zeros_like(self._buf, device="cpu")
+        self._event = None
+        if self.device.type == "cuda":
+            self._host = self._host.pin_memory()
+            self._event = torch.cuda.Event()
+        self.elems = torch.zeros(n, dtype=torch.int64)          # (host) elements per neuron in one forward; 0: not watched
+        self.scale = np.array([quant / m.D for m in self.nodes.values()], np.float64)
+        self.attached = False
+        self.base = 0          # the iterations that ran before row 0 (a resumed run)
+
+    # ------------------------------------------------------------------------------------------------ the neurons' counters
+    def attach(self):
+        """every neuron's `stats` <- its slice of the counters.  Raises when a neuron already counts into something (a live
+        FiringRecorder, another FiringLog)."""
+        if self.attached:
+            return
+        busy = [n for n, m in self.nodes.items() if m.stats is not None]
+        if busy:
+            raise RuntimeError(f"FiringLog.attach: {len(busy)} neurons already record firing (a live FiringRecorder or another "
+                               f"FiringLog), first {busy[0]!r}")
+        for i, m in enumerate(self.nodes.values()):
+            m.stats = self.counters[i]
+        self.attached = True
+
+    def detach(self):
+        if self.attached:
+            for m in self.nodes.values():
+                m.stats = None
+        self.attached = False
+
+    def measure(self, forward):
+        """Run `forward()` once and take from it how many elements each neuron fires over (`elems`): a neuron the forward never
+        runs is not watched (silent = -1), every other starts with a streak of 0.  Not under capture; what the forward counted
+        stays in the counters until `clear()` or the next `append()`."""
+        if not self.attached:
+            raise RuntimeError("FiringLog.measure before attach")
+        for m in self.nodes.values():
+            m.stats_elems = 0
+        forward()
+        self.elems = torch.tensor([int(m.stats_elems) for m in self.nodes.values()], dtype=torch.int64)
+        self.silent.copy_(torch.where(self.elems > 0, 0, -1).to(torch.int32))
+
+    def clear(self):
+        """counters, ring and head as new; the streaks of the watched neurons to 0.  Not under capture."""
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FiringLog.clear under capture")
+        self.counters.zero_()
+        self.ring.zero_()
+        self.silent.clamp_(max=0)          # (-1 stays)
+        self.head.copy_(torch.tensor([0, -1, 0, 0], dtype=torch.int64))
+
+    # ------------------------------------------------------------------------------------------------ rows
+    def append(self):
+        """one row: ONE launch on the current stream, capturable"""
+        ops.firing_log_append(self.counters, self.ring, self.silent, self.head, self.patience)
+
+    def read(self):
+        """-> FiringRead.  One device-to-host copy on the current stream, and a wait for that copy."""
+        if self._event is not None:
+            self._host.copy_(self._buf, non_blocking=True)
+            self._event.record()
+            self._event.synchronize()
+        else:
+            self._host.copy_(self._buf)
+        n, pad = self.n, (self.n + 1) // 2
+        count, dead = int(self._host[0]), int(self._host[1])
+        k = min(count, self.window)
+        ring = self._host[4 + pad:].view(self.window, n, 2).numpy()
+        sums = np.stack([ring[(count - k + i) % self.window] for i in range(k)]) if k else np.zeros((0, n, 2), np.int64)
+        silent = self._host[4:4 + pad].view(torch.int32)[:n].numpy().copy()
+        first = None if dead < 0 else (dead >> 32, self.names[dead & 0xffffffff])
+        return FiringRead(list(self.names), sums.copy(), self.elems.numpy().copy(), count, silent, first, self.scale)

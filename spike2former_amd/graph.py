@@ -32,7 +32,7 @@ def _process_group():
 class _Captured:
     """A step with static input `static_in`, recorded as one hipGraph per stage.  `red`: the flat gradient buffer
     (dist.FlatGradAllReduce) of the steps that pack into one; `optimizer`: a train.FlatAdamW captured behind the packing."""
-    optimizer = log = None
+    optimizer = log = firing = None
 
     def _capture(self, warm, warmup, stages, context=None):
         """`warmup` calls of `warm` on a side stream (allocator pools, lazy inits, caches), then each callable of `stages`
@@ -109,6 +109,22 @@ class _Captured:
         if self.log is not None and self.log_captured:
             self.log.bind(self.log_terms)
 
+    def _watch_firing(self, forward):
+        """before the warm-up passes: every neuron counts into `self.firing` (firing.FiringLog) from here on -- which changes the
+        launch structure: the memoised, pre-fired and fused-neuron routes step aside for a neuron with counters -- and one
+        `forward()` tells the log which neurons the step runs, and over how many elements."""
+        if self.firing is not None:
+            self.firing.attach()
+            with torch.no_grad():
+                self.firing.measure(forward)
+
+    def _record_firing(self):
+        """while the LAST stage is recorded, as its last launch: one row of every neuron's counters per replay, at every world
+        size (the forward is inside the graph on every rank; each rank logs its own shard).  The caller clears the log once the
+        capture has ended: what the warm-up passes counted is not row 0."""
+        if self.firing is not None:
+            self.firing.append()
+
     def _forward(self):
         reset_net(self.model)
         self.red.zero()
@@ -124,10 +140,11 @@ class GraphedStep(_Captured):
     """`optimizer` (train.FlatAdamW over `grad_buffer`): the parameter update -- clip + AdamW, three launches -- is captured behind
     the gradient packing, so one replay is one training ITERATION (single process; with N > 1 the all-reduce sits between the step
     and the update, which the caller then runs eagerly: `step(); grad_buffer.reduce(); optimizer.step()`).  `log` (runner.TrainLog):
-    every replay appends {loss, grad_norm, clip_coef} to it, at the end of the graph; None: the capture holds no such launch."""
+    every replay appends {loss, grad_norm, clip_coef} to it, at the end of the graph; None: the capture holds no such launch.
+    `firing` (firing.FiringLog): see GraphedHungarianStep."""
 
-    def __init__(self, model, loss_fn, example_input, grad_buffer=None, warmup=3, optimizer=None, log=None):
-        self.model, self.loss_fn, self.log = model, loss_fn, log
+    def __init__(self, model, loss_fn, example_input, grad_buffer=None, warmup=3, optimizer=None, log=None, firing=None):
+        self.model, self.loss_fn, self.log, self.firing = model, loss_fn, log, firing
         self.static_in = example_input.clone()
         self.grad_buffer = grad_buffer
         self.optimizer = optimizer
@@ -138,10 +155,14 @@ class GraphedStep(_Captured):
             self.static_loss = self._eager_step()
             if self.log is not None:
                 self._record_log({"loss": self.static_loss})
+            self._record_firing()
+        self._watch_firing(lambda: (reset_net(self.model), self.model(self.static_in)))
         # ops.GLUE_MODE: the residual aten calls of the step (autograd's gradient accumulation, scalar multiples, copies, fills, small
         # sums) are routed to csrc/glue.hip while the step is RECORDED -- the replay then consists of this package's kernels only
         self.graph, = self._capture(self._eager_step, warmup, [record], context=ops.glue_mode if ops.GLUE_MODE else None)
         self._bind_log()
+        if self.firing is not None:
+            self.firing.clear()
 
     def _eager_step(self):
         reset_net(self.model)
@@ -240,16 +261,22 @@ class GraphedHungarianStep(_Captured):
     `log` (runner.TrainLog): the last graph ends with one more launch that appends every entry of the loss dictionary, their sum
     `loss` and, with a captured optimizer, its grad_norm and clip_coef to a ring on the device -- the record of EVERY iteration,
     and of the first one with a non-finite term, that runner.LoggerHook reads once per log interval.  None: the capture is the
-    one without it."""
+    one without it.
+
+    `firing` (firing.FiringLog over `model`): every neuron counts its spikes into the log's counters, and the last graph ends with
+    one launch that turns them into a row per replay -- per-neuron firing rates of EVERY iteration, and the first neuron that stays
+    silent for the log's `patience` iterations, read by runner.LoggerHook with the losses.  Counters change the launch structure of
+    the step (the memoised, pre-fired and fused-neuron routes step aside for a neuron that has them); None: nothing is attached,
+    allocated or launched, the capture is the one without it."""
 
     def __init__(self, model, example_input, example_seg, grad_buffer, warmup=3, ignore_index=None, optimizer=None, assign="host",
-                 log=None):
+                 log=None, firing=None):
         if assign not in ("host", "device"):
             raise ValueError(f"assign must be 'host' or 'device', got {assign!r}")
         if assign == "device" and not (example_input.is_cuda and example_seg.is_cuda):
             raise RuntimeError("GraphedHungarianStep(assign='device') needs CUDA tensors: the device assignment is a HIP kernel and "
                                "has no host fall-back")
-        self.assign, self.log = assign, log
+        self.assign, self.log, self.firing = assign, log, firing
         head = model.decode_head
         self.optimizer = optimizer
         if optimizer is not None:
@@ -259,6 +286,7 @@ class GraphedHungarianStep(_Captured):
         self.static_in = example_input.clone()
         self.static_seg = self.crit.seg_as_u8(example_seg, self.ignore_index).clone()
         dev = example_input.device
+        self._watch_firing(self._forward)
         with torch.no_grad():                                     # shapes of the outputs (and a first warm-up)
             cls, masks = self._forward()
         if not self.crit.semantic_ok(masks, self.static_seg):
@@ -301,6 +329,7 @@ class GraphedHungarianStep(_Captured):
             if assign == "device":
                 self.sticky.bitwise_or_(self.status)
                 self.host_status.copy_(self.sticky, non_blocking=True)
+            self._record_firing()
 
         def whole():
             head()
@@ -309,6 +338,8 @@ class GraphedHungarianStep(_Captured):
         self._bind_log()
         for name, graph in zip(("graph", "graph_tail") if assign == "device" else ("graph_a", "graph_b"), self._graphs):
             setattr(self, name, graph)
+        if self.firing is not None:
+            self.firing.clear()                              # (the warm-up passes' spikes are not row 0)
         if assign == "device":
             self.sticky.zero_()                              # (whatever the warm-up on the example inputs left is not a replay's)
             torch.cuda.synchronize()

@@ -1,10 +1,11 @@
-"""The two launches a training loop adds to the captured step (csrc/trainstate.hip): `state_copy`, every tensor of a pointer table
-into one flat buffer or back, and `train_log_append`, one row of per-iteration scalars into a ring on the device.  CUDA tensors run
-the kernels on the current stream; CPU tensors run the same semantics in torch (the package's CPU implementation of these two ops,
-as the numpy route of `seg_draw`), so the classes of runner.py can be driven without a GPU."""
+"""The launches a training loop adds to the captured step: `state_copy`, every tensor of a pointer table into one flat buffer or
+back, and `train_log_append`, one row of per-iteration scalars into a ring on the device (csrc/trainstate.hip); `firing_log_append`,
+one row of per-neuron firing counters into a ring of its own (csrc/firinglog.hip).  CUDA tensors run the kernels on the current
+stream; CPU tensors run the same semantics in torch (the package's CPU implementation of these three ops, as the numpy route of
+`seg_draw`), so the classes of runner.py and firing.py can be driven without a GPU."""
 import torch
 
-from .core import _ptr, _stream, check, lib
+from .core import STAT_SLOTS, _ptr, _stream, check, lib
 
 TRAIN_LOG_MAX_TERMS = 256          # include/s2f.h S2F_TRAIN_LOG_MAX_TERMS
 
@@ -107,4 +108,45 @@ def train_log_append(srcs, ring, head, table=None, n=None):
     return ring
 
 
-__all__ = ["TRAIN_LOG_MAX_TERMS", "state_table", "state_copy", "train_log_table", "train_log_append"]
+def firing_log_append(counters, ring, silent, head, patience):
+    """One row of firing counters (s2f_firing_log_append).  counters: int64 [n, STAT_SLOTS, 2], ONE contiguous allocation whose
+    slice i is neuron i's `stats`; ring: int64 [window, n, 2]; silent: int32 [n]; head: int64 [4] = {rows appended, first dead
+    neuron as row * 2^32 + i or -1, the kernel's ticket word (0 between launches), reserved}.  Per neuron: {sum of counts, non-zero
+    counts} over the slots -> ring[head[0] % window, i]; the counters are cleared; silent[i] == -1 (not watched) stays, otherwise
+    it counts the rows in a row whose sum was 0; the first neuron whose streak reaches `patience` is latched in head[1] (the lowest
+    index of the earliest row).  head[0] += 1.  One launch on the current stream, no synchronisation; capturable."""
+    if counters.dtype != torch.int64 or counters.dim() != 3 or tuple(counters.shape[1:]) != (STAT_SLOTS, 2) or not counters.is_contiguous():
+        raise ValueError(f"firing_log_append: counters is a contiguous int64 [n, {STAT_SLOTS}, 2]")
+    n = counters.shape[0]
+    if ring.dtype != torch.int64 or ring.dim() != 3 or tuple(ring.shape[1:]) != (n, 2) or not ring.is_contiguous():
+        raise ValueError(f"firing_log_append: ring is a contiguous int64 [window, {n}, 2]")
+    if silent.dtype != torch.int32 or tuple(silent.shape) != (n,) or not silent.is_contiguous():
+        raise ValueError(f"firing_log_append: silent is a contiguous int32 [{n}]")
+    if head.dtype != torch.int64 or tuple(head.shape) != (4,) or not head.is_contiguous():
+        raise ValueError("firing_log_append: head is a contiguous int64 [4]")
+    if not (ring.device == silent.device == head.device == counters.device):
+        raise RuntimeError("firing_log_append: counters, ring, silent and head live on one device")
+    window, patience = ring.shape[0], int(patience)
+    if n < 1 or window < 1 or patience < 1:
+        raise ValueError(f"firing_log_append: {n} neurons, a ring of {window} rows, patience {patience}: each is at least 1")
+    if not counters.is_cuda:
+        count = int(head[0])
+        sums = counters.sum(1)
+        ring[count % window] = sums
+        counters.zero_()
+        watched = silent != -1
+        streak = torch.where(sums[:, 0] == 0, silent + 1, torch.zeros_like(silent))
+        silent.copy_(torch.where(watched, streak, silent))
+        dead = torch.nonzero(watched & (silent == patience))
+        if dead.numel():
+            event, mask = (count << 32) | int(dead[0]), (1 << 64) - 1
+            if event & mask < int(head[1]) & mask:          # the minimum under unsigned comparison: -1 is the largest
+                head[1] = event
+        head[0] = count + 1
+        return ring
+    check(lib.s2f_firing_log_append(_ptr(counters), n, _ptr(ring), window, _ptr(silent), patience, _ptr(head), _stream()),
+          "s2f_firing_log_append")
+    return ring
+
+
+__all__ = ["TRAIN_LOG_MAX_TERMS", "state_table", "state_copy", "train_log_table", "train_log_append", "firing_log_append"]

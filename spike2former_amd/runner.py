@@ -22,7 +22,8 @@ behaviour, and like the schedulers of train.py their parity is UNPINNED (DESIGN.
 named as mmengine names them in file names and log lines: "iteration n" is the n-th, counted from 1.
 
     log = TrainLog(window=50)
-    step = GraphedHungarianStep(model, example_in, example_seg, red, optimizer=optim, assign="device", log=log)
+    step = GraphedHungarianStep(model, example_in, example_seg, red, optimizer=optim, assign="device", log=log,
+                                firing=FiringLog(model, window=50))          # (optional: per-neuron firing rates in the log)
     loop = TrainLoop(step, optim, sched, aug, batches, max_iters=160000, val_interval=2500, validate=lambda: evaluate(...),
                      hooks=[dict(type='LoggerHook', interval=50), dict(type='CheckpointHook', interval=10000, save_best='mIoU')],
                      work_dir='work_dirs/run')
@@ -394,7 +395,15 @@ class LoggerHook(_Hook):
     0, and at the last one, ONE `TrainLog.read()`; the mean of the last `window_size` rows of every term, the learning rate of
     parameter group 0 in that iteration, seconds per iteration since the last line, the time left at that rate and the peak of
     allocated device memory in MiB -- one line on the `spike2former_amd` logger and one JSON line in {work_dir}/vis_data/scalars.json.
-    A non-finite value in ANY iteration since the last check raises FloatingPointError naming the first (TrainLoop.check_finite)."""
+    A non-finite value in ANY iteration since the last check raises FloatingPointError naming the first (TrainLoop.check_finite).
+
+    A step built with `firing=FiringLog(...)`: ONE `FiringLog.read()` more per log line.  Over the rows appended since the last
+    line (the ring holds at least `interval` of them) the line and scalars.json carry `firing/mean` (the mean rate over the watched
+    neurons), `firing/min` and `firing/min_name` (the neuron with the lowest mean rate) and `firing/silent` (the watched neurons
+    that did not fire in the last row); every neuron's mean rate and non-zero share go to {work_dir}/vis_data/firing.jsonl, one JSON
+    line per log line.  The first time a neuron has stayed silent for the log's `patience` iterations, ONE warning names it and the
+    iteration its streak reached the patience: a finding, not an error -- nothing is raised.  Every rank reads its own rank's
+    counters; rank 0 writes."""
     priority = 60
     HIDDEN = ("clip_coef",)
 
@@ -410,7 +419,34 @@ class LoggerHook(_Hook):
             raise ValueError("LoggerHook needs a step built with log=TrainLog(...)")
         if loop.log.window < self.window_size:
             raise ValueError(f"LoggerHook(window_size={self.window_size}) over a TrainLog of {loop.log.window} rows")
+        if loop.firing is not None and loop.firing.window < self.interval:
+            raise ValueError(f"LoggerHook(interval={self.interval}) over a FiringLog of {loop.firing.window} rows")
         self._clock, self._last = time.perf_counter(), loop.iter
+        self._dead_seen = False
+
+    def _firing(self, loop, n, record):
+        """the rows since the last line -> the record's firing/ keys and one line of firing.jsonl; the dead-neuron warning"""
+        fl = loop.firing
+        read = fl.read()
+        k = min(n - self._last, len(read.sums), read.count)
+        watched = read.elems > 0
+        if k > 0 and watched.any():
+            rates, nz = read.rates()[-k:].mean(0), read.nonzero()[-k:].mean(0)
+            low = int(np.flatnonzero(watched)[np.argmin(rates[watched])])
+            record["firing/mean"] = float(rates[watched].mean())
+            record["firing/min"], record["firing/min_name"] = float(rates[low]), read.names[low]
+            record["firing/silent"] = int((read.silent[watched] >= 1).sum())
+            if loop.work_dir is not None and loop.rank == 0:
+                path = os.path.join(loop.work_dir, "vis_data", "firing.jsonl")
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                idx = np.flatnonzero(watched)
+                with open(path, "a") as f:
+                    f.write(json.dumps(dict(iter=n, rows=k, rates={read.names[i]: float(rates[i]) for i in idx},
+                                            nonzero={read.names[i]: float(nz[i]) for i in idx})) + "\n")
+        if read.first_dead is not None and not self._dead_seen:
+            self._dead_seen = True
+            row, name = read.first_dead
+            logger.warning(f"neuron {name} has not fired for {fl.patience} iterations, up to iteration {fl.base + row + 1}")
 
     def _emit(self, loop, record, line):
         logger.info(line)
@@ -428,15 +464,18 @@ class LoggerHook(_Hook):
         rows = read.rows[-self.window_size:]
         now = time.perf_counter()
         per_iter = (now - self._clock) / max(n - self._last, 1)
-        self._clock, self._last = now, n
         record = dict(lr=float(loop.lr), time=per_iter, eta=per_iter * (loop.max_iters - n),
                       memory=int(torch.cuda.max_memory_allocated() // 2 ** 20) if torch.cuda.is_available() else 0)
         for j, name in enumerate(read.names):
             if name not in self.HIDDEN and len(rows):
                 record[name] = float(np.mean(np.ascontiguousarray(rows[:, j])))          # fp32, in the rows' order
+        if loop.firing is not None:
+            self._firing(loop, n, record)
+        self._clock, self._last = now, n
         record.update(iter=n, step=n)
         eta = str(datetime.timedelta(seconds=int(record["eta"])))
-        terms = "  ".join(f"{k}: {v:.4f}" for k, v in record.items() if k not in ("lr", "time", "eta", "memory", "iter", "step"))
+        terms = "  ".join(f"{k}: {v}" if isinstance(v, (str, int)) else f"{k}: {v:.4f}" for k, v in record.items()
+                          if k not in ("lr", "time", "eta", "memory", "iter", "step"))
         self._emit(loop, record, f"Iter(train) [{n:>{len(str(loop.max_iters))}}/{loop.max_iters}]  lr: {record['lr']:.4e}  eta: {eta}  "
                                  f"time: {per_iter:.4f}  memory: {record['memory']}  {terms}")
 
@@ -569,6 +608,7 @@ class TrainLoop:
         self.work_dir, self.load_from, self.resume = work_dir, load_from, bool(resume)
         self.rank, self.world = _rank_world()
         self.log = getattr(step, "log", None)
+        self.firing = getattr(step, "firing", None)          # a firing.FiringLog the step appends a row to per replay
         # a step that does not hold the optimizer (world size > 1: the all-reduce lies between the replay and the update) is
         # followed by `step.red.reduce()` and `optimizer.step()` here, and the log's row by an eager append behind them
         self.eager_update = hasattr(step, "red") and getattr(step, "optimizer", None) is None
@@ -620,7 +660,14 @@ class TrainLoop:
         self.check_finite()
         model = self.step.model
         training = getattr(model, "training", None)
-        metrics = self.validate()
+        watching = self.firing is not None and self.firing.attached
+        if watching:
+            self.firing.detach()          # a validation forward's spikes are not the next iteration's
+        try:
+            metrics = self.validate()
+        finally:
+            if watching:
+                self.firing.attach()          # (the same counters at the same addresses: the captured launches still hold)
         if training:
             model.train()
         self.val_metrics = metrics
@@ -640,6 +687,8 @@ class TrainLoop:
             self.iter = start
             if self.log is not None:
                 self.log.base = start - self.log.read().count          # row 0 of a fresh log is iteration start + 1
+            if self.firing is not None:          # (the ring and the streaks are in no checkpoint: a resumed run starts them afresh)
+                self.firing.base = start - self.firing.read().count
             self._call("before_run")
             batches = _cycle(self.batches, start)
             out = (self.step.static_in, self.step.static_seg)
