@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 45
+#define S2F_ABI_VERSION 46
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -41,7 +41,7 @@ const char* s2f_last_error(void);
  * (hipExtLaunchKernelGGL start/stop events = the dispatch packet's own begin/end timestamps, what rocprofv3 reports).
  *   s2f_event_create/destroy: a hipEvent_t as void*.
  *   s2f_time_next_call(start, stop): arms THIS thread; the next s2f_lif_fwd / s2f_lif_bwd / s2f_bn_stats /
- *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist / s2f_seg_confusion / s2f_seg_draw / s2f_state_copy call stamps `start` with the begin of
+ *       s2f_bn_act_fwd / s2f_bn_act_bwd / s2f_spike_gemm_fwd / s2f_spike_gemm_dw / s2f_spike_conv3x3_* / s2f_split_gemm / s2f_seg_hist / s2f_seg_confusion / s2f_seg_draw / s2f_slide_windows / s2f_slide_accumulate / s2f_state_copy call stamps `start` with the begin of
  *       its first kernel and `stop` with the end of its last one, then disarms.  Not valid during stream capture.
  *   s2f_event_elapsed_us: stop - start in microseconds (both must have completed: synchronise first). */
 void* s2f_event_create(void);
@@ -562,6 +562,35 @@ int s2f_tta_accumulate(const float* x, float* acc, int K, int64_t plane_stride, 
                        int H, int W, int flags, int first, void* stream);
 /* acc [K, HW] /= n_views in place, then the arg-max / threshold of s2f_seg_argmax (no sigmoid) into label or label_f. */
 int s2f_tta_finish(float* acc, int64_t* label, float* label_f, int K, int64_t HW, int n_views, float threshold, void* stream);
+
+/* ---- sliding-window inference: cut the windows, merge their logits (csrc/slide.hip, ABI 46) ---------------------------------------
+ * EncoderDecoder.slide_inference (mmseg/models/segmentors/encoder_decoder.py:246-296: per window a slice, an F.pad to the full map,
+ * preds += , count_mat += 1, and a final preds / count_mat) as one gather launch per group of windows, with no padded temporary, no
+ * zero-fill, no count map and no division pass.
+ * The window grid is a function of (H, W, crop_h, crop_w, stride_h, stride_w) alone and both kernels compute it themselves:
+ *     ny = max(H - crop_h + stride_h - 1, 0) / stride_h + 1            (nx alike from W, crop_w, stride_w)
+ *     row i of the grid:   y2 = min(i * stride_h + crop_h, H),  y1 = max(y2 - crop_h, 0)            (columns alike)
+ *     every window is eh = min(crop_h, H) by ew = min(crop_w, W); window index j = i * nx + jx, row-major: the reference's loop
+ *     order.  The windows of the last row / column are shifted back inside the picture, so two windows may coincide: both count.
+ * s2f_slide_windows: out [n, B, C, eh, ew] (contiguous, window-major) <- windows w0 .. w0 + n - 1 of x [B, C, H, W].  One launch;
+ *     x and out need only their 4-byte element alignment (a window starts at any column).
+ * s2f_slide_accumulate: merges logits [n, B, K, eh, ew], the logits of windows w0 .. w0 + n - 1, into preds [B, K, H, W].  For every
+ *     pixel covered by at least one window of the group and every (b, k):
+ *       acc = +0.0 if the group holds the FIRST of all windows that cover the pixel, else the stored preds value;
+ *       acc += the group's covering windows, in increasing window index, each a separate fp32 addition;
+ *       if the group holds the LAST window that covers the pixel: acc /= the number of ALL windows that cover it (IEEE fp32 division);
+ *       preds = acc.
+ *     Pixels outside the group's windows are not touched.  Submitted for all groups in INCREASING w0, this is bit for bit the
+ *     reference's loop (which adds exact zeros where a window does not cover a pixel), for every grouping.  preds MAY START
+ *     UNINITIALISED: no stale value is read.  A grid that leaves pixels uncovered (stride > crop on an axis where the picture is
+ *     larger than the crop) leaves them unwritten: the caller checks coverage (the reference's assert) on the host.
+ * Bounds (S2F_EINVAL before any launch): non-null pointers; B, C / K, H, W, crops, strides > 0; B * C (B * K) < 65536;
+ *     0 <= w0, n > 0, w0 + n <= ny * nx; B * C * H * W < 2^62.  S2F_EALIGN: a pointer that is not 4-byte aligned.
+ * Nothing is allocated and nothing synchronises: capturable in a hipGraph. */
+int s2f_slide_windows(const float* x, float* out, int B, int C, int H, int W, int crop_h, int crop_w, int stride_h, int stride_w,
+                      int w0, int n, void* stream);
+int s2f_slide_accumulate(const float* logits, float* preds, int B, int K, int H, int W, int crop_h, int crop_w, int stride_h,
+                         int stride_w, int w0, int n, void* stream);
 
 /* ---- evaluation: the class histograms behind mIoU / mDice / mFscore (csrc/segmetric.hip, ABI 35) ---------------------------------
  * One image of IoUMetric.intersect_and_union (mmseg/evaluation/metrics/iou_metric.py:164-205: two boolean-mask gathers, three

@@ -70,6 +70,8 @@ SIGNATURES = {
     "s2f_seg_argmax": (_i, [_p, _p, _p, _i, _i64, _i, _f, _p]),
     "s2f_tta_accumulate": (_i, [_p, _p, _i, _i64] + [_i] * 9 + [_p]),
     "s2f_tta_finish": (_i, [_p, _p, _p, _i, _i64, _i, _f, _p]),
+    "s2f_slide_windows": (_i, [_p, _p] + [_i] * 10 + [_p]),
+    "s2f_slide_accumulate": (_i, [_p, _p] + [_i] * 10 + [_p]),
     "s2f_seg_hist": (_i, [_p, _i, _p, _i, _i64, _i64, _i, _i64, _i, _i, _i, _p, _p]),
     "s2f_seg_confusion": (_i, [_p, _i, _p, _i, _i64, _i64, _i, _i64, _i, _i, _i, _p, _p]),
     "s2f_seg_draw": (_i, [_p, _p, _i, _p, _i, _p, _i, ctypes.c_double, _i, _i, _i, _p, _p]),

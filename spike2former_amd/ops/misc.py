@@ -406,6 +406,53 @@ def tta_finish(acc, n_views, threshold=0.3):
     return out
 
 
+def _pair(v):
+    a, b = v
+    return int(a), int(b)
+
+
+def slide_grid(H, W, crop, stride):
+    """-> (ny, nx, eh, ew): the window grid of sliding-window inference for an [H, W] picture (include/s2f.h "sliding-window
+    inference"; mmseg encoder_decoder.py:262-273): ny x nx windows of eh x ew = min(crop, size) pixels, window i of an axis starting
+    at min(i * stride, size - extent).  Host arithmetic."""
+    H, W = int(H), int(W)
+    (ch, cw), (sh, sw) = _pair(crop), _pair(stride)
+    if min(H, W, ch, cw, sh, sw) <= 0:
+        raise ValueError(f"slide_grid: sizes, crop and stride are positive, got {(H, W)}, {(ch, cw)}, {(sh, sw)}")
+    return max(H - ch + sh - 1, 0) // sh + 1, max(W - cw + sw - 1, 0) // sw + 1, min(ch, H), min(cw, W)
+
+
+def slide_windows(inputs, crop, stride, w0, n):
+    """inputs [B, C, H, W] fp32 CUDA contiguous -> [n, B, C, eh, ew]: windows w0 .. w0 + n - 1 of slide_grid (row-major), window-major,
+    in one launch (s2f_slide_windows).  There is no other route: a CPU tensor raises."""
+    _need_cuda(inputs)
+    assert inputs.dtype == torch.float32 and inputs.dim() == 4 and inputs.is_contiguous(), "a contiguous fp32 [B, C, H, W] input"
+    B, C, H, W = inputs.shape
+    ny, nx, eh, ew = slide_grid(H, W, crop, stride)
+    out = torch.empty(int(n), B, C, eh, ew, dtype=torch.float32, device=inputs.device)
+    check(lib.s2f_slide_windows(_ptr(inputs), _ptr(out), B, C, H, W, *_pair(crop), *_pair(stride), int(w0), int(n), _stream()),
+          "s2f_slide_windows")
+    return out
+
+
+def slide_accumulate(preds, logits, crop, stride, w0):
+    """preds [B, K, H, W] <- the merge of logits [n, B, K, eh, ew], the logits of windows w0 .. w0 + n - 1 (s2f_slide_accumulate): per
+    covered pixel the windows are added in increasing index -- from +0.0 when the group holds the pixel's first window, else from
+    the stored value -- and divided by the pixel's coverage count when it holds the last.  Groups go in increasing w0; preds may
+    start uninitialised; after the last group it is mmseg's slide_inference result, bit for bit.  Both fp32 CUDA contiguous."""
+    _need_cuda(preds, logits)
+    assert preds.dtype == torch.float32 and preds.dim() == 4 and preds.is_contiguous(), "a contiguous fp32 [B, K, H, W] map"
+    B, K, H, W = preds.shape
+    ny, nx, eh, ew = slide_grid(H, W, crop, stride)
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.device == preds.device, "contiguous fp32 logits on preds' device"
+    n = logits.numel() // max(B * K * eh * ew, 1)
+    assert n > 0 and logits.numel() == n * B * K * eh * ew and tuple(logits.shape[-2:]) == (eh, ew), \
+        f"logits {tuple(logits.shape)} are not [n, {B}, {K}, {eh}, {ew}]"
+    check(lib.s2f_slide_accumulate(_ptr(logits), _ptr(preds), B, K, H, W, *_pair(crop), *_pair(stride), int(w0), n, _stream()),
+          "s2f_slide_accumulate")
+    return preds
+
+
 # ------------------------------------------------------------------------------------------------ training augmentation, test-time views
 AUG_CANDIDATES = 11                  # include/s2f.h S2F_AUG_CANDIDATES
 AUG_MAX_CROP = 4096                  # include/s2f.h S2F_AUG_MAX_CROP

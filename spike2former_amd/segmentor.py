@@ -3,7 +3,8 @@
 `postprocess_result` (mmseg/models/segmentors/base.py:127-200) -- and `ResetModelHook`
 (mmseg/engine/hooks/resetmodel_hook.py:9-37).  The post-processing arithmetic (bilinear resizes, softmax / sigmoid, the class
 einsum, window averaging, argmax) is plain tensor glue around the kernels and is pinned against the reference's own files
-by tests/golden/predict_a13.npz (oracle/gen_golden_a13.py).  The runner is out of scope."""
+by tests/golden/predict_a13.npz (oracle/gen_golden_a13.py); on fp32 CUDA tensors the resizes, the arg-max and the window averaging
+of `slide_inference` (csrc/slide.hip) run on the package's kernels.  The runner is out of scope."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -12,6 +13,14 @@ from . import ops
 from .data_preprocessor import PixelData, SegDataSample
 from .neuron import reset_net
 from .registry import HOOKS, MODELS, ConfigDict
+
+
+def _axis_covered(size, extent, stride, count):
+    """whether the `count` windows of one axis of ops.slide_grid (window i starts at min(i * stride, size - extent)) leave no
+    coordinate uncovered: neighbours start at most one extent apart"""
+    if count == 1:
+        return True
+    return (count < 3 or stride <= extent) and (size - extent) - (count - 2) * stride <= extent
 
 
 @MODELS.register_module()
@@ -44,25 +53,69 @@ class EncoderDecoder(nn.Module):
     def whole_inference(self, inputs, batch_img_metas):
         return self.encode_decode(inputs, batch_img_metas)
 
-    def slide_inference(self, inputs, batch_img_metas):
-        """Overlapping windows of test_cfg.crop_size at test_cfg.stride, logits averaged by coverage (:246-296)."""
-        h_stride, w_stride = self.test_cfg["stride"]
-        h_crop, w_crop = self.test_cfg["crop_size"]
+    def slide_inference(self, inputs, batch_img_metas, route=None):
+        """Overlapping windows of test_cfg.crop_size at test_cfg.stride, logits averaged by coverage (:246-296).
+
+        Two routes give the same bits.  fp32 CUDA inputs whose `encode_decode` returns fp32 CUDA logits stay on the package's
+        kernels: every group of windows is merged by ONE ops.slide_accumulate launch (no padded temporary, no count map, no final
+        division pass).  Everything else -- CPU tensors, other dtypes, or `route="torch"` (the measurement baseline of
+        tools/slide_probe.py) -- runs the reference's loop: F.pad, preds +=, count_mat += 1, preds / count_mat.
+
+        test_cfg['window_batch'] = g (an addition; absent: the reference's protocol, one window per `encode_decode` call at batch
+        B, the membranes carried from window to window): the windows run g at a time as one window-major batch [g B, 3, eh, ew]
+        (the last group may be smaller), with the membranes reset before every group -- each window is then the stateless
+        inference of the training path (the stated deviation of SegTTAModel's reset per view).
+
+        The reference asserts after its loop that no pixel is left uncovered; coverage depends on the grid alone, so it is checked
+        here before any window runs (the same AssertionError)."""
+        assert route in (None, "torch"), f"route {route!r}: None or 'torch'"
+        stride, crop = tuple(self.test_cfg["stride"]), tuple(self.test_cfg["crop_size"])
+        (h_stride, w_stride), (h_crop, w_crop) = stride, crop
         batch_size, _, h_img, w_img = inputs.size()
-        h_grids = max(h_img - h_crop + h_stride - 1, 0) // h_stride + 1
-        w_grids = max(w_img - w_crop + w_stride - 1, 0) // w_stride + 1
-        preds = inputs.new_zeros((batch_size, self.out_channels, h_img, w_img))
-        count_mat = inputs.new_zeros((batch_size, 1, h_img, w_img))
+        h_grids, w_grids, eh, ew = ops.slide_grid(h_img, w_img, crop, stride)
+        assert _axis_covered(h_img, eh, h_stride, h_grids) and _axis_covered(w_img, ew, w_stride, w_grids)
+        group = self.test_cfg.get("window_batch")
+        if group is not None and (int(group) != group or group < 1):
+            raise ValueError(f"test_cfg['window_batch'] = {group!r}: an integer >= 1")
+        boxes = []
         for h_idx in range(h_grids):
             for w_idx in range(w_grids):
                 y1, x1 = h_idx * h_stride, w_idx * w_stride
                 y2, x2 = min(y1 + h_crop, h_img), min(x1 + w_crop, w_img)
-                y1, x1 = max(y2 - h_crop, 0), max(x2 - w_crop, 0)
+                boxes.append((max(y2 - h_crop, 0), y2, max(x2 - w_crop, 0), x2))
+        ours = route is None and inputs.is_cuda and inputs.dtype == torch.float32
+        preds = count_mat = None
+        step = 1 if group is None else int(group)
+        whole = inputs.contiguous() if ours and group is not None else inputs          # what ops.slide_windows cuts from
+        for w0 in range(0, len(boxes), step):
+            n = min(step, len(boxes) - w0)
+            if group is None:
+                y1, y2, x1, x2 = boxes[w0]
                 crop_img = inputs[:, :, y1:y2, x1:x2]
-                batch_img_metas[0]["img_shape"] = crop_img.shape[2:]          # as the reference: only the first meta
-                crop_seg_logit = self.encode_decode(crop_img, batch_img_metas)
-                preds += F.pad(crop_seg_logit, (int(x1), int(preds.shape[3] - x2), int(y1), int(preds.shape[2] - y2)))
+            else:
+                reset_net(self)
+                if ours:
+                    crop_img = ops.slide_windows(whole, crop, stride, w0, n).view(n * batch_size, -1, eh, ew)
+                else:
+                    crop_img = torch.cat([inputs[:, :, y1:y2, x1:x2] for y1, y2, x1, x2 in boxes[w0:w0 + n]])
+            batch_img_metas[0]["img_shape"] = crop_img.shape[2:]          # as the reference: only the first meta
+            crop_seg_logit = self.encode_decode(crop_img, batch_img_metas)
+            if preds is None:
+                ours = ours and crop_seg_logit.is_cuda and crop_seg_logit.dtype == torch.float32
+                shape = (batch_size, self.out_channels, h_img, w_img)
+                if ours:
+                    preds = inputs.new_empty(shape)          # (every pixel is written: the grid covers the picture)
+                else:
+                    preds, count_mat = inputs.new_zeros(shape), inputs.new_zeros((batch_size, 1, h_img, w_img))
+            if ours:
+                ops.slide_accumulate(preds, crop_seg_logit.contiguous(), crop, stride, w0)
+                continue
+            for k, (y1, y2, x1, x2) in enumerate(boxes[w0:w0 + n]):
+                preds += F.pad(crop_seg_logit[k * batch_size:(k + 1) * batch_size],
+                               (int(x1), int(preds.shape[3] - x2), int(y1), int(preds.shape[2] - y2)))
                 count_mat[:, :, y1:y2, x1:x2] += 1
+        if ours:
+            return preds
         assert (count_mat == 0).sum() == 0
         return preds / count_mat
 
