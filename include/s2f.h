@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 46
+#define S2F_ABI_VERSION 47
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -919,6 +919,19 @@ int s2f_dcnv3_bwd(const float* input, const float* offset, const float* mask, co
                   float* grad_input, float* grad_offset, float* grad_mask, int N, int H, int W, int G, int Cg, int Kh,
                   int Kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale,
                   void* stream);
+/* The same core on CHANNEL-MAJOR maps: input / grad_input [N, G*Cg, H*W], output / grad_output [N, G*Cg, Ho*Wo]; offset, mask and
+ * their gradients keep the layouts above.  One workgroup owns an (n, group) slice -- Cg contiguous planes, staged in LDS -- in the
+ * forward as in the backward, so only maps whose slice fits one workgroup's LDS are taken: s2f_dcnv3_cm_ok says which (1 / 0, no
+ * launch), and the two entry points return S2F_EINVAL, before any launch, for every other geometry (the caller transposes and uses
+ * the [N, H, W, C] entry points there).  Results are bit-identical to those entry points on the transposed maps. */
+int s2f_dcnv3_cm_ok(int N, int H, int W, int G, int Cg, int Kh, int Kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                    int dil_w);
+int s2f_dcnv3_fwd_cm(const float* input, const float* offset, const float* mask, float* output, int N, int H, int W, int G, int Cg,
+                     int Kh, int Kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale,
+                     void* stream);
+int s2f_dcnv3_bwd_cm(const float* input, const float* offset, const float* mask, const float* grad_output, float* grad_input,
+                     float* grad_offset, float* grad_mask, int N, int H, int W, int G, int Cg, int Kh, int Kw, int stride_h,
+                     int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale, void* stream);
 
 /* ---- f2: one training iteration's parameter update (csrc/optim.hip, round 5) -------------------------------------------
  * Replaces mmengine OptimWrapper.update_params for the Spike2Former configs

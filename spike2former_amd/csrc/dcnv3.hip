@@ -268,6 +268,47 @@ __device__ __forceinline__ void grouped_loads(int n, Load load, Use use) {
   }
 }
 
+// Three such streams with the loads of ALL of them issued before the first use: one global round trip where three grouped_loads in
+// a row are three (a workgroup that owns a CU has nothing else to run while it waits).  A stream of n = 0 elements is skipped.
+// load(e, j) / use(e, j, v): element e = threadIdx.x + j * blockDim.x; the row index j is uniform over the workgroup.
+template <int U1, int U2, int U3, typename L1, typename S1, typename L2, typename S2, typename L3, typename S3>
+__device__ __forceinline__ void grouped_loads3(int n1, L1 load1, S1 use1, int n2, L2 load2, S2 use2, int n3, L3 load3, S3 use3) {
+  const int bd = (int)blockDim.x;
+  for (int r = 0;; ++r) {
+    const int a = threadIdx.x + r * U1 * bd, b = threadIdx.x + r * U2 * bd, c = threadIdx.x + r * U3 * bd;
+    const bool ga = a < n1, gb = b < n2, gc = c < n3;
+    if (!(ga || gb || gc)) break;
+    float v1[U1], v2[U2], v3[U3];
+    if (ga) {
+#pragma unroll
+      for (int u = 0; u < U1; ++u) v1[u] = load1(min(a + u * bd, n1 - 1), r * U1 + u);
+    }
+    if (gb) {
+#pragma unroll
+      for (int u = 0; u < U2; ++u) v2[u] = load2(min(b + u * bd, n2 - 1), r * U2 + u);
+    }
+    if (gc) {
+#pragma unroll
+      for (int u = 0; u < U3; ++u) v3[u] = load3(min(c + u * bd, n3 - 1), r * U3 + u);
+    }
+    if (ga) {
+#pragma unroll
+      for (int u = 0; u < U1; ++u)
+        if (a + u * bd < n1) use1(a + u * bd, r * U1 + u, v1[u]);
+    }
+    if (gb) {
+#pragma unroll
+      for (int u = 0; u < U2; ++u)
+        if (b + u * bd < n2) use2(b + u * bd, r * U2 + u, v2[u]);
+    }
+    if (gc) {
+#pragma unroll
+      for (int u = 0; u < U3; ++u)
+        if (c + u * bd < n3) use3(c + u * bd, r * U3 + u, v3[u]);
+    }
+  }
+}
+
 // BANDED (round 4): the (n, group) slice of a larger map -- 64 x 32 at C3, 50 x 84 at C5 -- does not fit: `nb` workgroups share it,
 // each owning the accumulators of a BAND of input rows [y_lo, y_hi).  Every workgroup walks ALL output pixels of the slice and
 // scatters the corners that land in its band; grad_offset / grad_mask of a pixel are formed by ONE of them (the band its output
@@ -448,6 +489,292 @@ __global__ __launch_bounds__(1024) void dcn_bwd_lds_kernel(const float* __restri
   }
 }
 
+// ---- CHANNEL-MAJOR maps: input / output / grad_output / grad_input as [N, C, H*W] (offset and mask keep their layout) ----------
+// The pixel decoder's stream is channel-major; on the [N, H, W, C] entry points every call is wrapped in a transposition in and one
+// out (forward and backward: four 8 MB passes per layer at C2).  Here a workgroup owns one (n, group) slice, as dcn_bwd_lds_kernel
+// does: the slice's Cg planes are Cg CONTIGUOUS rows of H*W floats in this layout, staged into LDS pixel-major ([pixel][channel], so
+// that a bilinear corner is still one or two 16-byte reads); every plane is stored with the lanes along the pixels.  The arithmetic
+// of a (pixel, group) is that of the NHWC kernels, expression for expression: only the addresses differ.
+
+// Workgroups are dealt round-robin over the 8 XCDs, each with an L2 of its own, and the groups of a pixel lie side by side in offset /
+// mask (72 and 36 bytes each at 3x3): with slice = blockIdx the 32 groups of an image are spread over all eight L2s and every one of
+// them fetches nearly every 128-byte line of both maps.  Workgroups that share an XCD take consecutive slices instead -- at C2
+// (8 images x 32 groups) one image per XCD, whose L2 then reads each line once.  Placement only: any mapping computes the same bits.
+__device__ __forceinline__ int cm_slice_of_block() {
+  const int nwg = (int)gridDim.x, b = (int)blockIdx.x;
+  return (nwg % 8 == 0) ? (b % 8) * (nwg / 8) + b / 8 : b;
+}
+
+constexpr int kFwdCmThreads = 1024;          // = output pixels whose offsets / mask are staged in LDS at a time
+
+// Forward.  K3C8: the 3x3 / Cg = 8 geometry unrolled, as dcn_fwd_k3c8_kernel; otherwise dcn_fwd_kernel<1>'s loops.  `RS` = floats
+// per staged pixel row: Cg, or Cg + 4 when Cg % 8 == 0 -- with 8-float rows the 16 lanes that one ds_read_b128 cycle serves
+// (neighbouring pixels) would share 8 of the 16 slots of the bank row (2-way); 12-float rows put them on 16 different slots.
+template <bool K3C8>
+__global__ __launch_bounds__(1024) void dcn_fwd_cm_kernel(const float* __restrict__ in, const float* __restrict__ off,
+                                                          const float* __restrict__ msk, float* __restrict__ out, Geom g, int RS) {
+  typedef __attribute__((ext_vector_type(4))) float v4;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int ng = cm_slice_of_block();
+  const int n = ng / g.G, gi = ng % g.G;
+  // (K3C8: compile-time sizes -- the index arithmetic of the 35 staging loads per thread is then shifts and multiplications; with
+  // run-time divisors it was more VALU work than the nine taps)
+  const int Cg = K3C8 ? 8 : g.Cg, P = K3C8 ? 9 : g.Kh * g.Kw, C = g.G * Cg;
+  const int npix_in = g.H * g.W, npix_out = g.Ho * g.Wo;
+  const int chunk = blockDim.x;
+  float* s_in = reinterpret_cast<float*>(smem_raw);      // [H*W][RS]
+  float* s_off = s_in + (size_t)npix_in * RS;            // [chunk][P*2]
+  float* s_msk = s_off + (size_t)chunk * P * 2;          // [chunk][P]
+  const float* inb = in + ((int64_t)n * C + gi * Cg) * npix_in;          // Cg contiguous planes
+  float* outb = out + ((int64_t)n * C + gi * Cg) * npix_out;
+  const int in_rows = Cg * ((npix_in + chunk - 1) / chunk);          // staging rows of `chunk` pixels: row j = plane j % Cg, block j / Cg
+  for (int p0 = 0; p0 < npix_out; p0 += chunk) {
+    const int pc = min(chunk, npix_out - p0);
+    // the input slice (first chunk only), the offsets and the mask values in ONE round trip: at 32 x 32 / 3x3 / Cg = 8 that is
+    // 8 + 18 + 9 loads per thread, all in flight together
+    grouped_loads3<8, 18, 9>(
+        p0 == 0 ? in_rows * chunk : 0,
+        [&](int, int j) { return inb[(int64_t)(j % Cg) * npix_in + min((int)threadIdx.x + (j / Cg) * chunk, npix_in - 1)]; },
+        [&](int, int j, float v) {
+          const int pi = (int)threadIdx.x + (j / Cg) * chunk;
+          if (pi < npix_in) s_in[pi * RS + j % Cg] = v;
+        },
+        pc * P * 2, [&](int e, int) { return off[(((int64_t)n * npix_out + p0 + e / (P * 2)) * g.G + gi) * P * 2 + e % (P * 2)]; },
+        [&](int e, int, float v) { s_off[e] = v; },
+        pc * P, [&](int e, int) { return msk[(((int64_t)n * npix_out + p0 + e / P) * g.G + gi) * P + e % P]; },
+        [&](int e, int, float v) { s_msk[e] = v; });
+    __syncthreads();
+    const int pl = threadIdx.x;
+    if (pl < pc) {
+      const int p = p0 + pl;
+      const int ho = p / g.Wo, wo = p % g.Wo;
+      if (K3C8) {
+        const float* so = s_off + pl * 18;
+        const float* sm = s_msk + pl * 9;
+        v4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        // one tap at a time: 16 wavefronts share the CU's registers (128 per lane), and an LDS corner costs no global round trip --
+        // unrolled, the scheduler hoists the 72 corner vectors of a pixel ahead of the arithmetic and spills 419 registers
+#pragma unroll 1
+        for (int k = 0; k < 9; ++k) {
+          const Tap t = make_tap(g, ho, wo, k / 3, k % 3, so[2 * k], so[2 * k + 1]);
+          const float m = sm[k];
+          const float wgt[4] = {(1.f - t.ly) * (1.f - t.lx) * m, (1.f - t.ly) * t.lx * m, t.ly * (1.f - t.lx) * m, t.ly * t.lx * m};
+          const bool b[4] = {t.vy0 && t.vx0, t.vy0 && t.vx1, t.vy1 && t.vx0, t.vy1 && t.vx1};
+          const int o00 = (t.y0 * g.W + t.x0) * RS;
+          const int o[4] = {o00, o00 + RS, o00 + g.W * RS, o00 + g.W * RS + RS};
+          v4 c0[4], c1[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float* ps = s_in + (b[q] ? o[q] : 0);
+            const v4 z = {0.f, 0.f, 0.f, 0.f};
+            c0[q] = b[q] ? *reinterpret_cast<const v4*>(ps) : z;
+            c1[q] = b[q] ? *reinterpret_cast<const v4*>(ps + 4) : z;
+          }
+          // dcn_fwd_k3c8_kernel's operation order: ((v00*w00 + v01*w01) + v10*w10) + v11*w11, tap after tap
+          acc0 += ((c0[0] * wgt[0] + c0[1] * wgt[1]) + c0[2] * wgt[2]) + c0[3] * wgt[3];
+          acc1 += ((c1[0] * wgt[0] + c1[1] * wgt[1]) + c1[2] * wgt[2]) + c1[3] * wgt[3];
+        }
+        outb[p] = acc0.x;                              outb[(int64_t)npix_out + p] = acc0.y;
+        outb[(int64_t)2 * npix_out + p] = acc0.z;      outb[(int64_t)3 * npix_out + p] = acc0.w;
+        outb[(int64_t)4 * npix_out + p] = acc1.x;      outb[(int64_t)5 * npix_out + p] = acc1.y;
+        outb[(int64_t)6 * npix_out + p] = acc1.z;      outb[(int64_t)7 * npix_out + p] = acc1.w;
+      } else {
+        for (int c = 0; c < Cg; ++c) {
+          float acc = 0.f;
+          for (int k = 0; k < P; ++k) {
+            const Tap t = make_tap(g, ho, wo, k / g.Kh, k % g.Kh, s_off[(pl * P + k) * 2], s_off[(pl * P + k) * 2 + 1]);
+            const float m = s_msk[pl * P + k];
+            const float w00 = (1.f - t.ly) * (1.f - t.lx), w01 = (1.f - t.ly) * t.lx, w10 = t.ly * (1.f - t.lx),
+                        w11 = t.ly * t.lx;
+            const int o00 = (t.y0 * g.W + t.x0) * RS + c;
+            const float v00 = (t.vy0 && t.vx0) ? s_in[o00] : 0.f, v01 = (t.vy0 && t.vx1) ? s_in[o00 + RS] : 0.f,
+                        v10 = (t.vy1 && t.vx0) ? s_in[o00 + g.W * RS] : 0.f, v11 = (t.vy1 && t.vx1) ? s_in[o00 + g.W * RS + RS] : 0.f;
+            const float s = v00 * (w00 * m) + v01 * (w01 * m) + v10 * (w10 * m) + v11 * (w11 * m);
+            acc = acc + s;
+          }
+          outb[(int64_t)c * npix_out + p] = acc;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Backward: dcn_bwd_lds_kernel<false> (one workgroup per slice, the same LDS images, the same fixed-point accumulation and per-slice
+// scale rule, the same items in the same order) with the planes of input / grad_output read, and those of grad_input written, as
+// contiguous rows.  Integer adds: bit-identical to the NHWC kernel on the transposed maps.
+constexpr int kBwdCmThreads = 1024;
+constexpr int kPipeO = 5, kPipeM = 3, kPipeG = 2;          // registers per thread that hold the next chunk (PIPE)
+inline bool cm_bwd_pipe(int Cg, int P) {
+  return kChunk * P * 2 <= kPipeO * kBwdCmThreads && kChunk * P <= kPipeM * kBwdCmThreads && kChunk * Cg <= kPipeG * kBwdCmThreads;
+}
+
+template <bool PIPE, bool K3C8>
+__global__ __launch_bounds__(1024) void dcn_bwd_lds_cm_kernel(const float* __restrict__ in, const float* __restrict__ off,
+                                                             const float* __restrict__ msk, const float* __restrict__ gout,
+                                                             float* __restrict__ gin, float* __restrict__ goff,
+                                                             float* __restrict__ gmsk, Geom g, int acc_bits) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ float s_red[2][16];
+  const int ng = cm_slice_of_block();
+  const int n = ng / g.G, gi = ng % g.G;
+  // (K3C8: compile-time sizes, so that the index arithmetic of the staging loads and of the items is shifts and multiplications)
+  const int Cg = K3C8 ? 8 : g.Cg, P = K3C8 ? 9 : g.Kh * g.Kw, C = g.G * Cg, Kh = K3C8 ? 3 : g.Kh;
+  const int npix_in = g.H * g.W, npix_out = g.Ho * g.Wo;
+  const int CA = Cg + 1;          // (padded accumulator rows, see dcn_bwd_lds_kernel)
+  unsigned long long* s_acc = reinterpret_cast<unsigned long long*>(smem_raw);      // [H*W][Cg + 1] fixed-point grad_input
+  float* s_in = reinterpret_cast<float*>(s_acc + (size_t)npix_in * CA);             // [H*W][Cg]
+  float* s_off = s_in + npix_in * Cg;       // [kChunk][P*2]
+  float* s_msk = s_off + kChunk * P * 2;    // [kChunk][P]
+  float* s_go = s_msk + kChunk * P;         // [kChunk][Cg]
+  const float* inb = in + ((int64_t)n * C + gi * Cg) * npix_in;
+  const float* gob = gout + ((int64_t)n * C + gi * Cg) * npix_out;
+  // scale of this slice: max|grad_output| * max|mask| bounds every contribution.  (The input slice and the two scans: one round trip.)
+  float mg = 0.f, mm = 0.f;
+  const int slots = blockDim.x;
+  const int in_rows = Cg * ((npix_in + slots - 1) / slots);
+  grouped_loads3<8, 8, 9>(
+      in_rows * slots,          // staging rows of `slots` pixels: row j = plane j % Cg, block j / Cg (no division by a run-time size)
+      [&](int, int j) { return inb[(int64_t)(j % Cg) * npix_in + min((int)threadIdx.x + (j / Cg) * slots, npix_in - 1)]; },
+      [&](int, int j, float v) {
+        const int p = (int)threadIdx.x + (j / Cg) * slots, c = j % Cg;
+        if (p < npix_in) {
+          s_in[p * Cg + c] = v;
+          s_acc[p * CA + c] = 0ull;
+        }
+      },
+      npix_out * Cg, [&](int e, int) { return gob[e]; }, [&](int, int, float v) { mg = fmaxf(mg, fabsf(v)); },
+      npix_out * P, [&](int e, int) { return msk[(((int64_t)n * npix_out + e / P) * g.G + gi) * P + e % P]; },
+      [&](int, int, float v) { mm = fmaxf(mm, fabsf(v)); });
+  for (int o = 32; o > 0; o >>= 1) {
+    mg = fmaxf(mg, __shfl_xor(mg, o, 64));
+    mm = fmaxf(mm, __shfl_xor(mm, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_red[0][threadIdx.x >> 6] = mg;
+    s_red[1][threadIdx.x >> 6] = mm;
+  }
+  __syncthreads();
+  mg = 0.f, mm = 0.f;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
+    mg = fmaxf(mg, s_red[0][w]);
+    mm = fmaxf(mm, s_red[1][w]);
+  }
+  int ex = 0;
+  const float bound = mg * mm;
+  if (bound > 0.f) frexpf(fminf(bound, 3.0e38f), &ex);          // bound < 2^ex
+  const int shift = max(-126, min(126, acc_bits - ex));
+  const float scale = ldexpf(1.f, shift);
+  const double inv_scale = ldexp(1.0, -shift);
+
+  // PIPE (P <= 10, Cg <= 8: a chunk's offsets / mask / grad_output are at most kPipeO / kPipeM / kPipeG values per thread of the
+  // 1 024): the NEXT chunk is fetched into registers before this chunk's items are worked on and written to the staging arrays after
+  // them, so a chunk's global round trip hides behind the previous chunk's LDS atomics.  Otherwise: one round trip per chunk.
+  float r_off[kPipeO], r_msk[kPipeM], r_go[kPipeG];
+  auto off_at = [&](int p0, int e) { return off[(((int64_t)n * npix_out + p0 + e / (P * 2)) * g.G + gi) * P * 2 + e % (P * 2)]; };
+  auto msk_at = [&](int p0, int e) { return msk[(((int64_t)n * npix_out + p0 + e / P) * g.G + gi) * P + e % P]; };
+  // (a full chunk divides by the constant kChunk)
+  auto cdiv = [&](int e, int pc) { return pc == kChunk ? e / kChunk : e / pc; };
+  auto cmod = [&](int e, int pc) { return pc == kChunk ? e % kChunk : e % pc; };
+  auto go_at = [&](int p0, int pc, int e) { return gob[(int64_t)cdiv(e, pc) * npix_out + p0 + cmod(e, pc)]; };
+  auto fetch = [&](int p0) __attribute__((always_inline)) {
+    const int pc = min(kChunk, npix_out - p0);
+#pragma unroll
+    for (int u = 0; u < kPipeO; ++u) r_off[u] = off_at(p0, min((int)threadIdx.x + u * slots, pc * P * 2 - 1));
+#pragma unroll
+    for (int u = 0; u < kPipeM; ++u) r_msk[u] = msk_at(p0, min((int)threadIdx.x + u * slots, pc * P - 1));
+#pragma unroll
+    for (int u = 0; u < kPipeG; ++u) r_go[u] = go_at(p0, pc, min((int)threadIdx.x + u * slots, pc * Cg - 1));
+  };
+  if (PIPE) fetch(0);
+  for (int p0 = 0; p0 < npix_out; p0 += kChunk) {
+    const int pc = min(kChunk, npix_out - p0);
+    if (PIPE) {
+#pragma unroll
+      for (int u = 0; u < kPipeO; ++u) {
+        const int e = threadIdx.x + u * slots;
+        if (e < pc * P * 2) s_off[e] = r_off[u];
+      }
+#pragma unroll
+      for (int u = 0; u < kPipeM; ++u) {
+        const int e = threadIdx.x + u * slots;
+        if (e < pc * P) s_msk[e] = r_msk[u];
+      }
+#pragma unroll
+      for (int u = 0; u < kPipeG; ++u) {
+        const int e = threadIdx.x + u * slots;
+        if (e < pc * Cg) s_go[cmod(e, pc) * Cg + cdiv(e, pc)] = r_go[u];
+      }
+    } else {
+      grouped_loads3<5, 3, 2>(
+          pc * P * 2, [&](int e, int) { return off_at(p0, e); }, [&](int e, int, float v) { s_off[e] = v; },
+          pc * P, [&](int e, int) { return msk_at(p0, e); }, [&](int e, int, float v) { s_msk[e] = v; },
+          pc * Cg, [&](int e, int) { return go_at(p0, pc, e); }, [&](int e, int, float v) { s_go[cmod(e, pc) * Cg + cdiv(e, pc)] = v; });
+    }
+    __syncthreads();
+    if (PIPE && p0 + kChunk < npix_out) fetch(p0 + kChunk);
+    const int items = pc * P;
+    for (int it0 = 0; it0 < items; it0 += slots) {
+      const int it = it0 + threadIdx.x;
+      const bool live = it < items;
+      const int k = live ? cdiv(it, pc) : 0, pl = live ? cmod(it, pc) : 0;
+      const int pix = p0 + pl;
+      const int ho = pix / g.Wo, wo = pix % g.Wo;
+      const float offx = s_off[(pl * P + k) * 2], offy = s_off[(pl * P + k) * 2 + 1];
+      const float m = s_msk[pl * P + k];
+      const Tap t = make_tap(g, ho, wo, k / Kh, k % Kh, offx, offy);
+      const float w00 = (1.f - t.ly) * (1.f - t.lx), w01 = (1.f - t.ly) * t.lx, w10 = t.ly * (1.f - t.lx),
+                  w11 = t.ly * t.lx;
+      const bool b00 = live && t.vy0 && t.vx0, b01 = live && t.vy0 && t.vx1, b10 = live && t.vy1 && t.vx0,
+                 b11 = live && t.vy1 && t.vx1;
+      const int o00 = (t.y0 * g.W + t.x0) * Cg;
+      const int o01 = o00 + Cg, o10 = o00 + g.W * Cg, o11 = o10 + Cg;
+      const int a00 = (t.y0 * g.W + t.x0) * CA;
+      float am = 0.f, ax = 0.f, ay = 0.f;
+      auto body = [&](int c, float gv, float a, float b, float cc, float d) __attribute__((always_inline)) {
+        am += gv * (a * w00 + b * w01 + cc * w10 + d * w11);
+        ax += gv * ((1.f - t.ly) * (b - a) + t.ly * (d - cc));
+        ay += gv * ((1.f - t.lx) * (cc - a) + t.lx * (d - b));
+        const float gm = gv * m * scale;
+        if (b00) atomicAdd(&s_acc[a00 + c], fix64(gm * w00));
+        if (b01) atomicAdd(&s_acc[a00 + CA + c], fix64(gm * w01));
+        if (b10) atomicAdd(&s_acc[a00 + g.W * CA + c], fix64(gm * w10));
+        if (b11) atomicAdd(&s_acc[a00 + g.W * CA + CA + c], fix64(gm * w11));
+      };
+      if ((Cg & 3) == 0 && ((npix_in * CA) & 1) == 0) {          // second test: s_in starts 16-byte aligned
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int c = 0; c < Cg; c += 4) {
+          const float4 gv = live ? *reinterpret_cast<const float4*>(&s_go[pl * Cg + c]) : z4;
+          const float4 a = b00 ? *reinterpret_cast<const float4*>(&s_in[o00 + c]) : z4;
+          const float4 b = b01 ? *reinterpret_cast<const float4*>(&s_in[o01 + c]) : z4;
+          const float4 cc = b10 ? *reinterpret_cast<const float4*>(&s_in[o10 + c]) : z4;
+          const float4 d = b11 ? *reinterpret_cast<const float4*>(&s_in[o11 + c]) : z4;
+          body(c, gv.x, a.x, b.x, cc.x, d.x);
+          body(c + 1, gv.y, a.y, b.y, cc.y, d.y);
+          body(c + 2, gv.z, a.z, b.z, cc.z, d.z);
+          body(c + 3, gv.w, a.w, b.w, cc.w, d.w);
+        }
+      } else {
+        for (int c = 0; c < Cg; ++c)
+          body(c, live ? s_go[pl * Cg + c] : 0.f, b00 ? s_in[o00 + c] : 0.f, b01 ? s_in[o01 + c] : 0.f,
+               b10 ? s_in[o10 + c] : 0.f, b11 ? s_in[o11 + c] : 0.f);
+      }
+      if (live) {
+        const int64_t ob = (((int64_t)n * npix_out + pix) * g.G + gi) * P + k;
+        gmsk[ob] = am;
+        goff[ob * 2] = ax * m * g.osc;
+        goff[ob * 2 + 1] = ay * m * g.osc;
+      }
+    }
+    __syncthreads();
+  }
+  float* ginb = gin + ((int64_t)n * C + gi * Cg) * npix_in;
+  for (int e = threadIdx.x; e < npix_in * Cg; e += blockDim.x) {
+    const int p = e % npix_in, c = e / npix_in;
+    ginb[e] = (float)((double)(long long)s_acc[p * CA + c] * inv_scale);
+  }
+}
+
 int make_geom(Geom& g, int N, int H, int W, int G, int Cg, int Kh, int Kw, int sh, int sw, int ph, int pw, int dh, int dw,
               float osc, const char* who) {
   S2F_REQUIRE(N > 0 && H > 0 && W > 0 && G > 0 && Cg > 0 && Kh > 0 && Kw > 0 && sh > 0 && sw > 0 && ph >= 0 &&
@@ -569,4 +896,112 @@ extern "C" int s2f_dcnv3_bwd(const float* input, const float* offset, const floa
     hipLaunchKernelGGL(dcn_bwd_kernel<1>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, input, offset, mask,
                        grad_output, grad_input, grad_offset, grad_mask, g);
   return s2f_check_launch("s2f_dcnv3_bwd");
+}
+
+// ---- channel-major entry points ---------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr size_t kCmMaxDynLds = 160 * 1024 - 256;
+
+inline size_t cm_bwd_lds(int H, int W, int Cg, int P) {
+  return (size_t)H * W * (8 * (Cg + 1) + 4 * Cg) + sizeof(float) * (size_t)kChunk * (P * 3 + Cg);
+}
+inline int cm_fwd_threads(const Geom& g) {
+  const int64_t npix_out = (int64_t)g.Ho * g.Wo;
+  return (int)(npix_out >= kFwdCmThreads ? kFwdCmThreads : (npix_out + 63) / 64 * 64);
+}
+inline size_t cm_fwd_lds(const Geom& g, int RS) {
+  return sizeof(float) * ((size_t)g.H * g.W * RS + (size_t)cm_fwd_threads(g) * g.Kh * g.Kw * 3);
+}
+// the staged row of the forward kernel: padded where that keeps the 16-byte corner reads conflict-free and still fits
+inline int cm_fwd_row(const Geom& g) {
+  return (g.Cg % 8 == 0 && cm_fwd_lds(g, g.Cg + 4) <= kCmMaxDynLds) ? g.Cg + 4 : g.Cg;
+}
+// one (n, group) slice per workgroup, forward AND backward (a caller takes one route for both)
+inline bool cm_fits(const Geom& g) {
+  return (int64_t)g.H * g.W <= (1 << 20) && (int64_t)g.Ho * g.Wo <= (1 << 20) && (int64_t)g.N * g.G < ((int64_t)1 << 31) &&
+         cm_bwd_lds(g.H, g.W, g.Cg, g.Kh * g.Kw) <= kCmMaxDynLds && cm_fwd_lds(g, g.Cg) <= kCmMaxDynLds;
+}
+
+}  // namespace
+
+extern "C" int s2f_dcnv3_cm_ok(int N, int H, int W, int G, int Cg, int Kh, int Kw, int stride_h, int stride_w, int pad_h, int pad_w,
+                               int dil_h, int dil_w) {
+  if (!(N > 0 && H > 0 && W > 0 && G > 0 && Cg > 0 && Kh > 0 && Kw > 0 && stride_h > 0 && stride_w > 0 && pad_h >= 0 && pad_w >= 0 &&
+        dil_h > 0 && dil_w > 0))
+    return 0;
+  if ((int64_t)H * W > (1 << 20) || (int64_t)Kh * Kw > 1024 || Cg > 1024) return 0;
+  Geom g{N, H, W, G, Cg, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, 0, 0, 1.f};
+  g.Ho = (H + 2 * pad_h - (dil_h * (Kh - 1) + 1)) / stride_h + 1;
+  g.Wo = (W + 2 * pad_w - (dil_w * (Kw - 1) + 1)) / stride_w + 1;
+  return (g.Ho > 0 && g.Wo > 0 && cm_fits(g)) ? 1 : 0;
+}
+
+extern "C" int s2f_dcnv3_fwd_cm(const float* input, const float* offset, const float* mask, float* output, int N, int H, int W,
+                                int G, int Cg, int Kh, int Kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                int dil_w, float offset_scale, void* stream) {
+  S2F_REQUIRE(input && offset && mask && output, S2F_EINVAL, "s2f_dcnv3_fwd_cm: null pointer");
+  Geom g;
+  int rc = make_geom(g, N, H, W, G, Cg, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, offset_scale, "s2f_dcnv3_fwd_cm");
+  if (rc != S2F_OK) return rc;
+  S2F_REQUIRE(s2f_dcnv3_cm_ok(N, H, W, G, Cg, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w), S2F_EINVAL,
+              "s2f_dcnv3_fwd_cm: a %d x %d x %d slice does not fit one workgroup's LDS (use the [N, H, W, C] entry point)", H, W, Cg);
+  const int RS = cm_fwd_row(g), threads = cm_fwd_threads(g);
+  const size_t lds = cm_fwd_lds(g, RS);
+  const bool k3c8 = Cg == 8 && Kh == 3 && Kw == 3;
+  static bool raised[2] = {false, false};
+  if (!raised[k3c8]) {
+    hipError_t e = hipFuncSetAttribute(k3c8 ? reinterpret_cast<const void*>(dcn_fwd_cm_kernel<true>)
+                                            : reinterpret_cast<const void*>(dcn_fwd_cm_kernel<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCmMaxDynLds);
+    S2F_REQUIRE(e == hipSuccess, S2F_ELAUNCH, "s2f_dcnv3_fwd_cm: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
+    raised[k3c8] = true;
+  }
+  if (k3c8)
+    hipLaunchKernelGGL(dcn_fwd_cm_kernel<true>, dim3(N * G), dim3(threads), lds, (hipStream_t)stream, input, offset, mask, output, g,
+                       RS);
+  else
+    hipLaunchKernelGGL(dcn_fwd_cm_kernel<false>, dim3(N * G), dim3(threads), lds, (hipStream_t)stream, input, offset, mask, output,
+                       g, RS);
+  return s2f_check_launch("s2f_dcnv3_fwd_cm");
+}
+
+extern "C" int s2f_dcnv3_bwd_cm(const float* input, const float* offset, const float* mask, const float* grad_output,
+                                float* grad_input, float* grad_offset, float* grad_mask, int N, int H, int W, int G, int Cg, int Kh,
+                                int Kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale,
+                                void* stream) {
+  S2F_REQUIRE(input && offset && mask && grad_output && grad_input && grad_offset && grad_mask, S2F_EINVAL,
+              "s2f_dcnv3_bwd_cm: null pointer");
+  Geom g;
+  int rc = make_geom(g, N, H, W, G, Cg, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, offset_scale, "s2f_dcnv3_bwd_cm");
+  if (rc != S2F_OK) return rc;
+  S2F_REQUIRE(s2f_dcnv3_cm_ok(N, H, W, G, Cg, Kh, Kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w), S2F_EINVAL,
+              "s2f_dcnv3_bwd_cm: a %d x %d x %d slice does not fit one workgroup's LDS (use the [N, H, W, C] entry point)", H, W, Cg);
+  // the accumulator rule of s2f_dcnv3_bwd: 4*K*Ho*Wo contributions below 2^acc_bits fit 62 bits, one contribution fix64's range
+  int count_bits = 0;
+  while (((int64_t)1 << count_bits) < (int64_t)4 * Kh * Kw * g.Ho * g.Wo) ++count_bits;
+  if (count_bits < 12) count_bits = 12;
+  // the kernel's forms: 0 one round trip per chunk, 1 register-prefetched chunks, 2 the same with the 3x3 / Cg = 8 sizes compiled in
+  const int form = !cm_bwd_pipe(Cg, Kh * Kw) ? 0 : (Cg == 8 && Kh == 3 && Kw == 3) ? 2 : 1;
+  const void* fn = form == 0 ? reinterpret_cast<const void*>(dcn_bwd_lds_cm_kernel<false, false>)
+                   : form == 1 ? reinterpret_cast<const void*>(dcn_bwd_lds_cm_kernel<true, false>)
+                               : reinterpret_cast<const void*>(dcn_bwd_lds_cm_kernel<true, true>);
+  static bool raised[3] = {false, false, false};
+  if (!raised[form]) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCmMaxDynLds);
+    S2F_REQUIRE(e == hipSuccess, S2F_ELAUNCH, "s2f_dcnv3_bwd_cm: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
+    raised[form] = true;
+  }
+  const size_t lds = cm_bwd_lds(H, W, Cg, Kh * Kw);
+  const dim3 grid(N * G), block(kBwdCmThreads);
+  if (form == 0)
+    hipLaunchKernelGGL((dcn_bwd_lds_cm_kernel<false, false>), grid, block, lds, (hipStream_t)stream, input, offset, mask, grad_output,
+                       grad_input, grad_offset, grad_mask, g, 62 - count_bits);
+  else if (form == 1)
+    hipLaunchKernelGGL((dcn_bwd_lds_cm_kernel<true, false>), grid, block, lds, (hipStream_t)stream, input, offset, mask, grad_output,
+                       grad_input, grad_offset, grad_mask, g, 62 - count_bits);
+  else
+    hipLaunchKernelGGL((dcn_bwd_lds_cm_kernel<true, true>), grid, block, lds, (hipStream_t)stream, input, offset, mask, grad_output,
+                       grad_input, grad_offset, grad_mask, g, 62 - count_bits);
+  return s2f_check_launch("s2f_dcnv3_bwd_cm");
 }

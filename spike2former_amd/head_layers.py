@@ -125,14 +125,20 @@ class DCNv3_pytorch(nn.Module):
             nn.init.constant_(m.bias, 0.0)
 
     def forward_nchw(self, inp, scale=None, residual=None, next_lif=None):
-        """Channel-major form: inp, residual, result [T,N,C,H,W].  Only the sampling core works on NHWC (its gather reads
-        the Cg channels of a group as one vector): one transposition in, one out, instead of the reference's permute pair
-        around every sub-module."""
+        """Channel-major form: inp, residual, result [T,N,C,H,W].  Where an (image, group) slice of the map fits one workgroup's
+        LDS the sampling core reads input_proj's output and writes output_proj's input as they are (ops.dcnv3_core_cm;
+        ops.cfg.DCN_CHANNEL_MAJOR).  On larger maps only the core works on NHWC (its gather reads the Cg channels of a group as
+        one vector): one transposition in, one out, instead of the reference's permute pair around every sub-module."""
         T, N, C, H, W = inp.shape
         through = [residual]
+        k = self.kernel_size
+        geo = (k, k, self.stride, self.stride, self.pad, self.pad, self.dilation, self.dilation, self.group, self.group_channels)
+        cm = bool(ops.cfg.DCN_CHANNEL_MAJOR and inp.is_cuda and ops.dcnv3_cm_ok(T * N, H, W, *geo))
 
         def sampled_input():
             x = self.input_proj.forward_nchw(inp)
+            if cm:
+                return x.reshape(T * N, C, H, W)
             return ops.transpose_last2(x.reshape(T * N, C, H * W)).view(T * N, H, W, C)   # NCHW -> [T*N, H, W, C]
 
         def offset_and_mask():
@@ -153,10 +159,11 @@ class DCNv3_pytorch(nn.Module):
         # more costs more than it hides: two 2-kernel chains, 56.9 vs 54.4 ms/step -- a fork / join pair in the replayed
         # hipGraph is worth several short kernels.)
         x, (offset, mask) = ops.branches([sampled_input, offset_and_mask], inputs=(inp,))
-        k = self.kernel_size
-        y = ops.dcnv3_core(x, offset, mask, k, k, self.stride, self.stride, self.pad, self.pad,
-                           self.dilation, self.dilation, self.group, self.group_channels, self.offset_scale)
-        y = ops.transpose_last2(y.reshape(T * N, H * W, C)).view(T, N, C, H, W)
+        if cm:
+            y = ops.dcnv3_core_cm(x, offset, mask, *geo, self.offset_scale).view(T, N, C, H, W)
+        else:
+            y = ops.dcnv3_core(x, offset, mask, *geo, self.offset_scale)
+            y = ops.transpose_last2(y.reshape(T * N, H * W, C)).view(T, N, C, H, W)
         return self.output_proj.forward_nchw(y, scale=scale, residual=through[0], next_lif=next_lif)
 
     def forward(self, inp):

@@ -272,5 +272,44 @@ def dcnv3_core(x, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, offset_sc
     return _DCNv3.apply(x, offset, spikes_float(mask), kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, float(offset_scale))
 
 
+class _DCNv3CM(torch.autograd.Function):
+    """The same core on channel-major maps: x [N, C, H, W] -> [N, C, Ho, Wo]; offset / mask [N, Ho, Wo, .] as above."""
+
+    @staticmethod
+    def forward(ctx, x, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, offset_scale):
+        _need_cuda(x, offset, mask)
+        x, offset, mask = x.contiguous(), offset.contiguous(), mask.contiguous()
+        N, _, H, W = x.shape
+        Ho, Wo = offset.shape[1], offset.shape[2]
+        out = torch.empty(N, G * Cg, Ho, Wo, dtype=torch.float32, device=x.device)
+        geo = (N, H, W, G, Cg, kh, kw, sh, sw, ph, pw, dh, dw)
+        check(lib.s2f_dcnv3_fwd_cm(_ptr(x), _ptr(offset), _ptr(mask), _ptr(out), *geo, offset_scale, _stream()),
+              "s2f_dcnv3_fwd_cm")
+        ctx.save_for_backward(x, offset, mask)
+        ctx.geo, ctx.osc = geo, offset_scale
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        x, offset, mask = ctx.saved_tensors
+        go = go.contiguous()
+        gx = torch.empty_like(x)                      # s2f_dcnv3_bwd_cm overwrites all three gradients
+        goff, gm = torch.empty_like(offset), torch.empty_like(mask)
+        check(lib.s2f_dcnv3_bwd_cm(_ptr(x), _ptr(offset), _ptr(mask), _ptr(go), _ptr(gx), _ptr(goff), _ptr(gm), *ctx.geo,
+                                   ctx.osc, _stream()), "s2f_dcnv3_bwd_cm")
+        return (gx, goff, gm) + (None,) * 11
+
+
+def dcnv3_cm_ok(N, H, W, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg):
+    """An (image, group) slice of this geometry fits one workgroup's LDS: dcnv3_core_cm takes it (no launch)."""
+    return bool(lib.s2f_dcnv3_cm_ok(N, H, W, G, Cg, kh, kw, sh, sw, ph, pw, dh, dw))
+
+
+def dcnv3_core_cm(x, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, offset_scale):
+    """dcnv3_core on channel-major maps, x [N, C, H, W] -> [N, C, Ho, Wo], without the transposition pair around the NHWC core;
+    for geometries with dcnv3_cm_ok (any other is an error here: the caller keeps the transposing route for them)."""
+    return _DCNv3CM.apply(x, offset, spikes_float(mask), kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, float(offset_scale))
+
+
 
 __all__ = [n for n in dir() if not n.startswith('__')]

@@ -15,7 +15,7 @@ class Config:
     RUNTIME = ("KERNEL_EVENTS", "GRAD_SINKS", "WGRAD_STREAM", "BRANCH_STREAMS", "LONG_STREAMS")          # objects, not settings
     # A/B switches of changes whose comparison is still on record as open or fresh: part of what a captured graph depends on
     # (launch_snapshot) next to the settled list above, which tests/test_host_logic.py pins name by name
-    LAUNCH_FIELDS = ("DECODER_SIBLINGS",)
+    LAUNCH_FIELDS = ("DECODER_SIBLINGS", "DCN_CHANNEL_MAJOR")
 
     def __setattr__(self, name, value):
         if name not in self.FIELDS and name not in self.LAUNCH_FIELDS:
@@ -63,6 +63,10 @@ class Config:
         # DECODER_SIBLINGS: the q / k / v projection chains of the decoder's self-attention (conv1x1 -> BatchNorm -> neuron on the
         # 100-token maps) run as ONE grouped launch per stage, forward and backward, instead of three (S2F_DEC_SIBLINGS=0: one by one)
         self.DECODER_SIBLINGS = os.environ.get("S2F_DEC_SIBLINGS", "1") != "0"
+        # DCN_CHANNEL_MAJOR: the pixel decoder's DCNv3 sampling core reads and writes the channel-major stream itself where an
+        # (image, group) slice fits one workgroup's LDS (s2f_dcnv3_fwd_cm / _bwd_cm) instead of running on NHWC maps between two
+        # transpositions, forward and backward (S2F_DCN_CM=0: the transposing route everywhere)
+        self.DCN_CHANNEL_MAJOR = os.environ.get("S2F_DCN_CM", "1") != "0"
 
     def snapshot(self):
         """the settings a captured hipGraph depends on (scalars only)"""
