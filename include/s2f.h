@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 47
+#define S2F_ABI_VERSION 48
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -554,6 +554,13 @@ int s2f_resize_bwd_add(const float* gy, const float* add, float* gx, int64_t pla
  * K == 1 -> (sigmoid ? sigmoid(x) : x) > threshold, into label (int64) or label_f (float 0 / 1): exactly one of the two.
  * (EncoderDecoder.postprocess_result's arg-max / threshold, mmseg segmentors/base.py:190-198.) */
 int s2f_seg_argmax(const float* x, int64_t* label, float* label_f, int K, int64_t HW, int sigmoid, float threshold, void* stream);
+/* s2f_resize_fwd + s2f_seg_argmax in one launch, without the [K, H, W] planes between them (ABI 48): per pixel of the [H, W] output
+ * the K classes of x's window (plane_stride .. w and the align / flip flags as s2f_resize_fwd) are interpolated with s2f_resize_fwd's
+ * arithmetic and only the running best is kept.  K > 1 -> label = argmax over K (int64; the first maximum, NaN wins);
+ * K == 1 -> sigmoid(value) > threshold into label (int64) or label_f (float 0 / 1): exactly one of the two.  The bits of the two-pass
+ * route.  flags: S2F_RESIZE_ALIGN_CORNERS | S2F_RESIZE_FLIP_H / _V (S2F_RESIZE_SIGMOID is implied for K == 1 and not accepted). */
+int s2f_seg_label(const float* x, int64_t* label, float* label_f, int K, int64_t plane_stride, int row_stride, int row0, int col0,
+                  int h, int w, int H, int W, int flags, float threshold, void* stream);
 /* Test-time augmentation (mmseg segmentors/seg_tta.py:14-48) for one image and one view: the view's logits x [K] x (window, flags as
  * s2f_resize_fwd) are resized to the accumulator's [H, W] and acc [K, H, W] (first ? = : +=) softmax over K (max-subtracted, expf,
  * divided by the sum); K == 1: sigmoid, after a first sigmoid if flags has S2F_RESIZE_SIGMOID (the reference's one-class merge

@@ -15,6 +15,7 @@ from .neuron import LIFNode, Q_IFNode, Quant, reset_net, set_keep_membrane  # no
 from .pixel_decoder import DCNTransformerEncoderPixelDecoder  # noqa: F401
 from .registry import HOOKS, METRICS, MODELS, VISUALIZERS, ConfigDict, register_upstream  # noqa: F401
 from . import reparam  # noqa: F401
+from .graph import CapturePolicy, GraphedPredict  # noqa: F401
 from .segmentor import EncoderDecoder, ResetModelHook, headline_loss  # noqa: F401
 from .tta import SegTTAModel  # noqa: F401
 from .metrics import ConfusionMatrix, IoUMetric, evaluate  # noqa: F401

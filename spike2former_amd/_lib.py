@@ -68,6 +68,7 @@ SIGNATURES = {
     "s2f_resize_fwd": (_i, [_p, _p, _i64, _i64] + [_i] * 8 + [_p]),
     "s2f_resize_bwd_add": (_i, [_p, _p, _p, _i64] + [_i] * 5 + [_p]),
     "s2f_seg_argmax": (_i, [_p, _p, _p, _i, _i64, _i, _f, _p]),
+    "s2f_seg_label": (_i, [_p, _p, _p, _i, _i64] + [_i] * 8 + [_f, _p]),
     "s2f_tta_accumulate": (_i, [_p, _p, _i, _i64] + [_i] * 9 + [_p]),
     "s2f_tta_finish": (_i, [_p, _p, _p, _i, _i64, _i, _f, _p]),
     "s2f_slide_windows": (_i, [_p, _p] + [_i] * 10 + [_p]),

@@ -113,12 +113,14 @@ class RepConv(nn.Module):
         """BN_1(0) from the running statistics (the value the depthwise stencil reads outside the plane), cached by parameter version"""
         bn = self.body[1].bn
         key = tuple((t.data_ptr(), t._version) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        live = fused.live_fold(bn.weight)          # inside a live-weights capture: formed by the graph, the cache untouched
         hit = getattr(self, "_s2f_eval_border", None)
-        if hit is not None and hit[0] == key:
+        if hit is not None and hit[0] == key and not live:
             return hit[1]
         with torch.no_grad():
             border = (bn.bias - bn.running_mean * bn.weight / torch.sqrt(bn.running_var + bn.eps)).contiguous()
-        self._s2f_eval_border = (key, border)
+        if not live:
+            self._s2f_eval_border = (key, border)
         return border
 
 
@@ -309,8 +311,9 @@ class MS_Attention_RepConv_qkv_id(nn.Module):
         """eval mode: BN_1(0) (the stencil's border value) and BN_3 o BN_2 as one affine pair on BN_2's running statistics, cached on
         the versions of the 27 parameter / buffer tensors involved"""
         key = tuple((x.data_ptr(), x._version) for bns in t["bns"] for b in bns for x in (b.weight, b.bias, b.running_mean, b.running_var))
+        live = fused.live_fold(bn1.weight)          # as _eval_border
         hit = getattr(self, "_s2f_eval_affines", None)
-        if hit is not None and hit[0] == key:
+        if hit is not None and hit[0] == key and not live:
             return hit[1]
         with torch.no_grad():
             border = (bn1.bias - bn1.running_mean * bn1.weight / torch.sqrt(bn1.running_var + bn1.eps)).contiguous()
@@ -320,7 +323,8 @@ class MS_Attention_RepConv_qkv_id(nn.Module):
             pair.bias = ((bn2.bias - bn3.running_mean) * r3g3 + bn3.bias).contiguous()
             pair.running_mean, pair.running_var, pair.eps = bn2.running_mean.clone(), bn2.running_var.clone(), bn2.eps
         out = dict(border=border, pair=pair)
-        self._s2f_eval_affines = (key, out)
+        if not live:
+            self._s2f_eval_affines = (key, out)
         return out
 
     def _can_batch(self):

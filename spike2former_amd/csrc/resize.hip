@@ -1,6 +1,7 @@
 // General bilinear resizing of [planes, h, w] fp32 maps to [planes, H, W] (any sizes, enlarging or shrinking, align_corners False
-// or True), its deterministic adjoint, and the inference post-processing around it: arg-max / threshold of the class logits and
-// the test-time-augmentation accumulator (mmseg segmentors/seg_tta.py:14-48), for gfx950.
+// or True), its deterministic adjoint, and the inference post-processing around it: arg-max / threshold of the class logits, the
+// two fused into one pass that writes the label map alone (s2f_seg_label), and the test-time-augmentation accumulator (mmseg
+// segmentors/seg_tta.py:14-48), for gfx950.
 //
 // Call sites: every bilinear F.interpolate of the predict path that is not the exact-2x even-width case of upsample.hip -- the
 // pixel decoder's top-down up-samplings and MaskFormerHead.predict at image sizes that are not multiples of 32 (a 512 x 683
@@ -265,6 +266,49 @@ __global__ __launch_bounds__(256) void tta_acc_kernel(const float* __restrict__ 
   }
 }
 
+// Label map straight from the padded logits: one thread per output pixel of [H, W], tta_acc_kernel's walk over K.  Each class is
+// cropped, un-flipped and interpolated with resize_fwd_kernel's expressions (the same bits), and only the running best is kept:
+//   K > 1:  label = the arg-max over K by beats() -- seg_argmax_kernel's rule on values that are never stored;
+//   K == 1: sigmoid(v) > threshold into label (int64) or label_f (float 0 / 1).
+// What resize_fwd + seg_argmax write and read back as [K, H, W] fp32 planes stays in registers.
+__global__ __launch_bounds__(256) void seg_label_kernel(const float* __restrict__ x, int64_t* __restrict__ label,
+                                                        float* __restrict__ label_f, int K, Window wd, int h, int w, int H, int W,
+                                                        Axis ax, Axis ay, float threshold) {
+  const int ox = blockIdx.x * 256 + (int)threadIdx.x;
+  const int oy = blockIdx.y;
+  if (ox >= W) return;
+  int y0, y1, x0, x1;
+  float ly, lx;
+  axis_taps(ay, oy, y0, y1, ly);
+  axis_taps(ax, ox, x0, x1, lx);
+  const int64_t r0 = win_row(wd, h, y0), r1 = win_row(wd, h, y1);
+  const int c0 = win_col(wd, w, x0), c1 = win_col(wd, w, x1);
+  const int64_t o = (int64_t)oy * W + ox;
+  auto val = [&](int k) {
+    const float* b = x + (int64_t)k * wd.plane_stride;
+    const float top = (1.f - lx) * b[r0 + c0] + lx * b[r0 + c1];
+    const float bot = (1.f - lx) * b[r1 + c0] + lx * b[r1 + c1];
+    return (1.f - ly) * top + ly * bot;
+  };
+  if (K == 1) {
+    const bool on = sigmoidf_(val(0)) > threshold;
+    if (label) label[o] = on ? 1 : 0;
+    else label_f[o] = on ? 1.f : 0.f;
+    return;
+  }
+  float best = val(0);
+  int bi = 0;
+#pragma unroll 4
+  for (int k = 1; k < K; ++k) {
+    const float v = val(k);
+    if (beats(v, best)) {
+      best = v;
+      bi = k;
+    }
+  }
+  label[o] = bi;
+}
+
 inline int grid_1d(int64_t total) {
   int64_t b = (total + 255) / 256;
   if (b > 256 * 16) b = 256 * 16;
@@ -297,8 +341,8 @@ extern "C" int s2f_resize_fwd(const float* x, float* y, int64_t planes, int64_t 
   hipStream_t s = (hipStream_t)stream;
   s2f_dispatch_bool(vec, [&](auto v) {
     s2f_dispatch_bool(sig, [&](auto sg) {
-      hipLaunchKernelGGL((resize_fwd_kernel<v.value, sg.value>), grid, dim3(256), 0, s, x, y, planes, wd, h, w, H, W, ax, ay,
-                         rows_per_wg);
+      S2F_LAUNCH(true, true, (resize_fwd_kernel<v.value, sg.value>), grid, dim3(256), 0, s, x, y, planes, wd, h, w, H, W, ax, ay,
+                 rows_per_wg);
     });
   });
   return s2f_check_launch("s2f_resize_fwd");
@@ -325,8 +369,8 @@ extern "C" int s2f_seg_argmax(const float* x, int64_t* label, float* label_f, in
   S2F_REQUIRE(K > 0 && HW > 0, S2F_EINVAL, "s2f_seg_argmax: bad shape (K %d, HW %lld)", K, (long long)HW);
   S2F_REQUIRE(!(label && label_f) && (K == 1 || label), S2F_EINVAL,
               "s2f_seg_argmax: exactly one output; the float label map is for K == 1 only");
-  hipLaunchKernelGGL(seg_argmax_kernel, dim3(grid_1d(HW)), dim3(256), 0, (hipStream_t)stream, const_cast<float*>(x), label, label_f,
-                     K, HW, 0, sigmoid, threshold);
+  S2F_LAUNCH(true, true, seg_argmax_kernel, dim3(grid_1d(HW)), dim3(256), 0, (hipStream_t)stream, const_cast<float*>(x), label,
+             label_f, K, HW, 0, sigmoid, threshold);
   return s2f_check_launch("s2f_seg_argmax");
 }
 
@@ -342,6 +386,23 @@ extern "C" int s2f_tta_accumulate(const float* x, float* acc, int K, int64_t pla
   hipLaunchKernelGGL(tta_acc_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, (hipStream_t)stream, x, acc, K,
                      wd, h, w, H, W, ax, ay, first, (flags & S2F_RESIZE_SIGMOID) ? 1 : 0);
   return s2f_check_launch("s2f_tta_accumulate");
+}
+
+extern "C" int s2f_seg_label(const float* x, int64_t* label, float* label_f, int K, int64_t plane_stride, int row_stride, int row0,
+                             int col0, int h, int w, int H, int W, int flags, float threshold, void* stream) {
+  S2F_REQUIRE(x && (label || label_f), S2F_EINVAL, "s2f_seg_label: null pointer");
+  S2F_REQUIRE(K > 0 && H > 0 && W > 0 && H < 65536, S2F_EINVAL, "s2f_seg_label: bad shape (K %d, H %d, W %d)", K, H, W);
+  S2F_REQUIRE(!(label && label_f) && (K == 1 || label), S2F_EINVAL,
+              "s2f_seg_label: exactly one output; the float label map is for K == 1 only");
+  S2F_REQUIRE((flags & ~(S2F_RESIZE_ALIGN_CORNERS | S2F_RESIZE_FLIP_H | S2F_RESIZE_FLIP_V)) == 0, S2F_EINVAL,
+              "s2f_seg_label: unknown flags %d (the one-class sigmoid is implied)", flags);
+  if (check_window("s2f_seg_label", plane_stride, row_stride, row0, col0, h, w) != S2F_OK) return S2F_EINVAL;
+  const bool align = flags & S2F_RESIZE_ALIGN_CORNERS;
+  Window wd{plane_stride, row_stride, row0, col0, (flags & S2F_RESIZE_FLIP_H) != 0, (flags & S2F_RESIZE_FLIP_V) != 0};
+  const Axis ax = make_axis(w, W, align), ay = make_axis(h, H, align);
+  S2F_LAUNCH(true, true, seg_label_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)H), dim3(256), 0, (hipStream_t)stream, x, label,
+             label_f, K, wd, h, w, H, W, ax, ay, threshold);
+  return s2f_check_launch("s2f_seg_label");
 }
 
 extern "C" int s2f_tta_finish(float* acc, int64_t* label, float* label_f, int K, int64_t HW, int n_views, float threshold,

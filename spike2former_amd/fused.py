@@ -78,11 +78,21 @@ class _EvalBN:
     training, affine, momentum, num_batches_tracked = False, True, 0.0, None
 
 
+def live_fold(t):
+    """Whether what is folded from a BatchNorm's affine and running statistics (`t`: one of them) must be formed by launches of
+    the pass itself, past the version-keyed caches below: inside the capture of a step that re-converts its weights
+    (ops.RESPLIT_IN_GRAPH).  A cache hit would bake the folded values of capture time into the hipGraph while its replays
+    multiply by the live weights (graph.GraphedPredict: weights stay live); a value folded inside the capture lives in the graph's
+    pool, so the cache is not written either."""
+    return t.is_cuda and ops.cfg.RESPLIT_IN_GRAPH and torch.cuda.is_current_stream_capturing()
+
+
 def _composed_eval_pair(bn1, bn2):
     ts = (bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var)
     key = tuple((t.data_ptr(), t._version) for t in ts) + (bn1.eps, bn2.eps)
+    live = live_fold(bn1.weight)
     hit = getattr(bn2, "_s2f_eval_pair", None)
-    if hit is not None and hit[0] == key:
+    if hit is not None and hit[0] == key and not live:
         return hit[1]
     with torch.no_grad():
         r2g2 = bn2.weight / torch.sqrt(bn2.running_var + bn2.eps)
@@ -90,6 +100,8 @@ def _composed_eval_pair(bn1, bn2):
         out.weight = (bn1.weight * r2g2).contiguous()
         out.bias = ((bn1.bias - bn2.running_mean) * r2g2 + bn2.bias).contiguous()
         out.running_mean, out.running_var, out.eps = bn1.running_mean, bn1.running_var, bn1.eps
+    if live:
+        return out
     try:
         bn2._s2f_eval_pair = (key, out)
     except AttributeError:          # (an object without a __dict__)
@@ -102,14 +114,17 @@ def _scaled_eval_bn(bn, scale):
     the module by parameter version (inference: the parameters do not change between calls)."""
     ts = (bn.weight, bn.bias, scale)
     key = tuple((t.data_ptr(), t._version) for t in ts)
+    live = live_fold(bn.weight)
     hit = getattr(bn, "_s2f_eval_scaled", None)
-    if hit is not None and hit[0] == key:
+    if hit is not None and hit[0] == key and not live:
         return hit[1]
     with torch.no_grad():
         out = _EvalBN()
         out.weight = (bn.weight * scale).contiguous()
         out.bias = (bn.bias * scale).contiguous()
         out.running_mean, out.running_var, out.eps = bn.running_mean, bn.running_var, bn.eps
+    if live:
+        return out
     try:
         bn._s2f_eval_scaled = (key, out)
     except AttributeError:

@@ -15,13 +15,20 @@ capture (none on this path) would need a new capture.
 
 Every step class below is a `_Captured`: the capture protocol (`_capture`) and the replay prologue / epilogue (`_begin`,
 `_end`) are written there once; a class says which warm-up pass it runs, which stages it records and what lies between them.
+
+Inference is captured by the same protocol: `GraphedPredict` keeps one hipGraph per input shape of the stateless pass
+`reset_net(model); model.encode_decode(x, metas)` and `CapturePolicy` (host arithmetic only) decides which shapes are worth one.
 """
+import collections
 import contextlib
+import gc
+import time
+import weakref
 
 import torch
 
 from . import ops
-from .neuron import reset_net
+from .neuron import reset_net, reset_state, resettable
 
 
 def _process_group():
@@ -458,3 +465,176 @@ class GraphedOverlapStep(_Captured):
 
     def finish(self):
         self.red.wait()
+
+
+class CapturePolicy:
+    """Which inference calls become hipGraphs -- host arithmetic only, the device work injected:
+        eager(*args)          -> result                       a key not (yet) captured
+        capture(key, *args)   -> (entry, result)              at sighting number `capture_after` of a key
+        replay(entry, *args)  -> result                       every later call of that key
+    At most `max_graphs` entries live at once, the least recently used one is dropped (its graph and memory pool go with the last
+    reference); the sighting counts of uncaptured keys sit in a table of at most `max_sightings` keys, the oldest forgotten first, so
+    a stream of pictures whose shapes never repeat costs a dictionary entry each and nothing else.  `census`: what happened."""
+
+    def __init__(self, eager, capture, replay, max_graphs=8, capture_after=2, max_sightings=256):
+        if max_graphs < 1 or capture_after < 1 or max_sightings < 1:
+            raise ValueError(f"max_graphs, capture_after and max_sightings are >= 1, got {(max_graphs, capture_after, max_sightings)}")
+        self.eager, self.capture, self.replay = eager, capture, replay
+        self.max_graphs, self.capture_after, self.max_sightings = int(max_graphs), int(capture_after), int(max_sightings)
+        self.graphs, self.sightings = collections.OrderedDict(), collections.OrderedDict()
+        self.census = dict(captures=0, replays=0, evictions=0, eager={})
+
+    def count_eager(self, reason):
+        self.census["eager"][reason] = self.census["eager"].get(reason, 0) + 1
+
+    def __call__(self, key, *args):
+        entry = self.graphs.get(key)
+        if entry is not None:
+            self.graphs.move_to_end(key)
+            self.census["replays"] += 1
+            return self.replay(entry, *args)
+        seen = self.sightings.pop(key, 0) + 1
+        if seen < self.capture_after:
+            self.sightings[key] = seen                       # (re-inserted: the most recently seen key is forgotten last)
+            while len(self.sightings) > self.max_sightings:
+                self.sightings.popitem(last=False)
+            self.count_eager("sightings")
+            return self.eager(*args)
+        while len(self.graphs) >= self.max_graphs:           # before the capture: the dropped pool is free for the new one
+            self.graphs.popitem(last=False)
+            self.census["evictions"] += 1
+        entry, result = self.capture(key, *args)
+        self.graphs[key] = entry
+        self.census["captures"] += 1
+        return result
+
+
+class _PredictGraph(_Captured):
+    """one captured key of GraphedPredict: static input, graph, static output"""
+
+
+class GraphedPredict:
+    """The stateless inference `reset_net(model); model.encode_decode(x, metas)` (eval mode, no autograd) as hipGraph replays: one
+    graph per KEY = (input shape [B, 3, H, W], the `img_shape` MaskFormerHead.predict reads from batch_img_metas[0],
+    maskformer_head.PREDICT_LAST_ONLY, fused.EVAL_FUSION, ops.cfg.launch_snapshot()), by the rules of CapturePolicy.  `fn`: the
+    callable that is captured instead of `model.encode_decode` (EncoderDecoder routes its own encode_decode through here and passes
+    the plain one).
+
+    `gp(inputs, batch_img_metas)` -> seg logits [B, K, H, W].  A replay's result is the graph's STATIC output: the next replay of
+    that key overwrites it (`is_static(t)`: whether `t` is the buffer the last call returned).
+
+    Stateless by contract: the captured pass resets the membranes itself and runs with keep_membrane = False on every neuron (each
+    neuron's flag is put back when the capture ends); after every call of an eligible input -- eager, capturing or replaying -- the
+    membranes are in their reset state.
+    Weights stay live: ops.RESPLIT_IN_GRAPH is left alone, so a replay re-converts every weight from the fp32 parameters, and what
+    the eval routes fold from BatchNorm's affine and running statistics is folded inside the graph (fused.live_fold): an optimizer
+    step, an in-place edit or load_state_dict between replays is honoured without a new capture.  A parameter that is MOVED
+    (model.to(...), a new flat buffer) needs a new GraphedPredict.
+
+    Eligible: a contiguous fp32 CUDA input, the model in eval mode, autograd off, no capture under way, and no neuron with counters
+    (FiringRecorder, FiringLog) or forward hooks.  Anything else runs `fn` unchanged, and `census["eager"]` counts the reason next
+    to the captures, replays and evictions."""
+
+    def __init__(self, model, max_graphs=8, capture_after=2, warmup=2, fn=None):
+        self.model, self.warmup = model, max(int(warmup), 1)
+        self.fn = fn if fn is not None else model.encode_decode
+        # (through a weak reference: no cycle gp -> policy -> bound method -> gp, so a GraphedPredict that is dropped releases its
+        # graphs and their pools at once, by reference count, and not whenever the cycle collector next runs -- see _capture)
+        me = weakref.ref(self)
+        self.policy = CapturePolicy(lambda *a: me()._eager(*a), lambda *a: me()._capture(*a), lambda *a: me()._replay(*a),
+                                    max_graphs, capture_after)
+        self.census = self.policy.census
+        self.capture_log = []          # per capture: dict(key, seconds, reserved_bytes): what max_graphs is sized by
+        self._last_static = None
+        # the module tree is walked once, not per call (a replay is a few hundred microseconds of host time in all)
+        self._neurons = [m for m in model.modules() if hasattr(m, "keep_membrane")]
+        self._resettable = resettable(model)
+
+    def __deepcopy__(self, memo):      # a copied model captures its own graphs (EncoderDecoder builds a new one lazily)
+        return None
+
+    def key(self, inputs, batch_img_metas):
+        from . import fused, maskformer_head
+        return (tuple(inputs.shape), tuple(int(v) for v in batch_img_metas[0]["img_shape"]), bool(maskformer_head.PREDICT_LAST_ONLY),
+                bool(fused.EVAL_FUSION), tuple(sorted(ops.cfg.launch_snapshot().items())))
+
+    def ineligible(self, inputs):
+        """-> the reason this call cannot be a replay, or None"""
+        if not (torch.is_tensor(inputs) and inputs.is_cuda):
+            return "not_cuda"
+        if inputs.dtype != torch.float32 or inputs.dim() != 4 or not inputs.is_contiguous():
+            return "not_contiguous_fp32"
+        if self.model.training:
+            return "training_mode"
+        if torch.is_grad_enabled():
+            return "grad_enabled"
+        if torch.cuda.is_current_stream_capturing():
+            return "capturing"
+        for m in self._neurons:
+            if getattr(m, "stats", None) is not None:
+                return "firing_stats"
+            if m._forward_hooks:
+                return "forward_hooks"
+        return None
+
+    def is_static(self, t):
+        return t is not None and t is self._last_static
+
+    def __call__(self, inputs, batch_img_metas):
+        self._last_static = None
+        reason = self.ineligible(inputs)
+        if reason is not None:
+            self.policy.count_eager(reason)
+            return self.fn(inputs, batch_img_metas)
+        return self.policy(self.key(inputs, batch_img_metas), inputs, batch_img_metas)
+
+    def _eager(self, inputs, batch_img_metas):
+        reset_net(self.model)
+        out = self.fn(inputs, batch_img_metas)
+        reset_state(self.model, self._resettable)
+        return out
+
+    def _capture(self, key, inputs, batch_img_metas):
+        g = _PredictGraph()
+        neurons = self._neurons
+        flags = [m.keep_membrane for m in neurons]
+
+        def run():
+            reset_net(self.model)
+            return self.fn(g.static_in, batch_img_metas)
+
+        def warm():
+            g.result = run()
+
+        def record():
+            g.out = run()
+        # Nothing that owns a hipGraph may be released WHILE this capture records: destroying a graph or returning its pool inside a
+        # global-mode capture aborts the process, and the cycle collector runs whenever an allocation count says so (torch.cuda.graph
+        # no longer collects on entry).  Dead cycles -- a dropped model with its GraphedPredict -- are collected here, before.
+        gc.collect()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()          # (torch.cuda.graph does so on entry anyway: the growth below is then the graph's own)
+        t0, reserved = time.perf_counter(), torch.cuda.memory_reserved()
+        g.static_in = inputs.clone()
+        for m in neurons:
+            m.keep_membrane = False
+        try:
+            g.graph, = g._capture(warm, self.warmup, [record])
+        finally:
+            for m, keep in zip(neurons, flags):
+                m.keep_membrane = keep
+            reset_state(self.model, self._resettable)          # no module keeps a tensor of the graph's pool (a pre-fired spike map)
+        self.capture_log.append(dict(key=key[:2], seconds=time.perf_counter() - t0,
+                                     reserved_bytes=torch.cuda.memory_reserved() - reserved))
+        result, g.result = g.result, None          # the last warm-up pass computed this call's answer: a tensor of its own
+        result.record_stream(torch.cuda.current_stream())          # (allocated on the warm-up's side stream, read on this one)
+        return g, result
+
+    def _replay(self, g, inputs, batch_img_metas):
+        g._begin(inputs)
+        g.graph.replay()
+        for meta in batch_img_metas:          # what MaskFormerHead.predict leaves in the caller's metas
+            meta["batch_input_shape"] = meta["img_shape"]
+        reset_state(self.model, self._resettable)
+        self._last_static = g.out
+        return g.out

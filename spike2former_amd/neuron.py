@@ -181,12 +181,21 @@ _PURE_MEMO = {}
 PURE_MEMO = True          # share the launch of pure neurons applied to the same tensor (57.3 vs 57.7 ms/step at C2)
 
 
+def resettable(net: nn.Module):
+    return [m for m in net.modules() if hasattr(m, "reset")]
+
+
+def reset_state(net: nn.Module, modules=None):
+    """the host half of reset_net: `reset()` on every module that has one (`modules`: resettable(net), found earlier), no launch
+    (after a hipGraph replay of a stateless pass, graph.GraphedPredict: the modules hold nothing of the pass)"""
+    _PURE_MEMO.clear()
+    for m in resettable(net) if modules is None else modules:
+        m.reset()
+
+
 def reset_net(net: nn.Module):
     """functional.reset_net (functional.py:9-33): call `reset()` on every module that has one."""
-    _PURE_MEMO.clear()
-    for m in net.modules():
-        if hasattr(m, "reset"):
-            m.reset()
+    reset_state(net)
     p = next(net.parameters(), None)
     if p is not None and p.is_cuda:
         ops.begin_step(p.device)        # a reset opens a new step: rewind + clear the reduction-workspace arena

@@ -380,6 +380,22 @@ def seg_argmax(x, threshold=0.3, sigmoid=False, float_out=False):
     return out
 
 
+def seg_label(x, size, crop=None, flip=None, align_corners=False, threshold=0.3):
+    """x [K, Hp, Wp] fp32 CUDA -> the label map [1, H, W] of its window resized to `size`: int64 arg-max for K > 1, float 0 / 1
+    (sigmoid > threshold) for K == 1 -- the bits of seg_argmax(resize_window(x, size, crop, flip, align_corners, sigmoid=K == 1),
+    threshold, float_out=True) in ONE launch with no [K, H, W] intermediate (s2f_seg_label)."""
+    _need_cuda(x)
+    x = x.contiguous()
+    ps, ld, r0, c0, h, w = _window(x, crop)
+    K = x.shape[0]
+    H, W = (int(v) for v in size)
+    f = K == 1
+    out = torch.empty(1, H, W, dtype=torch.float32 if f else torch.int64, device=x.device)
+    check(lib.s2f_seg_label(_ptr(x), None if f else _ptr(out), _ptr(out) if f else None, K, ps, ld, r0, c0, h, w, H, W,
+                            lib_flags(align_corners, False, flip), float(threshold), _stream()), "s2f_seg_label")
+    return out
+
+
 def tta_accumulate(acc, x, first, crop=None, flip=None, align_corners=False, pre_sigmoid=False):
     """acc [K, H, W] (first ? = : +=) softmax over K of x's window (crop / flip / resize as resize_window) -- K == 1: sigmoid,
     after a first one with pre_sigmoid (s2f_tta_accumulate; mmseg seg_tta.py:29-34)"""

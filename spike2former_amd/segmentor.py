@@ -45,9 +45,38 @@ class EncoderDecoder(nn.Module):
         """mode='tensor': (all_cls_scores, all_mask_preds)."""
         return self.decode_head.forward(self.extract_feat(inputs), data_samples)
 
-    def encode_decode(self, inputs, batch_img_metas):
-        """-> seg logits [N, K, H, W] (encoder_decoder.py:126-136)."""
+    def _encode_decode(self, inputs, batch_img_metas):
         return self.decode_head.predict(self.extract_feat(inputs), batch_img_metas, self.test_cfg)
+
+    def encode_decode(self, inputs, batch_img_metas):
+        """-> seg logits [N, K, H, W] (encoder_decoder.py:126-136).
+
+        test_cfg['graph'] = True | dict(max_graphs=..., capture_after=..., warmup=...) (an addition; absent: every launch issued
+        from here, as before): the pass goes through a graph.GraphedPredict kept on the segmentor -- a shape seen `capture_after`
+        times is captured into a hipGraph and replayed from then on, as the STATELESS inference (membranes reset before the pass and
+        left reset after it); inputs it cannot replay (CPU tensors, train mode, autograd on, neurons with counters or hooks) run
+        the line below unchanged.  A replay returns the graph's static output: whatever leaves this class is cloned (`_own`)."""
+        gp = self.graphed_predict()
+        if gp is not None:
+            return gp(inputs, batch_img_metas)
+        return self._encode_decode(inputs, batch_img_metas)
+
+    def graphed_predict(self):
+        """the GraphedPredict of test_cfg['graph'] (built at first use; `.census` tells what it did), None without the option"""
+        opt = (self.test_cfg or {}).get("graph")
+        if not opt:
+            return None
+        gp = self.__dict__.get("_graphed_predict")
+        if gp is None:
+            from .graph import GraphedPredict
+            gp = GraphedPredict(self, fn=self._encode_decode, **(dict(opt) if isinstance(opt, dict) else {}))
+            self.__dict__["_graphed_predict"] = gp
+        return gp
+
+    def _own(self, seg_logits):
+        """`seg_logits` as a tensor the caller may keep: a copy where it is a captured graph's static output"""
+        gp = self.__dict__.get("_graphed_predict")
+        return seg_logits.clone() if gp is not None and gp.is_static(seg_logits) else seg_logits
 
     # ---- inference (encoder_decoder.py:246-350)
     def whole_inference(self, inputs, batch_img_metas):
@@ -77,6 +106,9 @@ class EncoderDecoder(nn.Module):
         group = self.test_cfg.get("window_batch")
         if group is not None and (int(group) != group or group < 1):
             raise ValueError(f"test_cfg['window_batch'] = {group!r}: an integer >= 1")
+        if group is None and self.test_cfg.get("graph"):
+            raise ValueError("test_cfg['graph'] with mode='slide' needs test_cfg['window_batch']: without it the membranes are carried "
+                             "from window to window, which the replay of a stateless pass cannot reproduce")
         boxes = []
         for h_idx in range(h_grids):
             for w_idx in range(w_grids):
@@ -138,6 +170,9 @@ class EncoderDecoder(nn.Module):
         if ours:
             seg_logits = seg_logits.contiguous()
         threshold = getattr(self.decode_head, "threshold", 0.3)
+        # test_cfg['seg_logits'] = False (an addition; absent: as before): fp32 CUDA logits go straight to the label map, one
+        # s2f_seg_label launch per image with no [K, H, W] planes at `ori_shape`, and the samples carry `pred_sem_seg` alone
+        labels_only = ours and (self.test_cfg or {}).get("seg_logits", True) is False
         for i in range(batch_size):
             if not only_prediction:
                 img_meta = data_samples[i].metainfo
@@ -147,6 +182,11 @@ class EncoderDecoder(nn.Module):
                 if flip:
                     flip_direction = img_meta.get("flip_direction", None)
                     assert flip_direction in ["horizontal", "vertical"]
+                if labels_only:
+                    data_samples[i].pred_sem_seg = PixelData(ops.seg_label(
+                        seg_logits[i], tuple(img_meta["ori_shape"]), crop=(padding_top, padding_bottom, padding_left, padding_right),
+                        flip=flip_direction if flip else None, align_corners=self.align_corners, threshold=threshold))
+                    continue
                 if ours:
                     i_seg_logits = ops.resize_window(seg_logits[i], tuple(img_meta["ori_shape"]),
                                                      crop=(padding_top, padding_bottom, padding_left, padding_right),
@@ -173,7 +213,8 @@ class EncoderDecoder(nn.Module):
             else:
                 i_seg_logits = i_seg_logits.sigmoid()
                 i_seg_pred = (i_seg_logits > threshold).to(i_seg_logits)
-            data_samples[i].seg_logits = PixelData(i_seg_logits)
+            if not labels_only:
+                data_samples[i].seg_logits = PixelData(i_seg_logits)
             data_samples[i].pred_sem_seg = PixelData(i_seg_pred)
         return data_samples
 
@@ -184,7 +225,10 @@ class EncoderDecoder(nn.Module):
         else:
             batch_img_metas = [dict(ori_shape=inputs.shape[2:], img_shape=inputs.shape[2:], pad_shape=inputs.shape[2:],
                                     padding_size=[0, 0, 0, 0])] * inputs.shape[0]
-        return self.postprocess_result(self.inference(inputs, batch_img_metas), data_samples)
+        seg_logits = self.inference(inputs, batch_img_metas)
+        if data_samples is None:          # the samples then carry views of the logits themselves
+            seg_logits = self._own(seg_logits)
+        return self.postprocess_result(seg_logits, data_samples)
 
     def preprocess(self, data, training=False):
         """data_preprocessor(data, training) -> dict(inputs, data_samples).  Without a data_preprocessor the inputs are only
@@ -216,7 +260,7 @@ class EncoderDecoder(nn.Module):
         if mode == "logits":
             metas = ([d.metainfo if hasattr(d, "metainfo") else d for d in data_samples] if data_samples
                      else [dict(img_shape=tuple(inputs.shape[-2:]))] * inputs.shape[0])
-            return self.inference(inputs, metas)
+            return self._own(self.inference(inputs, metas))
         if mode == "loss":
             return self.decode_head.loss(self.extract_feat(inputs), data_samples, self.train_cfg)
         raise RuntimeError(f'Invalid mode "{mode}". Only supports loss, predict and tensor mode')
