@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 48
+#define S2F_ABI_VERSION 49
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -1009,6 +1009,49 @@ int s2f_train_log_append(const float* const* srcs, int n, float* ring, int windo
  * synchronises: capturable behind the step's last launch. */
 int s2f_firing_log_append(uint64_t* counters, int n, int64_t* ring, int window, int32_t* silent, int patience, int64_t* head,
                           void* stream);
+
+/* ---- operand census: what a synaptic op really reads (csrc/opcensus.hip, ABI 49) -----------------------------------------------------
+ * The reference's tools/cal_firing_num.py stops at firing rates per neuron (fr_rate.csv) and leaves operations and energy to a
+ * spreadsheet.  Not every synaptic layer reads a neuron's output (SepConv.pwconv2 reads the depthwise convolution's real-valued map, the
+ * stem the image, the attention / DCNv3 / mask products tensors no neuron counter describes), so the census measures the OPERANDS:
+ *   s2f_operand_census   x: n contiguous elements, fp32 (dtype S2F_CENSUS_F32) or bf16 (S2F_CENSUS_BF16), aligned to the element only
+ *                        (any element offset into a larger buffer; nothing outside x[0 .. n) is read); D: the level grid, >= 1;
+ *                        row: int64 [8] on the device, ONE launch adds one operand into it:
+ *                          row[0] += n                   elements
+ *                          row[1] += sum level(x)        level(x) = x * D where that is an integer in [0, 65535], else 0
+ *                          row[2] += #{x != 0}           (-0.0 counts as zero)
+ *                          row[3] += #{x off the grid}   x * D not an integer, or < 0, or > 65535, or x not finite
+ *                          row[4]  = max(row[4], max level)
+ *                          row[5] += #{x not finite}
+ *                          row[6] += 1                   calls
+ *                          row[7]                        reserved, stays 0
+ *                        The product x * D is ONE fp32 multiply of x (a bf16 element widened exactly) by D converted to fp32, rounded
+ *                        to nearest even, and the integer test is made on that rounded product.  For D a power of two (every shipped
+ *                        config) the product is exact; for any other D an x whose exact product is within half an ulp of an integer
+ *                        counts as on the grid (1/3 as fp32 at D = 3 is level 1).  A subnormal x is off the grid.
+ *                        Integer sums and 64-bit atomics (one per field and workgroup): the row does not depend on the order of
+ *                        arrival, two runs give the same bits.  n == 0 adds one call and nothing else.
+ *                        S2F_EINVAL before any launch: null pointer, n < 0, D < 1, unknown dtype; S2F_EALIGN: x not aligned to its
+ *                        element, row not 8-byte aligned.  Nothing allocates or synchronises.
+ * Counting rules of the census built on it (spike2former_amd/energy.py: OpCensus / EnergyReport).  MACs of one call:
+ *     dense k x k conv        N C_out H_out W_out (C_in / groups) kh kw
+ *     depthwise conv          N C H_out W_out kh kw
+ *     1x1 conv / conv1d / linear   rows C_in C_out          (rows: every position the weight is applied at)
+ *     spike-driven attention  two products: k^T v = TB heads N_k d d  and  q (k^T v) = TB heads N_q d d  (csrc/sdsa.hip contracts in
+ *                             this association; the softmax-free form has no N_q x N_k product)
+ *     masked attention        q k^T and (q k^T) v: TB heads N_q N_k d each (csrc/sdsa_masked.hip; the mask forbids the association)
+ *     DCNv3 core              5 N H_out W_out G Cg K: per sampling point and channel 4 bilinear taps and 1 modulation
+ *     mask contraction        T B (L Q) C H W
+ *     class_mask_product      B K Q H W
+ * An operand is ON THE GRID when its row[3] == 0.  An op with at least one activation operand on the grid is accumulate-only: each
+ * spike of that operand adds the other operand's value `level` times, SOPs = MACs * min(rate) over its on-grid operands with
+ * rate = row[1] / row[0] (the mean integer count per element: the quantity in the reference's fr_rate.csv).  Any other op is real and
+ * costs its MACs.  energy = e_mac * sum(real MACs) + e_ac * sum(SOPs).  Not counted: BatchNorm (folded at inference), the neuron
+ * updates, residual adds, resizes, softmax / sigmoid. */
+#define S2F_CENSUS_F32 0
+#define S2F_CENSUS_BF16 1
+#define S2F_CENSUS_FIELDS 8
+int s2f_operand_census(const void* x, int dtype, int64_t n, int D, int64_t* row, void* stream);
 
 /* ---- general strided fp32 product on the vector ALUs (csrc/bmm.hip, round 6) -----------------------------------------------
  * C[b][m][n] = sum_k A[b][m][k] B[b][k][n], every operand with explicit ELEMENT strides (a transposed or broadcast operand is a

@@ -175,6 +175,7 @@ SIGNATURES = {
     "s2f_state_copy": (_i, [_p, _p, _i, _p, _i, _p]),
     "s2f_train_log_append": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "s2f_firing_log_append": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
+    "s2f_operand_census": (_i, [_p, _i, _i64, _i, _p, _p]),
 }
 
 

@@ -407,6 +407,7 @@ class MS_DownSampling(nn.Module):
         6-pass one.  None when the fusion does not apply (training, gradients, a stateful / observed neuron, odd shapes)."""
         conv, bn, n = self.encode_conv, self.encode_bn, next_lif
         if (bn.training or bn.running_mean is None or not bn.affine or torch.is_grad_enabled() or not fused.EVAL_FUSION
+                or ops.census_active()          # (a census reads the convolution's own input, not its column matrix)
                 or not x.is_cuda or conv.groups != 1 or conv.dilation != (1, 1) or conv.stride[0] != conv.stride[1]
                 or conv.padding[0] != conv.padding[1] or conv.kernel_size[0] != conv.kernel_size[1]):
             return None

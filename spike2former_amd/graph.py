@@ -570,6 +570,8 @@ class GraphedPredict:
             return "grad_enabled"
         if torch.cuda.is_current_stream_capturing():
             return "capturing"
+        if ops.census_active():          # (an OpCensus measures the operands of eager launches)
+            return "op_census"
         for m in self._neurons:
             if getattr(m, "stats", None) is not None:
                 return "firing_stats"

@@ -103,6 +103,11 @@ class Q_IFNode(nn.Module):
             y = pf[2].view(x.shape)
             return y.float() if as_float else y
         v_in = None if isinstance(self.v, float) else self.v
+        if v_in is not None and v_in.numel() != x.numel():
+            # the kernel reads one membrane value per input element: a membrane kept from a pass of another shape (a picture of another
+            # size, the SDME block evaluated for another number of decoder layers) would be read past its end
+            raise RuntimeError(f"Q_IFNode: the membrane kept from the last pass has shape {tuple(v_in.shape)}, the input "
+                               f"{tuple(x.shape)}: reset_net(model) before a pass of another shape")
         if self.stats is not None:
             self.stats_elems += x.numel()
         # A neuron that starts from a reset membrane, keeps none and records nothing is a pure function of its input: two

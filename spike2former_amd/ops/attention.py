@@ -158,6 +158,26 @@ class _SDSAMasked(torch.autograd.Function):
         return gq, gk, gv, None, None, None
 
 
+def _tap_sdsa(q, k, v, heads):
+    """the two products of the softmax-free core as csrc/sdsa.hip contracts them: k^T v per head, then q (k^T v)"""
+    TB, C, Nq = q.shape
+    kv, q_kv = sdsa_macs(TB, heads, C // heads, Nq, k.shape[2])
+    _TAP[0]("sdsa:kv", None, kv, (("k", k), ("v", v)))
+    _TAP[0]("sdsa:q_kv", None, q_kv, (("q", q),))
+
+
+def _tap_sdsa_stacked(y, dim, heads):
+    """the same for q | k | v stacked along `dim` of one spike map"""
+    data = y.data if isinstance(y, Spikes) else y
+    C = data.shape[dim] // 3
+    q, k, v = (data.narrow(dim, i * C, C) for i in range(3))
+    if dim == 0:
+        q, k, v = q[0], k[0], v[0]
+    if isinstance(y, Spikes):
+        q, k, v = Spikes(q), Spikes(k), Spikes(v)
+    _tap_sdsa(q, k, v, heads)
+
+
 def sdsa_masked(q, k, v, attn_mask, heads, scale, B):
     """The attention core with an `attn_mask` (True / non-zero = the score is replaced by 0).  q [T*B, C, Nq], k, v [T*B, C, Nk]: fp32
     tensors or Spikes.  attn_mask: b * heads * Nq * Nk booleans in any shape -- the reference reshapes to (t, heads, nq, nk) and
@@ -169,6 +189,11 @@ def sdsa_masked(q, k, v, attn_mask, heads, scale, B):
         raise NotImplementedError("sdsa_masked: head dimension > 64")
     if attn_mask.numel() != B * heads * Nq * Nk:
         raise RuntimeError(f"attn_mask has {attn_mask.numel()} elements; (batch {B}) x (heads {heads}) x (nq {Nq}) x (nk {Nk}) wanted")
+    if _TAP[0] is not None:
+        # the mask forbids the q (k^T v) association: q k^T, then (q k^T) v (csrc/sdsa_masked.hip), TB heads Nq Nk d each
+        qk, av = sdsa_masked_macs(TB, heads, C // heads, Nq, Nk)
+        _TAP[0]("sdsa_masked:qk", None, qk, (("q", q), ("k", k)))
+        _TAP[0]("sdsa_masked:av", None, av, (("v", v),))
     m = attn_mask.reshape(B, heads, Nq, Nk).to(device=q.device, dtype=torch.uint8)
     return _SDSAMasked.apply(spikes_float(q), spikes_float(k), spikes_float(v), m, heads, float(scale))
 
@@ -177,6 +202,8 @@ def sdsa(q, k, v, heads, scale, lif=None):
     """o = scale * q (k^T v) on channel-major spike maps.  q, k, v: fp32 tensors or Spikes.  `lif`: the Q_IFNode applied to o
     (the attention's attn_spike); given, the result is its spike map (Spikes) -- from ONE fused kernel when the neuron starts
     from a reset membrane and keeps none and the shapes allow it (backbone self-attention), else core + neuron."""
+    if _TAP[0] is not None:
+        _tap_sdsa(q, k, v, heads)
     bf = all(isinstance(t, Spikes) and t.tok is not None for t in (q, k, v))
     bf = bf and q.shape[2] % 4 == 0 and k.shape[2] % 4 == 0 and q.shape[1] // heads <= 64
     if not bf:
@@ -190,6 +217,8 @@ def sdsa_packed(y, heads, scale, lif=None):
     if not (isinstance(y, Spikes) and y.tok is not None and y.shape[2] % 4 == 0 and y.shape[1] // 3 // heads <= 64):
         q, k, v = split3(spikes_float(y))
         return sdsa(q, k, v, heads, scale, lif)
+    if _TAP[0] is not None:
+        _tap_sdsa_stacked(y, 1, heads)
     return _sdsa_spikes(y.data, None, None, y.tok, None, None, heads, scale, True, lif)
 
 
@@ -199,6 +228,8 @@ def sdsa_siblings(y, heads, scale, lif=None):
     if not (isinstance(y, Spikes) and y.tok is not None and y.data.dim() == 4 and y.shape[0] == 3 and y.shape[3] % 4 == 0
             and y.shape[2] // heads <= 64):
         raise RuntimeError("sdsa_siblings: a bf16 spike map [3, TB, C, N] with N % 4 == 0 and heads of at most 64 channels wanted")
+    if _TAP[0] is not None:
+        _tap_sdsa_stacked(y, 0, heads)
     return _sdsa_spikes(y.data, None, None, y.tok, None, None, heads, scale, 2, lif)
 
 
@@ -267,8 +298,18 @@ class _DCNv3(torch.autograd.Function):
         return (gx, goff, gm) + (None,) * 11
 
 
+def _tap_dcnv3(x, offset, mask, kh, kw, G, Cg):
+    """per output pixel, group channel and sampling point 4 bilinear taps of x and 1 modulation by the mask: 5 N Ho Wo G Cg K in two
+    rows, because the two read different operands (the map; the mask neuron's spikes)"""
+    sample, modulate = dcnv3_macs(offset.shape[0], offset.shape[1], offset.shape[2], G, Cg, kh * kw)
+    _TAP[0]("dcnv3:sample", None, sample, (("x", x),))
+    _TAP[0]("dcnv3:modulate", None, modulate, (("mask", mask),))
+
+
 def dcnv3_core(x, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, offset_scale):
     """`mask` may arrive as a Spikes pair (the module's mask neuron): the gather reads it as fp32."""
+    if _TAP[0] is not None:
+        _tap_dcnv3(x, offset, mask, kh, kw, G, Cg)
     return _DCNv3.apply(x, offset, spikes_float(mask), kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, float(offset_scale))
 
 
@@ -308,6 +349,8 @@ def dcnv3_cm_ok(N, H, W, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg):
 def dcnv3_core_cm(x, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, offset_scale):
     """dcnv3_core on channel-major maps, x [N, C, H, W] -> [N, C, Ho, Wo], without the transposition pair around the NHWC core;
     for geometries with dcnv3_cm_ok (any other is an error here: the caller keeps the transposing route for them)."""
+    if _TAP[0] is not None:
+        _tap_dcnv3(x, offset, mask, kh, kw, G, Cg)
     return _DCNv3CM.apply(x, offset, spikes_float(mask), kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, float(offset_scale))
 
 

@@ -76,6 +76,8 @@ def dwconv_bn_lif_eval(x, w, pad, running_mean, running_var, gamma, beta, eps, b
     N, C, H, W = data.shape
     K = w.shape[-1]
     Ho, Wo = H + 2 * pad - K + 1, W + 2 * pad - K + 1
+    if _TAP[0] is not None:
+        _TAP[0]("dwconv", w, conv_macs(N, C, H, W, C, K, K, 1, pad, C), (("x", x, 1),))
     dev = data.device
     with torch.no_grad():
         u = torch.empty(N, C, Ho, Wo, dtype=torch.float32, device=dev) if want_pre else None
@@ -91,6 +93,10 @@ def dwconv(x, w, pad, border=None, stats=False):
     """x: fp32 tensor or Spikes.  stats: the consumer is a train-mode BatchNorm -- where the stencil can (3 x 3, pad 1, no border,
     cfg.BN_PARTIALS) it stores the BatchNorm partials with y and hands them over as y's `_s2f_part` (gemm.stats_of)"""
     data, tok = _unpack(x)
+    if _TAP[0] is not None:
+        N, C, H, W = data.shape
+        K = w.shape[-1]
+        _TAP[0]("dwconv", w, conv_macs(N, C, H, W, C, K, K, 1, pad, C), (("x", x, 1),))
     return _with_part(*_DWConv.apply(data, tok, w, border, pad, bool(stats)))
 
 
@@ -229,7 +235,7 @@ class _ConvDense(torch.autograd.Function):
             elif M < C and stride == 1 and kh == kw and Ho == H and Wo == W:
                 wt = weight.flip(2, 3).permute(1, 0, 2, 3).reshape(C, M * kh * kw)        # [C, M*k*k], tiny
                 gcols = im2col(gy.view(N, M, Ho, Wo), kh, kw, 1, kh - 1 - padding)
-                gx = bmm_small(wt.unsqueeze(0).expand(N, -1, -1), gcols).view(N, C, H, W)
+                gx = _bmm_small(wt.unsqueeze(0).expand(N, -1, -1), gcols).view(N, C, H, W)
             else:
                 dcols = dx_gemm(w2d, gy)
                 gx = col2im(dcols, C, H, W, kh, kw, stride, padding)
@@ -272,7 +278,7 @@ class _ConvDense(torch.autograd.Function):
                 check(lib.s2f_gemm_dw_general(_ptr(gy), 0, _ptr(cols), 0, _ptr(gw if sink is None else sink), N, M, K, Ho * Wo,
                                               int(sink is not None), _stream()), "s2f_gemm_dw_general")
             else:
-                gw = bmm_small(gy, cols.float().transpose(1, 2), reduce_batch=True)          # ragged / tiny maps (csrc/bmm.hip)
+                gw = _bmm_small(gy, cols.float().transpose(1, 2), reduce_batch=True)          # ragged / tiny maps (csrc/bmm.hip)
             gw = gw.view_as(weight) if gw is not None else None
         if has_bias and ctx.needs_input_grad[3]:
             gb = gy.sum((0, 2))
@@ -282,6 +288,10 @@ class _ConvDense(torch.autograd.Function):
 def conv_dense(x, weight, bias, stride, padding, spike_input, stats=False):
     """x: fp32 tensor, or Spikes (then `spike_input` is implied).  stats: as spike_gemm"""
     data, tok = _unpack(x)
+    if _TAP[0] is not None:
+        N, C, H, W = data.shape
+        M, Cg, kh, kw = weight.shape
+        _TAP[0]("conv", weight, conv_macs(N, C, H, W, M, kh, kw, stride, padding, C // Cg), (("x", x),))
     return _with_part(*_ConvDense.apply(data, tok, weight, bias, stride, padding, spike_input or isinstance(x, Spikes), bool(stats)))
 
 

@@ -579,6 +579,57 @@ def split3(y):
 
 
 
+# ------------------------------------------------------------------------------------------------ operand census taps
+# Every synaptic product of the forward has ONE home, its ops entry point; while a census is live (energy.OpCensus) that entry point
+# reports itself once per call, before it launches:   _TAP[0](kind, weight, macs, operands)
+#   kind      "conv" | "dwconv" | "gemm" | "linear" | "sdsa:kv" | ... (the row's kind; for a weightless product part of its key)
+#   weight    the weight tensor as the op received it (the census finds the parameter(s) by address: a view from a parameter's first
+#             element, a slice of one, or an alias that spans adjacent sibling parameters -- then one row per parameter), or None
+#   macs      multiply-accumulates of this call (include/s2f.h "operand census": counting rules)
+#   operands  ((name, tensor or Spikes[, dim]), ...): the activation operands; `dim`: the operand's dimension that splits with the
+#             weight's rows when the weight spans several parameters (a depthwise stencil over stacked channel groups)
+# Inactive, a tap is the one test `_TAP[0] is not None`.
+_TAP = [None]
+
+
+# The counting rules (include/s2f.h "operand census"): the taps compute their MACs with these and with nothing else.
+def conv_macs(N, C_in, H, W, C_out, kh, kw, stride=1, padding=0, groups=1):
+    """dense / grouped / depthwise (groups == C_in == C_out) k x k convolution of an [N, C_in, H, W] map"""
+    Ho, Wo = (H + 2 * padding - kh) // stride + 1, (W + 2 * padding - kw) // stride + 1
+    return N * C_out * Ho * Wo * (C_in // groups) * kh * kw
+
+
+def linear_macs(rows, C_in, C_out):
+    """1x1 convolution / conv1d / linear layer applied at `rows` positions"""
+    return rows * C_in * C_out
+
+
+def product_macs(B, M, K, N):
+    """B products [M, K] @ [K, N]: the mask contraction (B = batch, K = T C), the class-mask product, a bare bmm"""
+    return B * M * K * N
+
+
+def sdsa_macs(TB, heads, d, N_q, N_k):
+    """-> (k^T v, q (k^T v)) of the spike-driven attention core: the association csrc/sdsa.hip contracts in"""
+    return TB * heads * N_k * d * d, TB * heads * N_q * d * d
+
+
+def sdsa_masked_macs(TB, heads, d, N_q, N_k):
+    """-> (q k^T, (q k^T) v) of the masked core (csrc/sdsa_masked.hip): the mask forbids the other association"""
+    return TB * heads * N_q * N_k * d, TB * heads * N_q * N_k * d
+
+
+def dcnv3_macs(N, H_out, W_out, G, Cg, K):
+    """-> (4 bilinear taps of the map, 1 modulation by the mask) per output pixel, group channel and sampling point"""
+    points = N * H_out * W_out * G * Cg * K
+    return 4 * points, points
+
+
+def census_active():
+    """a census is live: routes that fold two layers into one product, or lower a layer to another op's input, step aside"""
+    return _TAP[0] is not None
+
+
 BN_PARTIALS_USED = [0, 0]          # [BatchNorm launches fed by partials, s2f_bn_stats launches] since the last reset (tests, census)
 
 

@@ -21,7 +21,14 @@ from .wcache import pack_weight, pack_weight_conv3, split_weight          # the 
 
 def bmm_small(a, b, reduce_batch=False):
     """a [B, M, K] @ b [B, K, N] -> [B, M, N] (or, `reduce_batch`, their sum over B -> [M, N]); fp32, any strides (expanded /
-    transposed views are read in place)."""
+    transposed views are read in place).  The entry point of a caller outside the op layer: a product of its own to a live census
+    (the ops of this package call _bmm_small, whose product their own tap has already reported)."""
+    if _TAP[0] is not None:
+        _TAP[0]("bmm", None, product_macs(a.shape[0], a.shape[1], a.shape[2], b.shape[2]), (("a", a), ("b", b)))
+    return _bmm_small(a, b, reduce_batch)
+
+
+def _bmm_small(a, b, reduce_batch=False):
     _need_cuda(a, b)
     B, M, K = a.shape
     N = b.shape[2]
@@ -62,7 +69,7 @@ def _dense_product(x, ws, stats):
     B, _, L = x.shape
     if not _dense_fast(L):
         wb = torch.stack(ws, 0).unsqueeze(0).expand(B, G, M, K).reshape(B * G, M, K) if G > 1 else ws[0].expand(B, M, K)
-        return bmm_small(wb, x.view(B * G, K, L)).view(B, G * M, L), None
+        return _bmm_small(wb, x.view(B * G, K, L)).view(B, G * M, L), None
     y = torch.empty(B, G * M, L, dtype=torch.float32, device=x.device)
     P = _want_partials(stats, B, G * M, L)
     part = torch.empty(G * M, P, 2, dtype=torch.float32, device=x.device) if P else None
@@ -143,11 +150,19 @@ class _DenseGemm(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             wt = torch.stack(ws, 0).transpose(1, 2)
             wb = wt.unsqueeze(0).expand(B, G, K, M).reshape(B * G, K, M) if G > 1 else wt[0].expand(B, K, M)
-            gx = bmm_small(wb, gyv).view(B, G * K, L)
+            gx = _bmm_small(wb, gyv).view(B, G * K, L)
         if any(ctx.needs_input_grad[2:]):
-            gw = bmm_small(gyv, x.view(B * G, K, L).transpose(1, 2)).view(B, G, M, K).sum(0)
+            gw = _bmm_small(gyv, x.view(B * G, K, L).transpose(1, 2)).view(B, G, M, K).sum(0)
             gws = [gw[g] for g in range(G)]
         return (None, gx, *gws)
+
+
+def _tap_grouped(x, ws):
+    """G weights [M, K] on the consecutive channel groups of x [B, G K, L]: one report per weight, each with its own group of x"""
+    B, _, L = x.shape
+    for g, w in enumerate(ws):
+        M, K = w.shape
+        _TAP[0]("gemm", w, linear_macs(B * L, K, M), (("x", x[:, g * K:(g + 1) * K]),))
 
 
 def dense_gemm(x, w, stats=False):
@@ -155,6 +170,8 @@ def dense_gemm(x, w, stats=False):
     keeps its own cached pack and gradient sink) -> [B, G*M, L].  stats: as spike_gemm"""
     if torch.is_tensor(w):
         w = [w] if w.dim() == 2 else list(w.unbind(0))
+    if _TAP[0] is not None:
+        _tap_grouped(x, w)
     y, part = _DenseGemm.apply(bool(stats), x, *w)
     return _with_part(y, part)
 
@@ -297,7 +314,7 @@ class _SpikeGemm(torch.autograd.Function):
             if L % 4 == 0 and M >= 16:     # the matrix-core kernels: 32- / 64- / 128-row tiles by M
                 gw = _spike_dw(gy, x, w2d, B, M, K, L, pipe=True)
             else:
-                gw = bmm_small(gy, x.float().transpose(1, 2), reduce_batch=True)          # shapes the matrix-core kernels do not take
+                gw = _bmm_small(gy, x.float().transpose(1, 2), reduce_batch=True)          # shapes the matrix-core kernels do not take
         if ctx.has_bias and ctx.needs_input_grad[3]:
             gb = gy.sum((0, 2))
         return _grad_pair(ctx.has_tok, gx) + (gw, gb, None)
@@ -373,6 +390,8 @@ def spike_gemm_siblings(xs, ws):
     """xs: G bf16 Spikes [B, K, L], ws: G weights [M, K] (spike_gemm_siblings_ok) -> fp32 [G, B, M, L], one launch."""
     args = []
     for x, w in zip(xs, ws):
+        if _TAP[0] is not None:
+            _TAP[0]("gemm", w, linear_macs(x.shape[0] * x.shape[2], w.shape[1], w.shape[0]), (("x", x),))
         args += [x.data, x.tok, w]
     return _SpikeGemmSiblings.apply(*args)
 
@@ -388,7 +407,7 @@ def dx_gemm(w2d, gy):
         check(lib.s2f_pgemm_dx_f32(_ptr(pack_weight(w2d)), _ptr(gy), 0, _ptr(gx), 0, B, M, K, N, 0.0, 0, _stream()),
               "s2f_pgemm_dx_f32")
         return gx
-    return bmm_small(w2d.t().unsqueeze(0).expand(B, -1, -1), gy)          # N % 4 != 0 (10-query rows of the plumbing configuration)
+    return _bmm_small(w2d.t().unsqueeze(0).expand(B, -1, -1), gy)          # N % 4 != 0 (10-query rows of the plumbing configuration)
 
 
 def gemm_bn_lif_eval_ok(x, N):
@@ -406,6 +425,8 @@ def gemm_bn_lif_eval(x, w2d, conv_bias, running_mean, running_var, gamma, beta, 
     data = x.data.contiguous()
     B, K, N = data.shape
     M = w2d.shape[0]
+    if _TAP[0] is not None:
+        _TAP[0]("gemm", w2d, linear_macs(B * N, K, M), (("x", x),))
     dev = data.device
     with torch.no_grad():
         u = torch.empty(B, M, N, dtype=torch.float32, device=dev) if want_pre else None
@@ -442,6 +463,8 @@ def dense_gemm_bn_lif_eval(x, ws, conv_bias, running_mean, running_var, gamma, b
     x = x.contiguous()
     B, GK, N = x.shape
     assert GK == G * K and 1 <= G <= 4
+    if _TAP[0] is not None:
+        _tap_grouped(x, ws)
     dev = x.device
     with torch.no_grad():
         u = torch.empty(B, G * M, N, dtype=torch.float32, device=dev) if want_pre else None
@@ -463,6 +486,8 @@ def conv3x3_bn_lif_eval(x, weight, running_mean, running_var, gamma, beta, eps, 
     data = x.data.contiguous()
     B, C, H, W = data.shape
     M = weight.shape[0]
+    if _TAP[0] is not None:
+        _TAP[0]("conv", weight, conv_macs(B, C, H, W, M, 3, 3, 1, 1), (("x", x),))
     dev = data.device
     with torch.no_grad():
         u = torch.empty(B, M, H, W, dtype=torch.float32, device=dev) if want_pre else None
@@ -484,6 +509,8 @@ def spike_gemm(x, w2d, bias=None, stats=False):
     """x: Spikes or an fp32 spike tensor [B, K, N].  stats: a train-mode BatchNorm follows -- store its partial statistics with
     the output (attribute `_s2f_part`, see cfg.BN_PARTIALS) when the kernel path can"""
     data, tok = _unpack(x)
+    if _TAP[0] is not None:
+        _TAP[0]("gemm", w2d, linear_macs(data.shape[0] * data.shape[2], data.shape[1], w2d.shape[0]), (("x", x),))
     return _with_part(*_SpikeGemm.apply(data, tok, w2d, bias, bool(stats)))
 
 
@@ -546,7 +573,7 @@ def _mm_tm(x2d, w_oc):
     repeats bit for bit); ops.bmm_small for c % 4 != 0."""
     n, c = x2d.shape
     if not (c % 4 == 0 and x2d.is_cuda and n > 0):
-        return bmm_small(x2d.unsqueeze(0), w_oc.t().unsqueeze(0))[0]
+        return _bmm_small(x2d.unsqueeze(0), w_oc.t().unsqueeze(0))[0]
     y = torch.zeros(n, w_oc.shape[0], dtype=torch.float32, device=x2d.device)
     check(lib.s2f_gemm_dw_general(_ptr(x2d.contiguous()), 0, _ptr(w_oc.contiguous()), 0, _ptr(y), 1, n, w_oc.shape[0], c, 3, _stream()),
           "s2f_gemm_dw_general")
@@ -560,7 +587,7 @@ def _mtm_tm(a2d, b2d, out=None):
     n, o = a2d.shape
     c = b2d.shape[1]
     if not (c % 4 == 0 and a2d.is_cuda and n > 0):
-        r = bmm_small(a2d.t().unsqueeze(0), b2d.unsqueeze(0))[0]
+        r = _bmm_small(a2d.t().unsqueeze(0), b2d.unsqueeze(0))[0]
         return r if out is None else out.copy_(r)
     ap = torch.empty(int(lib.s2f_pack_elems(n, o)), dtype=torch.int16, device=a2d.device)
     check(lib.s2f_pack_bf16x3(_ptr(a2d.contiguous()), _ptr(ap), n, o, 0, 0, _stream()), "s2f_pack_bf16x3")
@@ -582,14 +609,14 @@ class _LinearSmall(torch.autograd.Function):
         _need_cuda(x, w, b)
         ctx.save_for_backward(x, w)
         ctx.has_bias = b is not None
-        y = bmm_small(x.unsqueeze(0), w.detach().t().unsqueeze(0))[0]
+        y = _bmm_small(x.unsqueeze(0), w.detach().t().unsqueeze(0))[0]
         return y + b.detach() if b is not None else y
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gx = bmm_small(gy.unsqueeze(0), w.detach().unsqueeze(0))[0] if ctx.needs_input_grad[0] else None
-        gw = bmm_small(gy.t().unsqueeze(0), x.unsqueeze(0))[0] if ctx.needs_input_grad[1] else None
+        gx = _bmm_small(gy.unsqueeze(0), w.detach().unsqueeze(0))[0] if ctx.needs_input_grad[0] else None
+        gw = _bmm_small(gy.t().unsqueeze(0), x.unsqueeze(0))[0] if ctx.needs_input_grad[1] else None
         gb = gy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         return gx, gw, gb
 
@@ -598,6 +625,8 @@ def linear_tm(x, weight, bias=None):
     """torch.nn.functional.linear(x, weight, bias) for x [..., c] fp32 on the GPU: the token-major matrix-core products for
     c % 4 == 0, ops.bmm_small otherwise."""
     c = x.shape[-1]
+    if _TAP[0] is not None:
+        _TAP[0]("linear", weight, linear_macs(x.numel() // c, c, weight.shape[0]), (("x", x),))
     if not (x.is_cuda and x.dtype == torch.float32 and x.numel() > 0):
         fallback("linear_tm", f"c={c} dtype={x.dtype} cuda={x.is_cuda}")
         return torch.nn.functional.linear(x, weight, bias)
@@ -647,7 +676,7 @@ class _MaskEinsum(torch.autograd.Function):
         else:
             # E not exact in bf16, or ragged rows: one strided product with the T slabs folded into the contraction
             # (row (b, q) x column (t, c) against row (t, c) x column hw), ascending-k fp32 multiply-adds
-            out = bmm_small((e * scale).permute(1, 2, 0, 3).reshape(B, Q, T * C), mf.permute(1, 0, 2, 3).reshape(B, T * C, HW))
+            out = _bmm_small((e * scale).permute(1, 2, 0, 3).reshape(B, Q, T * C), mf.permute(1, 0, 2, 3).reshape(B, T * C, HW))
         ctx.save_for_backward(e, mf)
         ctx.scale, ctx.mfma = scale, mfma
         return out
@@ -669,7 +698,7 @@ class _MaskEinsum(torch.autograd.Function):
                         check(lib.s2f_spike_gemm_dw(_ptr(g[b]), _ptr(mf[t, b]), _ptr(ge[t, b]), 1, Q, C, HW, 1, 3, _stream()),
                               "s2f_spike_gemm_dw")
             else:
-                ge = torch.stack([bmm_small(g, mf[t].transpose(1, 2)) for t in range(T)], 0)
+                ge = torch.stack([_bmm_small(g, mf[t].transpose(1, 2)) for t in range(T)], 0)
             ge.mul_(ctx.scale)
         if ctx.needs_input_grad[1]:
             gmf = torch.empty_like(mf)
@@ -683,11 +712,14 @@ class _MaskEinsum(torch.autograd.Function):
             else:
                 es = e * ctx.scale
                 for t in range(T):
-                    gmf[t].copy_(bmm_small(es[t].transpose(1, 2), g))
+                    gmf[t].copy_(_bmm_small(es[t].transpose(1, 2), g))
         return ge, gmf, None, None
 
 
 def mask_einsum(e, mf, scale, e_exact=False):
+    if _TAP[0] is not None:
+        T, B, Q, C = e.shape
+        _TAP[0]("mask_einsum", None, product_macs(B, Q, T * C, mf.shape[-1]), (("e", e), ("mask_features", mf)))
     return _MaskEinsum.apply(e, mf, float(scale), bool(e_exact))
 
 
@@ -810,6 +842,8 @@ def class_mask_product(cls_score, mask_probs):
     the class scores packed on the fly) instead of the vendor GEMM the einsum lowers to.  No autograd (inference glue)."""
     B, Q, K = cls_score.shape
     h, w = mask_probs.shape[-2:]
+    if _TAP[0] is not None:
+        _TAP[0]("class_mask_product", None, product_macs(B, K, Q, h * w), (("cls_score", cls_score), ("mask_probs", mask_probs)))
     if not cls_score.is_cuda:
         # host tensors: the a13 callers are Python glue in the reference too and are pinned on the CPU bit for bit
         # (tests/test_a13_callers.py); nothing of the hot path runs there
@@ -818,7 +852,7 @@ def class_mask_product(cls_score, mask_probs):
         fallback("class_mask_product", "autograd wanted through the inference post-processing")
         return torch.einsum("bqc,bqhw->bchw", cls_score, mask_probs)
     if not ((h * w) % 4 == 0 and cls_score.dtype == torch.float32):          # (host tensors returned above)
-        return bmm_small(cls_score.transpose(1, 2), mask_probs.reshape(B, Q, h * w)).view(B, K, h, w)
+        return _bmm_small(cls_score.transpose(1, 2), mask_probs.reshape(B, Q, h * w)).view(B, K, h, w)
     out = torch.empty(B, K, h, w, dtype=torch.float32, device=cls_score.device)          # every image's product lands in its slice
     for b in range(B):
         _mtm_tm(cls_score[b], mask_probs[b].reshape(Q, h * w), out=out[b].view(K, h * w))
@@ -829,6 +863,12 @@ def mask_einsum_folded(e, spikes, W, bias, scale, T, B, e_exact=False):
     """e [T, B, Q, Co], spikes: bf16 Spikes [T*B, C, HW] (mask_feature_spike's output), W [Co, C], bias [Co] or None -> [B, Q, HW].
     Needs C % 32 == 0 and HW % 4 == 0 (RuntimeError otherwise, nothing launched): see _MaskEinsumFolded."""
     assert isinstance(spikes, Spikes) and spikes.tok is not None and spikes.data.dtype == torch.bfloat16
+    if _TAP[0] is not None:
+        # what this route contracts: E W (a product with the mask_feature weight, per token) and (E W) S; a census pass itself runs
+        # the two layers apart (maskformer_head.FOLD_MASK_FEATURE steps aside)
+        Q, Co, C = e.shape[2], W.shape[0], W.shape[1]
+        _TAP[0]("linear", W, linear_macs(T * B * Q, Co, C), (("e", e),))
+        _TAP[0]("mask_einsum_folded", None, product_macs(B, Q, T * C, spikes.shape[-1]), (("spikes", spikes),))
     return _MaskEinsumFolded.apply(e, spikes.data, spikes.tok, W, bias, float(scale), int(T), int(B), bool(e_exact))
 
 

@@ -54,7 +54,7 @@ class EncoderDecoder(nn.Module):
         test_cfg['graph'] = True | dict(max_graphs=..., capture_after=..., warmup=...) (an addition; absent: every launch issued
         from here, as before): the pass goes through a graph.GraphedPredict kept on the segmentor -- a shape seen `capture_after`
         times is captured into a hipGraph and replayed from then on, as the STATELESS inference (membranes reset before the pass and
-        left reset after it); inputs it cannot replay (CPU tensors, train mode, autograd on, neurons with counters or hooks) run
+        left reset after it); inputs it cannot replay (CPU tensors, train mode, autograd on, neurons with counters or hooks, a live OpCensus) run
         the line below unchanged.  A replay returns the graph's static output: whatever leaves this class is cloned (`_own`)."""
         gp = self.graphed_predict()
         if gp is not None:
