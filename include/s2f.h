@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 49
+#define S2F_ABI_VERSION 50
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -1009,6 +1009,45 @@ int s2f_train_log_append(const float* const* srcs, int n, float* ring, int windo
  * synchronises: capturable behind the step's last launch. */
 int s2f_firing_log_append(uint64_t* counters, int n, int64_t* ring, int window, int32_t* silent, int patience, int64_t* head,
                           void* stream);
+
+/* ---- gradient log: per-parameter gradient, weight and update norms from inside the step (csrc/gradlog.hip, ABI 50) ---------------
+ * Where the gradient goes, per parameter tensor and iteration, without ~1 000 norm launches and a host stop: a segmented reduction
+ * over the buffers s2f_adamw_step has just updated, into a ring the host reads once per interval.  Per parameter i and iteration one
+ * row of eight 8-byte words -- columns 0-3 doubles stored by bit pattern, columns 4-7 int64:
+ *     0  sum g^2 over the finite elements of the raw gradient (as the all-reduce left it, before clipping)
+ *     1  sum p^2 over the finite elements of the parameter AFTER the update
+ *     2  sum u^2 over the finite u = step_size * (m / (sqrtf(v) / bc2s + eps)), the Adam step just applied without the decay term:
+ *        the fp32 expressions of s2f_adamw_step in their order, from the post-update m, v, hyper and state[2], state[3]; u = 0 for a
+ *        parameter with lr < 0 (no gradient)
+ *     3  max |g| over the finite elements (0 if none)        4  elements with g == 0        5  non-finite elements of g
+ *     6  elements whose p or u is non-finite                  7  numel
+ * Only numel elements count, never the zero pads of the 16-byte slots.
+ *   s2f_grad_log_span_elems  the most elements of one span (16 384).
+ *   s2f_grad_log_partials    slots, hyper, g, m, v, state: the arguments of s2f_adamw_step, after it ran.  spans int32 [nspans][2] =
+ *                            {slot, first element}: every parameter in runs of s2f_grad_log_span_elems(), sorted by slot (built on
+ *                            the host, once).  One workgroup per span; 16-byte loads where the parameter pointer is 16-byte aligned,
+ *                            scalar loads otherwise and in the tail; fp64 accumulation per thread and a fixed-order tree over the
+ *                            block; partials int64 [nspans][8] <- the row's columns over the span (column 7: the span's elements),
+ *                            plain stores.  Bit-repeatable.
+ *                            S2F_EINVAL: null pointer, nspans < 1; S2F_EALIGN: g / m / v not 16-byte, slots / partials not 8-byte.
+ *   s2f_grad_log_rows        one wave per parameter i of n combines its spans' partials IN SPAN ORDER (sums add, max of max, counts
+ *                            add; a parameter without elements gets a row of zeros) -> ring int64 [window][n][8] at row
+ *                            head[0] % window.  streak int32 [n][2]: [i][0] counts the rows in a row whose gradient was all zero
+ *                            (column 4 == column 7 > 0), [i][1] those with column 5 > 0.  head int64 [4], initialised by the caller
+ *                            to {0, -1, 0, -1}: where streak[i][0] REACHES `patience` the event head[0] * 2^32 + i is offered to
+ *                            head[1], where streak[i][1] becomes 1 to head[3]; both keep the minimum under UNSIGNED comparison
+ *                            (-1: none yet) -- the lowest parameter of the earliest row, whatever order the workgroups finish in.
+ *                            head[0] advances exactly once per launch by the ticket in head[2] (0 at entry and on exit), as in
+ *                            s2f_firing_log_append; the words of head see agent-scope atomics only.
+ *                            S2F_EINVAL: null pointer, nspans / n / window / patience < 1; S2F_EALIGN: partials / ring / head not
+ *                            8-byte, streak not 4-byte aligned.
+ * Both launches only READ g, m, v, the parameters, hyper and state; nothing allocates or synchronises: capturable behind
+ * s2f_adamw_step.  No floating-point value passes between workgroups inside a launch. */
+int s2f_grad_log_span_elems(void);
+int s2f_grad_log_partials(const int64_t* slots, const float* hyper, const int32_t* spans, int nspans, const float* g, const float* m,
+                          const float* v, const float* state, float eps, int64_t* partials, void* stream);
+int s2f_grad_log_rows(const int32_t* spans, int nspans, const int64_t* partials, int n, int64_t* ring, int window, int32_t* streak,
+                      int patience, int64_t* head, void* stream);
 
 /* ---- operand census: what a synaptic op really reads (csrc/opcensus.hip, ABI 49) -----------------------------------------------------
  * The reference's tools/cal_firing_num.py stops at firing rates per neuron (fr_rate.csv) and leaves operations and energy to a

@@ -9,6 +9,7 @@ from .backbone_sdtv3 import Multispike_norm, Spiking_vit_MetaFormerv2  # noqa: F
 from .configs import WORKLOADS, model_cfg  # noqa: F401
 from .data_preprocessor import SegDataPreProcessor, SegDataSample  # noqa: F401
 from .firing import FiringLog, FiringRead, FiringRecorder  # noqa: F401
+from .gradlog import GradLog, GradRead  # noqa: F401
 from .energy import EnergyReport, OpCensus  # noqa: F401
 from .loss import MaskFormerLoss, seg_to_instances  # noqa: F401
 from .maskformer_head import MaskFormerHead  # noqa: F401

@@ -41,6 +41,17 @@ class _Captured:
     (dist.FlatGradAllReduce) of the steps that pack into one; `optimizer`: a train.FlatAdamW captured behind the packing."""
     optimizer = log = firing = None
 
+    @property
+    def grad_log(self):
+        """the captured optimizer's gradlog.GradLog (FlatAdamW(grad_log=...)): `optimizer.step()` appends its row behind the update,
+        so the recorded stages hold its two launches without knowing of them; None: the capture is the one without them"""
+        return getattr(self.optimizer, "grad_log", None)
+
+    def _clear_grad_log(self):
+        """once the capture has ended: the warm-up passes' rows are not row 0"""
+        if self.grad_log is not None:
+            self.grad_log.clear()
+
     def _capture(self, warm, warmup, stages, context=None):
         """`warmup` calls of `warm` on a side stream (allocator pools, lazy inits, caches), then each callable of `stages`
         recorded into a hipGraph of its own -> the graphs, in that order.  `context`: a context manager factory that changes
@@ -170,6 +181,7 @@ class GraphedStep(_Captured):
         self._bind_log()
         if self.firing is not None:
             self.firing.clear()
+        self._clear_grad_log()
 
     def _eager_step(self):
         reset_net(self.model)
@@ -347,6 +359,7 @@ class GraphedHungarianStep(_Captured):
             setattr(self, name, graph)
         if self.firing is not None:
             self.firing.clear()                              # (the warm-up passes' spikes are not row 0)
+        self._clear_grad_log()
         if assign == "device":
             self.sticky.zero_()                              # (whatever the warm-up on the example inputs left is not a replay's)
             torch.cuda.synchronize()

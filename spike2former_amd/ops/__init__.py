@@ -1,6 +1,6 @@
 """torch.autograd wrappers around the C ABI, by kernel family: neuron (lif.hip), bn (bn_lif.hip), gemm (pgemm / gemm / gemm_bf16),
 conv (dwconv.hip + the k x k lowering), attention (sdsa.hip, dcnv3.hip), misc (transposes, up-sampling, mask losses), trainstate
-(trainstate.hip: the training loop's state copy and log ring; firinglog.hip: the firing log's row); `wcache` holds
+(trainstate.hip: the training loop's state copy and log ring; firinglog.hip: the firing log's row; gradlog.hip: the gradient log's row); `wcache` holds
 the cached bf16 conversions of the weights that the matrix-core products multiply by, `core`
 the shared plumbing and `config` the process-global switches that are left (ops.cfg: runtime objects, semantics, debugging aids and
 the A/B switches the tests and bench.py set).  `ops.NAME` keeps working for every function and for every switch: reading or assigning

@@ -2,7 +2,9 @@
 back, and `train_log_append`, one row of per-iteration scalars into a ring on the device (csrc/trainstate.hip); `firing_log_append`,
 one row of per-neuron firing counters into a ring of its own (csrc/firinglog.hip).  CUDA tensors run the kernels on the current
 stream; CPU tensors run the same semantics in torch (the package's CPU implementation of these three ops, as the numpy route of
-`seg_draw`), so the classes of runner.py and firing.py can be driven without a GPU."""
+`seg_draw`), so the classes of runner.py and firing.py can be driven without a GPU.  `grad_log_table` / `grad_log_append`: one row
+of per-parameter gradient, weight and update norms behind the optimizer's update (csrc/gradlog.hip), HIP only -- the kernels read
+the parameters through device pointers."""
 import torch
 
 from .core import STAT_SLOTS, _ptr, _stream, check, lib
@@ -149,4 +151,65 @@ def firing_log_append(counters, ring, silent, head, patience):
     return ring
 
 
-__all__ = ["TRAIN_LOG_MAX_TERMS", "state_table", "state_copy", "train_log_table", "train_log_append", "firing_log_append"]
+def grad_log_table(slots):
+    """-> spans int32 [nspans, 2] = {slot, first element} on the slots' device: every parameter of `slots` (int64 [n, 3] = {parameter
+    pointer, offset in the flat buffers, numel}: `FlatAdamW.slots`) in runs of at most s2f_grad_log_span_elems() elements, sorted by
+    slot -- the workgroups of s2f_grad_log_partials.  A parameter without elements gets no span.  One device-to-host and one
+    host-to-device copy: build it once, outside a capture, and again when the slot table is rebuilt."""
+    if slots.dtype != torch.int64 or slots.dim() != 2 or slots.shape[1] != 3 or not slots.is_contiguous():
+        raise ValueError("grad_log_table: slots is a contiguous int64 [n, 3]")
+    span = int(lib.s2f_grad_log_span_elems())
+    spans = [(i, s) for i, (_, _, n) in enumerate(slots.tolist()) for s in range(0, n, span)]
+    if not spans:
+        raise ValueError("grad_log_table: no parameter has an element")
+    return torch.tensor(spans, dtype=torch.int32).reshape(-1, 2).to(slots.device)
+
+
+def grad_log_append(slots, spans, hyper, state, flat, exp_avg, exp_avg_sq, partials, ring, streak, head, eps, patience):
+    """One row of per-parameter gradient figures (s2f_grad_log_partials -> s2f_grad_log_rows), behind s2f_adamw_step.  slots int64
+    [n, 3], hyper fp32 [n, 2], state fp32 [>= 5], flat / exp_avg / exp_avg_sq fp32 flat buffers of one length: FlatAdamW's, after the
+    update; spans: `grad_log_table(slots)`; partials int64 [nspans, 8] (workspace); ring int64 [window, n, 8]; streak int32 [n, 2];
+    head int64 [4] = {rows appended, first stalled parameter as row * 2^32 + i or -1, the kernel's ticket word, first parameter with
+    a non-finite gradient element or -1}.  Row head[0] % window <- per parameter {sum g^2, sum p^2, sum u^2, max |g| as doubles'
+    bits; g == 0, non-finite g, non-finite p or u, numel} (include/s2f.h "gradient log"); head[0] += 1.  Two launches on the current
+    stream, no synchronisation, capturable; everything but partials, ring, streak and head is only read.  HIP only: CPU tensors
+    raise."""
+    if slots.dtype != torch.int64 or slots.dim() != 2 or slots.shape[1] != 3 or not slots.is_contiguous():
+        raise ValueError("grad_log_append: slots is a contiguous int64 [n, 3]")
+    n = slots.shape[0]
+    if spans.dtype != torch.int32 or spans.dim() != 2 or spans.shape[1] != 2 or not spans.is_contiguous():
+        raise ValueError("grad_log_append: spans is a contiguous int32 [nspans, 2] (grad_log_table)")
+    nspans = spans.shape[0]
+    if hyper.dtype != torch.float32 or tuple(hyper.shape) != (n, 2) or not hyper.is_contiguous():
+        raise ValueError(f"grad_log_append: hyper is a contiguous fp32 [{n}, 2]")
+    if state.dtype != torch.float32 or state.dim() != 1 or state.numel() < 5 or not state.is_contiguous():
+        raise ValueError("grad_log_append: state is a contiguous fp32 [>= 5]")
+    for name, t in (("flat", flat), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != flat.numel():
+            raise ValueError(f"grad_log_append: {name} is a contiguous fp32 [{flat.numel()}]")
+    if partials.dtype != torch.int64 or tuple(partials.shape) != (nspans, 8) or not partials.is_contiguous():
+        raise ValueError(f"grad_log_append: partials is a contiguous int64 [{nspans}, 8]")
+    if ring.dtype != torch.int64 or ring.dim() != 3 or tuple(ring.shape[1:]) != (n, 8) or not ring.is_contiguous():
+        raise ValueError(f"grad_log_append: ring is a contiguous int64 [window, {n}, 8]")
+    if streak.dtype != torch.int32 or tuple(streak.shape) != (n, 2) or not streak.is_contiguous():
+        raise ValueError(f"grad_log_append: streak is a contiguous int32 [{n}, 2]")
+    if head.dtype != torch.int64 or tuple(head.shape) != (4,) or not head.is_contiguous():
+        raise ValueError("grad_log_append: head is a contiguous int64 [4]")
+    if any(t.device != slots.device for t in (spans, hyper, state, flat, exp_avg, exp_avg_sq, partials, ring, streak, head)):
+        raise RuntimeError("grad_log_append: every tensor lives on the slot table's device")
+    window, patience = ring.shape[0], int(patience)
+    if n < 1 or nspans < 1 or window < 1 or patience < 1:
+        raise ValueError(f"grad_log_append: {n} parameters in {nspans} spans, a ring of {window} rows, patience {patience}: each is "
+                         "at least 1")
+    if not slots.is_cuda:
+        raise RuntimeError("grad_log_append: the gradient log is two HIP launches over device pointers; there is no CPU route")
+    s = _stream()
+    check(lib.s2f_grad_log_partials(_ptr(slots), _ptr(hyper), _ptr(spans), nspans, _ptr(flat), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                    _ptr(state), float(eps), _ptr(partials), s), "s2f_grad_log_partials")
+    check(lib.s2f_grad_log_rows(_ptr(spans), nspans, _ptr(partials), n, _ptr(ring), window, _ptr(streak), patience, _ptr(head), s),
+          "s2f_grad_log_rows")
+    return ring
+
+
+__all__ = ["TRAIN_LOG_MAX_TERMS", "state_table", "state_copy", "train_log_table", "train_log_append", "firing_log_append",
+           "grad_log_table", "grad_log_append"]

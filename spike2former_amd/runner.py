@@ -403,7 +403,15 @@ class LoggerHook(_Hook):
     that did not fire in the last row); every neuron's mean rate and non-zero share go to {work_dir}/vis_data/firing.jsonl, one JSON
     line per log line.  The first time a neuron has stayed silent for the log's `patience` iterations, ONE warning names it and the
     iteration its streak reached the patience: a finding, not an error -- nothing is raised.  Every rank reads its own rank's
-    counters; rank 0 writes."""
+    counters; rank 0 writes.
+
+    An optimizer built with `grad_log=...` (gradlog.GradLog): ONE `GradLog.read()` more per log line.  Over the rows appended since
+    the last line (the ring holds at least `interval` of them): `grad/min` and `grad/min_name` (the parameter with the lowest mean
+    gradient norm), `grad/max_share` and `grad/max_name` (the parameter holding the largest share of sum g^2: the one the clip is
+    reacting to), `grad/update_ratio_max` and `grad/update_ratio_max_name` (the largest mean |u| / |p|), `grad/zero_share` (the share
+    of gradient elements that are exactly 0) and `grad/stalled` (parameters whose gradient was all zero in the last row); every
+    parameter's figures go to {work_dir}/vis_data/grad.jsonl, one JSON line per log line.  The first time a parameter's gradient has
+    stayed all zero for the log's `patience` iterations, ONE warning names it; nothing is raised."""
     priority = 60
     HIDDEN = ("clip_coef",)
 
@@ -421,8 +429,10 @@ class LoggerHook(_Hook):
             raise ValueError(f"LoggerHook(window_size={self.window_size}) over a TrainLog of {loop.log.window} rows")
         if loop.firing is not None and loop.firing.window < self.interval:
             raise ValueError(f"LoggerHook(interval={self.interval}) over a FiringLog of {loop.firing.window} rows")
+        if getattr(loop, "grad_log", None) is not None and loop.grad_log.window < self.interval:
+            raise ValueError(f"LoggerHook(interval={self.interval}) over a GradLog of {loop.grad_log.window} rows")
         self._clock, self._last = time.perf_counter(), loop.iter
-        self._dead_seen = False
+        self._dead_seen = self._stalled_seen = False
 
     def _firing(self, loop, n, record):
         """the rows since the last line -> the record's firing/ keys and one line of firing.jsonl; the dead-neuron warning"""
@@ -448,6 +458,35 @@ class LoggerHook(_Hook):
             row, name = read.first_dead
             logger.warning(f"neuron {name} has not fired for {fl.patience} iterations, up to iteration {fl.base + row + 1}")
 
+    def _grad(self, loop, n, record):
+        """the gradient log's rows since the last line -> the record's grad/ keys and one line of grad.jsonl; the stalled warning"""
+        gl = loop.grad_log
+        read = gl.read()
+        k = len(read.cols)
+        if k > 0:
+            sq = read.grad_sq.sum(0)
+            norm, ratio = read.grad_norm.mean(0), read.update_ratio.mean(0)
+            low, top, far = int(np.argmin(norm)), int(np.argmax(sq)), int(np.argmax(ratio))
+            elems = float(read.numel.sum())
+            record["grad/min"], record["grad/min_name"] = float(norm[low]), read.names[low]
+            record["grad/max_share"], record["grad/max_name"] = float(sq[top] / sq.sum()) if sq.sum() > 0 else 0.0, read.names[top]
+            record["grad/update_ratio_max"], record["grad/update_ratio_max_name"] = float(ratio[far]), read.names[far]
+            record["grad/zero_share"] = float(read.cols[:, :, 4].sum()) / elems if elems else 0.0
+            record["grad/stalled"] = int((read.streak[:, 0] >= 1).sum())
+            if loop.work_dir is not None and loop.rank == 0:
+                path = os.path.join(loop.work_dir, "vis_data", "grad.jsonl")
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                per = dict(grad_norm=norm, weight_norm=read.weight_norm.mean(0), update_ratio=ratio, grad_max=read.grad_max.max(0),
+                           zero_share=read.zero_share.mean(0))
+                with open(path, "a") as f:
+                    f.write(json.dumps(dict(iter=n, rows=k, **{key: {name: float(v) for name, v in zip(read.names, vals)}
+                                                               for key, vals in per.items()})) + "\n")
+        if read.first_stalled is not None and not self._stalled_seen:
+            self._stalled_seen = True
+            row, name = read.first_stalled
+            logger.warning(f"parameter {name} has had an all-zero gradient for {gl.patience} iterations, up to iteration "
+                           f"{gl.base + row + 1}")
+
     def _emit(self, loop, record, line):
         logger.info(line)
         if loop.work_dir is not None and loop.rank == 0:
@@ -471,6 +510,8 @@ class LoggerHook(_Hook):
                 record[name] = float(np.mean(np.ascontiguousarray(rows[:, j])))          # fp32, in the rows' order
         if loop.firing is not None:
             self._firing(loop, n, record)
+        if getattr(loop, "grad_log", None) is not None:
+            self._grad(loop, n, record)
         self._clock, self._last = now, n
         record.update(iter=n, step=n)
         eta = str(datetime.timedelta(seconds=int(record["eta"])))
@@ -609,6 +650,7 @@ class TrainLoop:
         self.rank, self.world = _rank_world()
         self.log = getattr(step, "log", None)
         self.firing = getattr(step, "firing", None)          # a firing.FiringLog the step appends a row to per replay
+        self.grad_log = getattr(optimizer, "grad_log", None)          # a gradlog.GradLog `optimizer.step()` appends a row to
         # a step that does not hold the optimizer (world size > 1: the all-reduce lies between the replay and the update) is
         # followed by `step.red.reduce()` and `optimizer.step()` here, and the log's row by an eager append behind them
         self.eager_update = hasattr(step, "red") and getattr(step, "optimizer", None) is None
@@ -651,8 +693,12 @@ class TrainLoop:
             if row < bad <= row + len(read.rows):
                 vals = read.rows[bad - 1 - row]
                 seen = ": " + ", ".join(f"{k} = {v}" for k, v in zip(read.names, vals) if not np.isfinite(v))
+            where = ""
+            first = self.grad_log.read(consume=False).first_nonfinite if self.grad_log is not None else None
+            if first is not None:          # the tensor it started in: the lowest parameter of the first row with a non-finite gradient
+                where = f"; the first non-finite gradient is in {first[1]}, iteration {self.grad_log.base + first[0] + 1}"
             raise FloatingPointError(f"non-finite training terms first at iteration {bad}{seen}; checkpoints up to iteration "
-                                     f"{bad - 1} predate it")
+                                     f"{bad - 1} predate it{where}")
         self._read = (self.iter, read)
         return read
 
@@ -689,6 +735,8 @@ class TrainLoop:
                 self.log.base = start - self.log.read().count          # row 0 of a fresh log is iteration start + 1
             if self.firing is not None:          # (the ring and the streaks are in no checkpoint: a resumed run starts them afresh)
                 self.firing.base = start - self.firing.read().count
+            if self.grad_log is not None:        # (neither is the gradient log's ring)
+                self.grad_log.base = start - self.grad_log.read(consume=False).count
             self._call("before_run")
             batches = _cycle(self.batches, start)
             out = (self.step.static_in, self.step.static_seg)

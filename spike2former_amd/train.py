@@ -74,10 +74,15 @@ class FlatAdamW:
     are flat buffers of the same layout, parameters are addressed through a pointer table (they stay where their modules own
     them).  `param_groups` is a list of {'lr', 'weight_decay', 'name'} dictionaries, one per parameter, that a scheduler
     (LinearThenPoly) may rewrite between iterations; the table goes to the device at the start of `step()`.
-    Build it AFTER `grad_buffer.compact()`: the tables follow the buffer's layout (checked at every step)."""
+    Build it AFTER `grad_buffer.compact()`: the tables follow the buffer's layout (checked at every step).
+
+    `grad_log`: None (default: the step is the three launches above, nothing else is allocated or launched), True or a dictionary of
+    `gradlog.GradLog` arguments (`dict(window=50, patience=200)`): `step()` appends one row of per-parameter gradient, weight and
+    update norms directly behind s2f_adamw_step, two launches more that only read (`self.grad_log`; `attach_grad_log` takes a log
+    built by the caller)."""
 
     def __init__(self, model, grad_buffer, lr=0.001, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.005, paramwise_cfg=None,
-                 clip_grad=None):
+                 clip_grad=None, grad_log=None):
         from ._lib import lib
         self.red, self.betas, self.eps = grad_buffer, (float(betas[0]), float(betas[1])), float(eps)
         self.max_norm = float((clip_grad or {}).get("max_norm", 0.0)) if clip_grad else 0.0
@@ -99,6 +104,18 @@ class FlatAdamW:
         self._hyper_events, self._hyper_turn, self._hyper_last = [None, None], 0, None
         self.hyper = torch.zeros(len(self.params), 2, dtype=torch.float32, device=dev)
         self._build_tables()
+        self.grad_log = None
+        if grad_log is not None and grad_log is not False:
+            from .gradlog import GradLog
+            self.attach_grad_log(GradLog(self, **({} if grad_log is True else dict(grad_log))))
+
+    def attach_grad_log(self, log):
+        """`log`: a gradlog.GradLog over THIS optimizer (None detaches); from the next `step()` on every update is followed by one row.
+        A step that was captured before holds the launches it was recorded with: attach before building the captured step."""
+        if log is not None and log.optimizer is not self:
+            raise ValueError("FlatAdamW.attach_grad_log: the log was built over another optimizer")
+        self.grad_log = log
+        return log
 
     def _build_tables(self):
         from ._lib import lib
@@ -161,6 +178,8 @@ class FlatAdamW:
         check(lib.s2f_adamw_step(self.slots.data_ptr(), self.hyper.data_ptr(), self.chunks.data_ptr(), self.chunks.shape[0],
                                  flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.state.data_ptr(),
                                  b1, b2, self.eps, s), "s2f_adamw_step")
+        if self.grad_log is not None:
+            self.grad_log.append()
         # the kernels wrote the parameters behind autograd's back: bump their version counters so that every cache keyed on a
         # weight's version (the bf16 term splits / packs of ops.gemm) re-converts in eager use; a captured step re-converts inside
         # the graph anyway (ops.resplit_all)
@@ -182,6 +201,8 @@ class FlatAdamW:
         self.param_groups = [groups[id(p)] for p in self.params]
         self._hyper_last = None                      # the table's row order changed with the buffer's layout: upload again
         self._build_tables()
+        if self.grad_log is not None:
+            self.grad_log.rebuild()                  # (its span table follows the slot table; its rows start afresh)
 
     @property
     def grad_norm(self):
