@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 50
+#define S2F_ABI_VERSION 51
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -955,10 +955,27 @@ int s2f_dcnv3_bwd_cm(const float* input, const float* offset, const float* mask,
  *                              = {slot, first element} covering every slot in runs of s2f_adamw_chunk_elems();
  *                              g' = g * state[0]; p *= 1 - lr wd; m += (g' - m)(1 - beta1); v = beta2 v + (1 - beta2) g'^2;
  *                              p -= lr / state[2] * m / (sqrt(v) / state[3] + eps)      (torch/optim/adamw.py, single-tensor form)
- * All tables are DEVICE memory; nothing synchronises, so the three launches can be captured behind the step's hipGraph. */
+ * All tables are DEVICE memory; nothing synchronises, so the three launches can be captured behind the step's hipGraph.
+ *
+ * Gradient accumulation over the same buffer (mmengine OptimWrapper(accumulative_counts = k); ABI 51):
+ *   s2f_grad_accumulate        out[i] = fl(acc[i] + fl(scale * g[i])), or fl(scale * g[i]) with acc == NULL: two fp32 roundings, never
+ *                              contracted into an fma; non-finite values propagate.  `out` may be `g` or `acc` (each element is read and
+ *                              written by one thread); any other overlap is the caller's error.  16-byte accesses on whole groups of
+ *                              four, scalar ones in the tail; one workgroup per run of 16 384 elements, as s2f_grad_sqnorm.
+ *                              partials: NULL, or s2f_grad_sqnorm_parts(n) doubles: partials[i] = sum of g^2 of the INPUT g over run
+ *                              i, bit-identical to what s2f_grad_sqnorm writes for that buffer (plain stores).  n == 0: S2F_OK, no
+ *                              launch.  S2F_EINVAL: g or out NULL, n < 0; S2F_EALIGN: g / acc / out not 16-byte aligned, partials not
+ *                              8-byte aligned.
+ *   s2f_grad_accum_stats       ONE workgroup of 256 threads.  micro double [rows][nparts]; every row and accum_parts[nparts] is summed
+ *                              in s2f_adamw_prepare's fixed order, the row sums are added in ascending row order.
+ *                              stats[0] = (float)(sum of the row sums / rows), [1] = (float)(sum of accum_parts), [2] = rows, [3] = 0.
+ *                              Bit-repeatable.  S2F_EINVAL: null pointer, rows < 1, nparts < 1.
+ * Neither allocates or synchronises: both can be captured. */
 int64_t s2f_grad_sqnorm_parts(int64_t n);
 int s2f_grad_sqnorm(const float* g, int64_t n, double* partials, void* stream);
 int s2f_adamw_prepare(const double* partials, int nparts, float max_norm, double beta1, double beta2, float* state, void* stream);
+int s2f_grad_accumulate(const float* g, const float* acc, float* out, int64_t n, float scale, double* partials, void* stream);
+int s2f_grad_accum_stats(const double* micro, int rows, const double* accum_parts, int nparts, float* stats, void* stream);
 int s2f_adamw_chunk_elems(void);
 int s2f_adamw_step(const int64_t* slots, const float* hyper, const int32_t* chunks, int nchunks, const float* g, float* m, float* v,
                    const float* state, double beta1, double beta2, float eps, void* stream);

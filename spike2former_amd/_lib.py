@@ -157,6 +157,8 @@ SIGNATURES = {
     "s2f_grad_sqnorm_parts": (_i64, [_i64]),
     "s2f_grad_sqnorm": (_i, [_p, _i64, _p, _p]),
     "s2f_adamw_prepare": (_i, [_p, _i, _f, ctypes.c_double, ctypes.c_double, _p, _p]),
+    "s2f_grad_accumulate": (_i, [_p, _p, _p, _i64, _f, _p, _p]),
+    "s2f_grad_accum_stats": (_i, [_p, _i, _p, _i, _p, _p]),
     "s2f_adamw_chunk_elems": (_i, []),
     "s2f_sum_all_parts": (_i64, [_i64]),
     "s2f_sum_all": (_i, [_p, _i64, _f, _p, _p, _p]),

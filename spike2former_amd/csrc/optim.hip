@@ -12,6 +12,10 @@
 //                                   g' = g * clip;  p *= 1 - lr * wd;  m = m + (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g'^2;
 //                                   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
 //                               -- torch.optim.AdamW's single-tensor expressions in their order (adamw.py `_single_tensor_adamw`).
+// Gradient accumulation (mmengine OptimWrapper's accumulative_counts) lives on the same flat buffer:
+//   s2f_grad_accumulate         out = acc + scale * g (or scale * g), one streaming launch per micro-batch, which also hands back the
+//                               micro-batch's g^2 partials -- the bits s2f_grad_sqnorm would write (one shared body)
+//   s2f_grad_accum_stats        ONE workgroup: {mean micro-batch sum g^2, sum g^2 of the accumulated gradient} for the noise-scale log
 // Parameters are addressed through a pointer table (they stay where the modules own them: sibling weights that the attention
 // blocks keep adjacent in one storage, ops.flatten_together, are not moved); gradients and both moments are flat buffers with
 // the layout of dist.FlatGradAllReduce (16-byte-aligned slots, zero pads).  HBM-bound: 28 B per parameter.
@@ -24,7 +28,12 @@ namespace {
 constexpr int kNormBlock = 256;
 constexpr int kNormElemsPerBlock = kNormBlock * 4 * 16;          // 16 float4 per thread
 
-__global__ __launch_bounds__(kNormBlock) void grad_sqnorm_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
+// The part of s2f_grad_sqnorm that s2f_grad_accumulate shares, so that both write the same bits for the same buffer: one workgroup's
+// run of kNormElemsPerBlock elements, 16 float4 per thread, the squares added into ONE fp32 accumulator per thread in element order
+// (whole groups of four by 16-byte loads, the ragged end of the buffer element by element).  `sink(e, v)` / `sink.tail(k, x)` see
+// every value once, behind the accumulation: the thread that read an element is the one that may write it.
+template <class Sink>
+__device__ __forceinline__ float norm_run(const float* g, int64_t n, Sink sink) {
   const int64_t base = (int64_t)blockIdx.x * kNormElemsPerBlock;
   float acc = 0.f;
 #pragma unroll 4
@@ -36,10 +45,20 @@ __global__ __launch_bounds__(kNormBlock) void grad_sqnorm_kernel(const float* __
       acc += v.y * v.y;
       acc += v.z * v.z;
       acc += v.w * v.w;
+      sink(e, v);
     } else {
-      for (int64_t k = e; k < n && k < e + 4; ++k) acc += g[k] * g[k];
+      for (int64_t k = e; k < n && k < e + 4; ++k) {
+        const float x = g[k];
+        acc += x * x;
+        sink.tail(k, x);
+      }
     }
   }
+  return acc;
+}
+
+// ... and the fp64 tree over the workgroup's 256 accumulators -> part[blockIdx.x] (a plain store)
+__device__ __forceinline__ void norm_tree(float acc, double* __restrict__ part) {
   __shared__ double red[kNormBlock];
   red[threadIdx.x] = (double)acc;
   __syncthreads();
@@ -50,11 +69,46 @@ __global__ __launch_bounds__(kNormBlock) void grad_sqnorm_kernel(const float* __
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 
-// state[0] clip coefficient, [1] gradient norm, [2] 1 - beta1^t, [3] sqrt(1 - beta2^t), [4] t (after the increment)
-__global__ __launch_bounds__(256) void adamw_prepare_kernel(const double* __restrict__ part, int nparts, float max_norm, double beta1,
-                                                            double beta2, float* __restrict__ state) {
-  __shared__ double red[256];
-  // fixed order: thread i owns the contiguous run [i * per, (i + 1) * per) of partials, then a tree over the 256 run sums
+struct NoSink {
+  __device__ __forceinline__ void operator()(int64_t, const float4&) const {}
+  __device__ __forceinline__ void tail(int64_t, float) const {}
+};
+
+__global__ __launch_bounds__(kNormBlock) void grad_sqnorm_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
+  norm_tree(norm_run(g, n, NoSink()), part);
+}
+
+// out = fl(acc + fl(scale * g)) (kAdd) or fl(scale * g): two fp32 roundings, never contracted (the pragma above).  `out` may be `g` or
+// `acc` (no __restrict__ on the three): every element is read and written by one thread, the read first.
+template <bool kAdd>
+struct AccumSink {
+  const float* acc;
+  float* out;
+  float scale;
+  __device__ __forceinline__ void operator()(int64_t e, const float4& v) const {
+    float4 r = make_float4(scale * v.x, scale * v.y, scale * v.z, scale * v.w);
+    if (kAdd) {
+      const float4 a = *reinterpret_cast<const float4*>(acc + e);
+      r.x = a.x + r.x, r.y = a.y + r.y, r.z = a.z + r.z, r.w = a.w + r.w;
+    }
+    *reinterpret_cast<float4*>(out + e) = r;
+  }
+  __device__ __forceinline__ void tail(int64_t k, float x) const {
+    const float r = scale * x;
+    out[k] = kAdd ? acc[k] + r : r;
+  }
+};
+
+template <bool kAdd>
+__global__ __launch_bounds__(kNormBlock) void grad_accumulate_kernel(const float* g, const float* acc, float* out, int64_t n, float scale,
+                                                                     double* __restrict__ part) {
+  const float sq = norm_run(g, n, AccumSink<kAdd>{acc, out, scale});
+  if (part) norm_tree(sq, part);          // (uniform over the grid: a kernel argument)
+}
+
+// fixed order: thread i owns the contiguous run [i * per, (i + 1) * per) of partials, then a tree over the 256 run sums
+// -> the sum, in every thread; `red` (256 doubles of shared memory) is free again on return
+__device__ __forceinline__ double ordered_sum256(const double* __restrict__ part, int nparts, double* red) {
   const int per = (nparts + 255) / 256;
   double a = 0.0;
   for (int k = threadIdx.x * per; k < nparts && k < ((int)threadIdx.x + 1) * per; ++k) a += part[k];
@@ -64,8 +118,18 @@ __global__ __launch_bounds__(256) void adamw_prepare_kernel(const double* __rest
     if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
+  const double total = red[0];
+  __syncthreads();
+  return total;
+}
+
+// state[0] clip coefficient, [1] gradient norm, [2] 1 - beta1^t, [3] sqrt(1 - beta2^t), [4] t (after the increment)
+__global__ __launch_bounds__(256) void adamw_prepare_kernel(const double* __restrict__ part, int nparts, float max_norm, double beta1,
+                                                            double beta2, float* __restrict__ state) {
+  __shared__ double red[256];
+  const double total = ordered_sum256(part, nparts, red);
   if (threadIdx.x == 0) {
-    const double norm = sqrt(red[0]);
+    const double norm = sqrt(total);
     // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
     double coef = max_norm > 0.f ? (double)max_norm / (norm + 1e-6) : 1.0;
     if (coef > 1.0) coef = 1.0;
@@ -75,6 +139,21 @@ __global__ __launch_bounds__(256) void adamw_prepare_kernel(const double* __rest
     state[2] = (float)(1.0 - pow(beta1, t));
     state[3] = (float)sqrt(1.0 - pow(beta2, t));
     state[4] = (float)t;
+  }
+}
+
+// stats[0] mean over the group's micro-batches of sum g^2, [1] sum g^2 of the accumulated gradient, [2] micro-batches, [3] 0
+__global__ __launch_bounds__(256) void grad_accum_stats_kernel(const double* __restrict__ micro, int rows, const double* __restrict__ accum,
+                                                               int nparts, float* __restrict__ stats) {
+  __shared__ double red[256];
+  double m = 0.0;
+  for (int r = 0; r < rows; ++r) m += ordered_sum256(micro + (int64_t)r * nparts, nparts, red);          // ascending rows
+  const double a = ordered_sum256(accum, nparts, red);
+  if (threadIdx.x == 0) {
+    stats[0] = (float)(m / (double)rows);
+    stats[1] = (float)a;
+    stats[2] = (float)rows;
+    stats[3] = 0.f;
   }
 }
 
@@ -155,6 +234,30 @@ extern "C" int s2f_grad_sqnorm(const float* g, int64_t n, double* partials, void
   S2F_REQUIRE(blocks < (1ll << 31), S2F_EINVAL, "s2f_grad_sqnorm: too large");
   hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)blocks), dim3(kNormBlock), 0, (hipStream_t)stream, g, n, partials);
   return s2f_check_launch("s2f_grad_sqnorm");
+}
+
+extern "C" int s2f_grad_accumulate(const float* g, const float* acc, float* out, int64_t n, float scale, double* partials, void* stream) {
+  S2F_REQUIRE(g && out && n >= 0, S2F_EINVAL, "s2f_grad_accumulate: null pointer or n < 0");
+  S2F_REQUIRE(s2f_aligned16(g) && s2f_aligned16(out) && (!acc || s2f_aligned16(acc)), S2F_EALIGN,
+              "s2f_grad_accumulate: g, acc and out must be 16-byte aligned");
+  S2F_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7u) == 0, S2F_EALIGN, "s2f_grad_accumulate: partials must be 8-byte aligned");
+  if (n == 0) return S2F_OK;
+  const int64_t blocks = s2f_grad_sqnorm_parts(n);
+  S2F_REQUIRE(blocks < (1ll << 31), S2F_EINVAL, "s2f_grad_accumulate: too large");
+  if (acc)
+    hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3((unsigned)blocks), dim3(kNormBlock), 0, (hipStream_t)stream, g, acc, out, n, scale,
+                       partials);
+  else
+    hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3((unsigned)blocks), dim3(kNormBlock), 0, (hipStream_t)stream, g, acc, out, n, scale,
+                       partials);
+  return s2f_check_launch("s2f_grad_accumulate");
+}
+
+extern "C" int s2f_grad_accum_stats(const double* micro, int rows, const double* accum_parts, int nparts, float* stats, void* stream) {
+  S2F_REQUIRE(micro && accum_parts && stats, S2F_EINVAL, "s2f_grad_accum_stats: null pointer");
+  S2F_REQUIRE(rows >= 1 && nparts >= 1, S2F_EINVAL, "s2f_grad_accum_stats: rows and nparts are at least 1");
+  hipLaunchKernelGGL(grad_accum_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, micro, rows, accum_parts, nparts, stats);
+  return s2f_check_launch("s2f_grad_accum_stats");
 }
 
 extern "C" int s2f_adamw_prepare(const double* partials, int nparts, float max_norm, double beta1, double beta2, float* state,

@@ -36,6 +36,11 @@ def _process_group():
     return dist.is_available() and dist.is_initialized()
 
 
+def _world_size():
+    import torch.distributed as dist
+    return dist.get_world_size() if _process_group() else 1
+
+
 class _Captured:
     """A step with static input `static_in`, recorded as one hipGraph per stage.  `red`: the flat gradient buffer
     (dist.FlatGradAllReduce) of the steps that pack into one; `optimizer`: a train.FlatAdamW captured behind the packing."""
@@ -46,6 +51,33 @@ class _Captured:
         """the captured optimizer's gradlog.GradLog (FlatAdamW(grad_log=...)): `optimizer.step()` appends its row behind the update,
         so the recorded stages hold its two launches without knowing of them; None: the capture is the one without them"""
         return getattr(self.optimizer, "grad_log", None)
+
+    @property
+    def accum(self):
+        """the optimizer's train.GradAccum (FlatAdamW(accumulative_counts=k), k > 1) or None.  With one, the update is NOT part of
+        the capture: the recorded stages end with the packing (plus the status and firing launches), and every call runs
+        `_accumulate()` eagerly behind the replay, on the same stream."""
+        return getattr(self.optimizer, "accum", None)
+
+    def _update_in_graph(self):
+        return self.optimizer is not None and self.accum is None
+
+    def _accumulate(self):
+        """behind the last replay of a call, with an accumulating optimizer: `accum.add()` on every call; at world size 1 also, on the
+        iteration that closes a group, `optimizer.step()` and `accum.finish()`, and on every call the log's row -- the loss terms
+        of THIS iteration, and grad_norm, clip_coef, grad_sq_micro, grad_sq_accum as the last update left them: rows of iterations
+        without an update repeat the last update's four values (zeros before the first), as grad_norm does in mmengine's log.
+        At world size > 1 the step stops behind `add()`: the all-reduce lies before the update, the caller (runner.TrainLoop) runs
+        reduce, update, `finish()` and the append.  Nothing here waits for the GPU.  -> whether the weights were updated."""
+        last = self.accum.add()
+        if _world_size() > 1:
+            return False
+        if last:
+            self.optimizer.step(sync_hyper=False)          # (`_begin` uploaded the table; eager: bumps the weight versions itself)
+            self.accum.finish()
+        if self.log is not None:
+            self.log.append()
+        return last
 
     def _clear_grad_log(self):
         """once the capture has ended: the warm-up passes' rows are not row 0"""
@@ -101,11 +133,14 @@ class _Captured:
             self.optimizer.sync_hyper()
 
     def _end(self):
-        """After the last replay of a step.  A replayed update changed every weight after this replay's own re-split ran (at
+        """After the last replay of a step (with an accumulating optimizer: `_accumulate()` takes its place, and the versions are
+        bumped only behind an update).  A replayed update changed every weight after this replay's own re-split ran (at
         its START): the version-keyed conversion caches now hold the terms of the weights BEFORE the update under unchanged
         version counters -- an eager forward (validation, predict(), export) would multiply by one-step-stale bf16 terms.
         Bump the versions."""
-        if self.optimizer is not None:
+        if self.accum is not None:
+            self._accumulate()          # (its `optimizer.step()` runs eagerly and bumps the versions itself, behind an update only)
+        elif self.optimizer is not None:
             self.optimizer.mark_updated()
 
     def _record_log(self, terms):
@@ -114,17 +149,19 @@ class _Captured:
         reads the scalars through a pointer table that `_bind_log` fills once the capture has ended."""
         if self.optimizer is not None:
             terms = {**terms, "grad_norm": self.optimizer.grad_norm, "clip_coef": self.optimizer.clip_coef}
+        if self.accum is not None:
+            terms = {**terms, "grad_sq_micro": self.accum.stats[0:1], "grad_sq_accum": self.accum.stats[1:2]}
         self.log_terms = terms
         # at world size > 1 the all-reduce and the update follow the replay eagerly: the row is appended behind them, by the caller
-        # (runner.TrainLoop), who also binds the optimizer's terms
-        import torch.distributed as dist
-        self.log_captured = not (_process_group() and dist.get_world_size() > 1)
+        # (runner.TrainLoop), who also binds the optimizer's terms.  An accumulating optimizer's update is eager at every world
+        # size, and the row with it (`_accumulate`).
+        self.log_captured = _world_size() == 1 and self.accum is None
         if self.log_captured:
             self.log.declare(terms.keys())
             self.log.append()
 
     def _bind_log(self):
-        if self.log is not None and self.log_captured:
+        if self.log is not None and (self.log_captured or (self.accum is not None and _world_size() == 1)):
             self.log.bind(self.log_terms)
 
     def _watch_firing(self, forward):
@@ -159,7 +196,10 @@ class GraphedStep(_Captured):
     the gradient packing, so one replay is one training ITERATION (single process; with N > 1 the all-reduce sits between the step
     and the update, which the caller then runs eagerly: `step(); grad_buffer.reduce(); optimizer.step()`).  `log` (runner.TrainLog):
     every replay appends {loss, grad_norm, clip_coef} to it, at the end of the graph; None: the capture holds no such launch.
-    `firing` (firing.FiringLog): see GraphedHungarianStep."""
+    `firing` (firing.FiringLog): see GraphedHungarianStep.
+    An optimizer built with `accumulative_counts=k` (its `accum` is set): the capture ends with the packing, and `__call__` runs the
+    accumulation, every k-th call the update, and the log's row eagerly behind the replay (`_Captured._accumulate`);
+    `log_captured` is False."""
 
     def __init__(self, model, loss_fn, example_input, grad_buffer=None, warmup=3, optimizer=None, log=None, firing=None):
         self.model, self.loss_fn, self.log, self.firing = model, loss_fn, log, firing
@@ -196,7 +236,7 @@ class GraphedStep(_Captured):
         ops.wgrad_join()                  # side-stream weight gradients (ops.WGRAD_STREAM) rejoin before packing
         if self.grad_buffer is not None:
             self.grad_buffer.gather()
-        if self.optimizer is not None:
+        if self._update_in_graph():
             self.optimizer.step(sync_hyper=False)
         return loss.detach()
 
@@ -284,7 +324,8 @@ class GraphedHungarianStep(_Captured):
 
     `firing` (firing.FiringLog over `model`): every neuron counts its spikes into the log's counters, and the last graph ends with
     one launch that turns them into a row per replay -- per-neuron firing rates of EVERY iteration, and the first neuron that stays
-    silent for the log's `patience` iterations, read by runner.LoggerHook with the losses.  Counters change the launch structure of
+    silent for the log's `patience` iterations, read by runner.LoggerHook with the losses.  (With an optimizer whose `accum` is
+    set -- FlatAdamW(accumulative_counts=k) -- the update and the log's row are not captured: see GraphedStep.)  Counters change the launch structure of
     the step (the memoised, pre-fired and fused-neuron routes step aside for a neuron that has them); None: nothing is attached,
     allocated or launched, the capture is the one without it."""
 
@@ -340,7 +381,7 @@ class GraphedHungarianStep(_Captured):
             losses = self._losses(self.outs)
             total = sum(losses.values())
             self.red.pack(self._grads(total))
-            if self.optimizer is not None:
+            if self._update_in_graph():
                 self.optimizer.step(sync_hyper=False)
             self.losses = {k: v.detach() for k, v in losses.items()}
             if self.log is not None:          # behind the update: grad_norm is this iteration's

@@ -56,6 +56,19 @@ def _rank_world():
     return 0, 1
 
 
+def noise_scale(micro_sq, accum_sq, small, big):
+    """The simple gradient-noise-scale estimate from two batch sizes (McCandlish et al. 2018, "An Empirical Model of Large-Batch
+    Training", appendix A.1): `micro_sq` = mean |g|^2 at batch `small`, `accum_sq` = mean |g|^2 at batch `big` ->
+        G2 = (big * accum_sq - small * micro_sq) / (big - small)          (unbiased for |G|^2, the true gradient's)
+        S  = (micro_sq - accum_sq) / (1 / small - 1 / big)                (unbiased for the trace of the per-example covariance)
+    -> (S / G2, G2, S): the noise scale in the unit of `small` and `big` (images); S / G2 is None where G2 <= 0 (the estimate of
+    |G|^2 is itself noise then).  The ratio is taken of means, not as a mean of ratios."""
+    small, big = float(small), float(big)
+    g2 = (big * accum_sq - small * micro_sq) / (big - small)
+    s = (micro_sq - accum_sq) / (1.0 / small - 1.0 / big)
+    return (s / g2 if g2 > 0 else None), g2, s
+
+
 class TrainLog:
     """A ring of the last `window` iterations' scalars on the device.  `terms`: ordered {name: one-element fp32 tensor}, static
     tensors of a captured step (its losses, their sum, the optimizer's grad_norm and clip_coef).  `append()` is one launch
@@ -411,9 +424,17 @@ class LoggerHook(_Hook):
     reacting to), `grad/update_ratio_max` and `grad/update_ratio_max_name` (the largest mean |u| / |p|), `grad/zero_share` (the share
     of gradient elements that are exactly 0) and `grad/stalled` (parameters whose gradient was all zero in the last row); every
     parameter's figures go to {work_dir}/vis_data/grad.jsonl, one JSON line per log line.  The first time a parameter's gradient has
-    stayed all zero for the log's `patience` iterations, ONE warning names it; nothing is raised."""
+    stayed all zero for the log's `patience` iterations, ONE warning names it; nothing is raised.
+
+    An optimizer built with `accumulative_counts=k`: the gradient log's rows count UPDATES (the warning and grad.jsonl name the
+    iteration of the update), and the line carries `grad/accum` = k and `grad/noise_scale`, in images: `noise_scale()` of the means
+    of the step's two hidden terms `grad_sq_micro` (mean |g|^2 of the group's micro-batches, b images each) and `grad_sq_accum`
+    (|g|^2 of the accumulated and all-reduced gradient, k b W images) over the rows of UPDATE iterations since the last line that
+    the TrainLog's ring still holds; omitted where no such row is in reach or the estimate of |G|^2 is not positive.  A diagnostic
+    without a counterpart in the reference, and approximate: train-mode BatchNorm and the matching couple the images of a
+    micro-batch; at world size > 1 the micro-batch term is this rank's."""
     priority = 60
-    HIDDEN = ("clip_coef",)
+    HIDDEN = ("clip_coef", "grad_sq_micro", "grad_sq_accum")
 
     def __init__(self, interval=50, window_size=10, log_metric_by_epoch=False, **unused):
         if log_metric_by_epoch:
@@ -463,6 +484,8 @@ class LoggerHook(_Hook):
         gl = loop.grad_log
         read = gl.read()
         k = len(read.cols)
+        if loop.accum is not None:          # the rows count updates: the line is named after the last update it holds
+            n = loop.update_iteration(gl.base + read.count)
         if k > 0:
             sq = read.grad_sq.sum(0)
             norm, ratio = read.grad_norm.mean(0), read.update_ratio.mean(0)
@@ -485,7 +508,24 @@ class LoggerHook(_Hook):
             self._stalled_seen = True
             row, name = read.first_stalled
             logger.warning(f"parameter {name} has had an all-zero gradient for {gl.patience} iterations, up to iteration "
-                           f"{gl.base + row + 1}")
+                           f"{loop.update_iteration(gl.base + row + 1)}")
+
+    def _accum(self, loop, n, read, record):
+        """grad/accum and grad/noise_scale (see the class); `read`: the TrainLog as of iteration n, whose last row is iteration n"""
+        counts = loop.accum.counts
+        record["grad/accum"] = counts
+        if "grad_sq_micro" not in read.names or "grad_sq_accum" not in read.names:
+            return
+        first = n - len(read.rows) + 1          # the iteration (from 1) of the ring's oldest row
+        at = [i for i in range(len(read.rows)) if first + i > self._last and ((first + i) % counts == 0 or first + i == loop.max_iters)]
+        if not at:
+            return
+        m = float(np.mean(read.rows[at, read.names.index("grad_sq_micro")].astype(np.float64)))
+        big = float(np.mean(read.rows[at, read.names.index("grad_sq_accum")].astype(np.float64)))
+        b = int(loop.step.static_in.shape[0])
+        ratio = noise_scale(m, big, b, counts * b * loop.world)[0]
+        if ratio is not None:
+            record["grad/noise_scale"] = float(ratio)
 
     def _emit(self, loop, record, line):
         logger.info(line)
@@ -512,6 +552,8 @@ class LoggerHook(_Hook):
             self._firing(loop, n, record)
         if getattr(loop, "grad_log", None) is not None:
             self._grad(loop, n, record)
+        if getattr(loop, "accum", None) is not None:
+            self._accum(loop, n, read, record)
         self._clock, self._last = now, n
         record.update(iter=n, step=n)
         eta = str(datetime.timedelta(seconds=int(record["eta"])))
@@ -559,6 +601,11 @@ class CheckpointHook(_Hook):
     def before_run(self, loop):
         if loop.work_dir is None:
             raise ValueError("CheckpointHook needs the loop's work_dir")
+        accum = getattr(loop, "accum", None)
+        if accum is not None and self.interval > 0 and self.interval % accum.counts:
+            # a checkpoint inside a group would drop the accumulator (it is in no file); the one after the last iteration is always
+            # on a boundary: the last iteration closes its group
+            raise ValueError(f"CheckpointHook(interval={self.interval}) is no multiple of accumulative_counts={accum.counts}")
         best = (loop.resumed or {}).get("best") or {}
         if self.save_best is not None and best.get("key") == self.save_best:
             self.best_score, self.best_path = best.get("score"), best.get("path")
@@ -634,7 +681,11 @@ class TrainLoop:
     """mmengine's IterBasedTrainLoop for a captured step: per iteration the next (images, segs) of `batches` (decoded uint8
     pictures and annotations; an iterable that is restarted when exhausted) -> `augment(images, segs, out=(step.static_in,
     step.static_seg))` -> `step()` (at world size > 1, where the step holds no optimizer: -> `step.red.reduce()` ->
-    `optimizer.step()` -> `log.append()`) -> `scheduler.step()` -> the hooks.  Nothing in an iteration reads the device; the log,
+    `optimizer.step()` -> `log.append()`) -> `scheduler.step()` -> the hooks.  With an optimizer built with `accumulative_counts=k`
+    (handed to the step as well) the step accumulates, and updates every k-th iteration and after the last (train.GradAccum); at
+    world size > 1 reduce, update and `accum.finish()` run here, only on the iterations that close a group: ONE all-reduce per k
+    iterations.  The scheduler steps every iteration, as mmengine's ParamSchedulerHook does.  A run resumed inside a group raises
+    (the partial group's gradients are in no file; mmengine only warns).  Nothing in an iteration reads the device; the log,
     validation and checkpoint iterations do (one `TrainLog.read()`, `step.check()`).  Every `val_interval` iterations and after the
     last, `validate()` -> a metric dictionary (a closure over `evaluate(...)`), handed to the hooks' `after_val`.
 
@@ -655,6 +706,14 @@ class TrainLoop:
         # followed by `step.red.reduce()` and `optimizer.step()` here, and the log's row by an eager append behind them
         self.eager_update = hasattr(step, "red") and getattr(step, "optimizer", None) is None
         self.eager_append = self.log is not None and not getattr(step, "log_captured", True)
+        self.accum = getattr(optimizer, "accum", None)          # a train.GradAccum: FlatAdamW(accumulative_counts=k), k > 1
+        if self.accum is not None:
+            if getattr(step, "optimizer", None) is not optimizer:
+                raise ValueError("TrainLoop: an optimizer with accumulative_counts > 1 has to be the step's own (optimizer=...): "
+                                 "the step accumulates behind its packing")
+            # at world size 1 the step updates and appends by itself, behind its replay; beyond, it stops behind the accumulation
+            self.eager_update = self.world > 1
+            self.eager_append = self.log is not None and self.world > 1
         if self.eager_append:
             self.log.bind({**step.log_terms, "grad_norm": optimizer.grad_norm, "clip_coef": optimizer.clip_coef})
         self.state = TrainState(step.model, optimizer, scheduler, augment, async_write=async_write)
@@ -671,6 +730,10 @@ class TrainLoop:
 
     def meta(self):
         return dict(iter=self.iter + 1, max_iters=self.max_iters)
+
+    def update_iteration(self, updates):
+        """the iteration (from 1) whose update was the `updates`-th (from 1): every accumulative_counts-th, and the last one"""
+        return updates if self.accum is None else min(updates * self.accum.counts, self.max_iters)
 
     def check_finite(self):
         """-> the log as of this iteration (read once per iteration, whoever asks), after raising for what went wrong on the device
@@ -696,7 +759,8 @@ class TrainLoop:
             where = ""
             first = self.grad_log.read(consume=False).first_nonfinite if self.grad_log is not None else None
             if first is not None:          # the tensor it started in: the lowest parameter of the first row with a non-finite gradient
-                where = f"; the first non-finite gradient is in {first[1]}, iteration {self.grad_log.base + first[0] + 1}"
+                where = (f"; the first non-finite gradient is in {first[1]}, iteration "
+                         f"{self.update_iteration(self.grad_log.base + first[0] + 1)}")
             raise FloatingPointError(f"non-finite training terms first at iteration {bad}{seen}; checkpoints up to iteration "
                                      f"{bad - 1} predate it{where}")
         self._read = (self.iter, read)
@@ -731,12 +795,18 @@ class TrainLoop:
                 if self.resume:
                     start = int(self.resumed["meta"]["iter"])
             self.iter = start
+            counts = 1 if self.accum is None else self.accum.counts
+            if self.accum is not None:
+                if start % counts:
+                    raise ValueError(f"TrainLoop: resumed at iteration {start}, inside a group of accumulative_counts={counts}: the "
+                                     f"group's gradients are in no checkpoint")
+                self.accum.total, self.accum.count = self.max_iters, start
             if self.log is not None:
                 self.log.base = start - self.log.read().count          # row 0 of a fresh log is iteration start + 1
             if self.firing is not None:          # (the ring and the streaks are in no checkpoint: a resumed run starts them afresh)
                 self.firing.base = start - self.firing.read().count
             if self.grad_log is not None:        # (neither is the gradient log's ring)
-                self.grad_log.base = start - self.grad_log.read(consume=False).count
+                self.grad_log.base = start // counts - self.grad_log.read(consume=False).count          # (its rows count updates)
             self._call("before_run")
             batches = _cycle(self.batches, start)
             out = (self.step.static_in, self.step.static_seg)
@@ -745,10 +815,12 @@ class TrainLoop:
                 images, segs = next(batches)
                 self.augment(images, segs, out=out)
                 self.step()
-                if self.eager_update:
+                if self.eager_update and (self.accum is None or self.accum.plan(it)[2]):
                     self.step.red.reduce()
                     self.step.red.wait()
                     self.optimizer.step()
+                    if self.accum is not None:
+                        self.accum.finish()
                 if self.eager_append:
                     self.log.append()
                 self.lr = self.optimizer.param_groups[0]["lr"]          # this iteration's: the scheduler moves on below

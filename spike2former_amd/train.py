@@ -8,7 +8,9 @@ mmengine itself is not part of the reference tree (third-party, mmengine 0.8.4 p
 the `custom_keys` rule of DefaultOptimWrapperConstructor and the two schedulers are restated from its published behaviour;
 parity is pinned by the config's own values only.  The reference's optimiser is torch.optim.AdamW behind clip_grad_norm_;
 `OptimWrapper` runs exactly that (eager, one group per parameter), `FlatAdamW` is the same update as three HIP launches over
-the flat gradient buffer of the data-parallel step (csrc/optim.hip), pinned against the former in tests/test_gpu_round5.py."""
+the flat gradient buffer of the data-parallel step (csrc/optim.hip), pinned against the former in tests/test_gpu_round5.py.
+Both take mmengine's `accumulative_counts`: `GradAccum` adds micro-batch gradients up on the flat buffer (one launch each),
+`OptimWrapper` does it the way mmengine does, through autograd (tests/test_gpu_grad_accum.py compares the two)."""
 import torch
 
 from .neuron import reset_net
@@ -64,6 +66,102 @@ def _multipliers(names, paramwise_cfg):
     return out
 
 
+def accumulation_plan(i, counts, total=None):
+    """mmengine 0.8.4 OptimWrapper's gradient accumulation rule (`accumulative_counts`, `should_update`, `_get_loss_factor` after
+    `initialize_count_status(model, 0, total)`), restated: iteration `i` (from 0) of a run of `total` iterations (None: unknown, no
+    trailing group) -> (scale, first, last).  Groups are counted from iteration 0; `first` opens a group, `last` closes it (the
+    update follows); `scale` multiplies the micro-batch's gradient: 1 / counts, and 1 / (total % counts) in the trailing partial
+    group, the iterations >= total - total % counts when counts does not divide total."""
+    first = i % counts == 0
+    last = (i + 1) % counts == 0 or (total is not None and i + 1 == total)
+    scale = 1.0 / counts
+    if total is not None and total % counts and i >= total - total % counts:
+        scale = 1.0 / (total % counts)
+    return scale, first, last
+
+
+class GradAccum:
+    """mmengine's `OptimWrapper(accumulative_counts=k)` on the flat gradient buffer: the gradients of k micro-batches are added up,
+    then ONE clip and ONE AdamW step follow.  The accumulator is a second flat buffer of `grad_buffer.flat`'s layout; `add()` is
+    one streaming launch (s2f_grad_accumulate, csrc/optim.hip) behind the step's packing:
+
+        not the group's last iteration:  acc = [acc +] scale * flat            (and the micro-batch's g^2 partials, row i % k)
+        the group's last iteration:      flat = acc + scale * flat             -> `grad_buffer.flat` holds the accumulated MEAN gradient:
+                                         reduce(), FlatAdamW.step() and GradLog read the buffer they always read
+
+    `finish()`, directly behind `FlatAdamW.step()`: one launch (s2f_grad_accum_stats) turns the micro partials of the group just
+    closed and the optimizer's own partials (s2f_grad_sqnorm of the accumulated gradient, written inside step()) into
+    `stats` = {mean micro-batch |g|^2, |accumulated g|^2, micro-batches, 0}: the two terms of the gradient-noise-scale estimate
+    (runner.LoggerHook).  Rows of `micro` hold |g|^2 of the UNSCALED micro-batch gradient.
+
+    `count`: the iterations done (host; set it for a resumed run), `total`: the run's max_iters or None -- what `plan()` needs.
+    mmengine is not part of the reference tree: the rule is restated from mmengine 0.8.4's OptimWrapper and, like the schedulers',
+    its parity is UNPINNED.  Stated deviation: mmengine scales the LOSS before backward, here the finished gradient is scaled --
+    fp32 round-off apart the same, and exactly the same for power-of-two counts."""
+
+    def __init__(self, grad_buffer, counts, total=None):
+        from ._lib import lib
+        counts = int(counts)
+        if counts < 1:
+            raise ValueError(f"GradAccum: accumulative_counts {counts} below 1")
+        self.red, self.counts, self.total, self.count = grad_buffer, counts, total, 0
+        flat = grad_buffer.flat
+        self.acc = torch.zeros_like(flat)
+        self.parts = int(lib.s2f_grad_sqnorm_parts(flat.numel()))
+        self.micro = torch.zeros(counts, self.parts, dtype=torch.float64, device=flat.device)
+        self.stats = torch.zeros(4, dtype=torch.float32, device=flat.device)
+        self._rows = counts          # the micro-batches of the group closed last
+        self._layout = self._layout_now()
+        self.partials = None         # the optimizer's s2f_grad_sqnorm partials (FlatAdamW sets it)
+
+    def _layout_now(self):
+        return tuple(getattr(self.red, "offsets", ())), tuple(id(p) for p in getattr(self.red, "params", ()))
+
+    def plan(self, i):
+        return accumulation_plan(i, self.counts, self.total)
+
+    @property
+    def open(self):
+        """whether a group is under way (gradients in the accumulator that no update has consumed)"""
+        return self.count % self.counts != 0 and self.count != self.total
+
+    def add(self):
+        """-> whether this iteration closed its group (the caller updates).  One launch, no wait."""
+        from ._lib import check, lib
+        from .ops.core import _stream
+        flat = self.red.flat
+        if flat.numel() != self.acc.numel() or self._layout_now() != self._layout:
+            raise RuntimeError("GradAccum: the gradient buffer was laid out again (compact()); call rebuild()")
+        scale, first, last = self.plan(self.count)
+        row = self.count % self.counts
+        check(lib.s2f_grad_accumulate(flat.data_ptr(), None if first else self.acc.data_ptr(),
+                                      (flat if last else self.acc).data_ptr(), flat.numel(), scale,
+                                      self.micro[row].data_ptr(), _stream()), "s2f_grad_accumulate")
+        if last:
+            self._rows = row + 1
+        self.count += 1
+        return last
+
+    def finish(self, partials=None):
+        """directly behind `FlatAdamW.step()`.  `partials`: the optimizer's (FlatAdamW.partials, which FlatAdamW hands over when it
+        builds the accumulator), as its step() on the accumulated gradient just left them"""
+        from ._lib import check, lib
+        from .ops.core import _stream
+        partials = self.partials if partials is None else partials
+        if partials is None or partials.numel() != self.parts or partials.dtype != torch.float64:
+            raise ValueError(f"GradAccum.finish needs the optimizer's {self.parts} fp64 partials")
+        check(lib.s2f_grad_accum_stats(self.micro.data_ptr(), self._rows, partials.data_ptr(), self.parts, self.stats.data_ptr(),
+                                       _stream()), "s2f_grad_accum_stats")
+
+    def rebuild(self):
+        """after grad_buffer.compact(): a new accumulator in the new layout.  Only at a group boundary: between updates the old
+        one holds gradients whose slots moved."""
+        if self.open:
+            raise RuntimeError(f"GradAccum.rebuild inside a group (iteration {self.count}, accumulative_counts {self.counts})")
+        self.acc = torch.zeros_like(self.red.flat)
+        self._layout = self._layout_now()
+
+
 class FlatAdamW:
     """clip_grad_norm_(max_norm) + AdamW over `dist.FlatGradAllReduce`'s flat gradient buffer: three HIP launches per iteration
     (s2f_grad_sqnorm -> s2f_adamw_prepare -> s2f_adamw_step), no host synchronisation -- `step()` can be captured behind the
@@ -79,10 +177,15 @@ class FlatAdamW:
     `grad_log`: None (default: the step is the three launches above, nothing else is allocated or launched), True or a dictionary of
     `gradlog.GradLog` arguments (`dict(window=50, patience=200)`): `step()` appends one row of per-parameter gradient, weight and
     update norms directly behind s2f_adamw_step, two launches more that only read (`self.grad_log`; `attach_grad_log` takes a log
-    built by the caller)."""
+    built by the caller).
+
+    `accumulative_counts` (mmengine's OptimWrapper argument): 1 (default) -- `self.accum` is None, nothing is allocated, the class is
+    what it is without the argument; k > 1 -- `self.accum = GradAccum(grad_buffer, k)`: whoever drives the step calls
+    `accum.add()` behind the packing of EVERY iteration and `step(); accum.finish()` behind the one that closes a group
+    (graph.GraphedStep / GraphedHungarianStep and runner.TrainLoop do)."""
 
     def __init__(self, model, grad_buffer, lr=0.001, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.005, paramwise_cfg=None,
-                 clip_grad=None, grad_log=None):
+                 clip_grad=None, grad_log=None, accumulative_counts=1):
         from ._lib import lib
         self.red, self.betas, self.eps = grad_buffer, (float(betas[0]), float(betas[1])), float(eps)
         self.max_norm = float((clip_grad or {}).get("max_norm", 0.0)) if clip_grad else 0.0
@@ -104,6 +207,10 @@ class FlatAdamW:
         self._hyper_events, self._hyper_turn, self._hyper_last = [None, None], 0, None
         self.hyper = torch.zeros(len(self.params), 2, dtype=torch.float32, device=dev)
         self._build_tables()
+        self.accum = None
+        if int(accumulative_counts) != 1:
+            self.accum = GradAccum(grad_buffer, accumulative_counts)          # (raises for a count below 1)
+            self.accum.partials = self.partials
         self.grad_log = None
         if grad_log is not None and grad_log is not False:
             from .gradlog import GradLog
@@ -201,6 +308,8 @@ class FlatAdamW:
         self.param_groups = [groups[id(p)] for p in self.params]
         self._hyper_last = None                      # the table's row order changed with the buffer's layout: upload again
         self._build_tables()
+        if self.accum is not None:
+            self.accum.rebuild()                     # (only at a group boundary: raises inside a group)
         if self.grad_log is not None:
             self.grad_log.rebuild()                  # (its span table follows the slot table; its rows start afresh)
 
@@ -259,9 +368,15 @@ class LinearThenPoly:
 
 
 class OptimWrapper:
-    """optimizer + clip_grad, as the config's `optim_wrapper` (:150-155)."""
+    """optimizer + clip_grad, as the config's `optim_wrapper` (:150-155).
 
-    def __init__(self, model, optimizer=None, clip_grad=None, paramwise_cfg=None):
+    `accumulative_counts=k`: mmengine's own mechanics, the readable statement of what GradAccum does on the flat buffer --
+    `update_params(loss)` scales the loss by the plan's factor (accumulation_plan) and runs backward, autograd adds into `p.grad`,
+    and the clip, the step and zero_grad happen only where the plan says the group closes.  `initialize_count_status(total)`
+    tells the plan where the run ends (the trailing partial group); `count` is the number of `update_params` calls so far.
+    Restated from mmengine 0.8.4 (not part of the reference tree); parity UNPINNED."""
+
+    def __init__(self, model, optimizer=None, clip_grad=None, paramwise_cfg=None, accumulative_counts=1):
         cfg = dict(optimizer or dict(type="AdamW", lr=0.001, betas=(0.9, 0.999), weight_decay=0.005))
         kind = cfg.pop("type", "AdamW")
         if kind != "AdamW":
@@ -270,10 +385,23 @@ class OptimWrapper:
         self.optimizer = torch.optim.AdamW(param_groups(model, lr, wd, paramwise_cfg), lr=lr, weight_decay=wd, **cfg)
         self.clip = dict(clip_grad) if clip_grad else None
         self.params = [p for g in self.optimizer.param_groups for p in g["params"]]
+        self.counts, self.count, self.total = int(accumulative_counts), 0, None
+        if self.counts < 1:
+            raise ValueError(f"OptimWrapper: accumulative_counts {self.counts} below 1")
+
+    def initialize_count_status(self, total, count=0):
+        """`total`: the run's max_iters; `count`: the iterations already done (a resumed run)"""
+        self.total, self.count = total, int(count)
 
     def update_params(self, loss):
-        loss.backward()
-        return self.step()
+        """-> the gradient norm where an update happened (and a clip is configured), else None"""
+        if self.counts == 1:
+            loss.backward()
+            return self.step()
+        scale, _, last = accumulation_plan(self.count, self.counts, self.total)
+        (loss * scale).backward()
+        self.count += 1
+        return self.step() if last else None
 
     def step(self):
         norm = None
