@@ -8,6 +8,7 @@ from .backbone_sdtv2 import Spiking_vit_MetaFormer  # noqa: F401
 from .backbone_sdtv3 import Multispike_norm, Spiking_vit_MetaFormerv2  # noqa: F401
 from .configs import WORKLOADS, model_cfg  # noqa: F401
 from .data_preprocessor import SegDataPreProcessor, SegDataSample  # noqa: F401
+from .devring import DeviceRing  # noqa: F401
 from .firing import FiringLog, FiringRead, FiringRecorder  # noqa: F401
 from .gradlog import GradLog, GradRead  # noqa: F401
 from .energy import EnergyReport, OpCensus  # noqa: F401

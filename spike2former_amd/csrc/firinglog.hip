@@ -5,21 +5,17 @@
 //   s2f_firing_log_append  ONE launch, one wave per neuron.  The wave loads its neuron's 256 slots (each lane four slots, one
 //                          16-byte load per slot: a slot IS a {sum, nonzero} pair), adds them up as 64-bit integers, stores the
 //                          pair into row head[0] % window of the ring, clears the 512 counter words with 16-byte stores and moves
-//                          the neuron's silent streak on.  A streak that REACHES `patience` is offered to head[1] by an unsigned
-//                          64-bit atomicMin of row * 2^32 + neuron: the earliest row's lowest neuron wins in whatever order the
-//                          workgroups finish, and -1 (all ones: the largest unsigned value) means none.
-//                          head[0] advances once per launch: every workgroup reads the row index at entry -- before it takes a
-//                          ticket from head[2] -- and the workgroup that draws the last ticket, when every other has read its row
-//                          index, stores head[0] + 1 and puts the ticket word back to 0.  No workgroup waits for another.
-//                          The words of `head` are touched by agent-scope atomics only: nothing of them lives in a CU's L1.
+//                          the neuron's silent streak on.  A streak that REACHES `patience` is offered to the latch head[1], and
+//                          head[0] advances once per launch, by the head protocol of s2f_ring.h.
 #include "s2f_common.h"
+#include "s2f_ring.h"
 
 namespace {
 
 constexpr int kSlotsPerLane = S2F_STAT_SLOTS / S2F_WAVE;
 static_assert(kSlotsPerLane * S2F_WAVE == S2F_STAT_SLOTS, "a wave covers the slots in whole rounds");
 
-typedef unsigned long long u64;
+typedef s2f_u64 u64;
 
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
   // (__shfl_xor moves a 64-bit value as two 32-bit halves and hands the whole value back: the ADD below is a 64-bit one, so a
@@ -33,7 +29,7 @@ __global__ __launch_bounds__(S2F_WAVE) void firing_log_append_kernel(u64* __rest
                                                                      int window, int* __restrict__ silent, int patience, u64* head) {
   const int i = blockIdx.x;          // (the grid is n workgroups of one wave)
   const int lane = threadIdx.x;
-  const u64 row = __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const u64 row = s2f_ring_row(head);
   ulonglong2* __restrict__ slots = reinterpret_cast<ulonglong2*>(counters + (size_t)i * (2 * S2F_STAT_SLOTS));
   u64 sum = 0, nonzero = 0;
 #pragma unroll
@@ -54,14 +50,9 @@ __global__ __launch_bounds__(S2F_WAVE) void firing_log_append_kernel(u64* __rest
     if (s != -1) {          // -1: a neuron the step never runs is not watched
       s = sum == 0 ? s + 1 : 0;
       silent[i] = s;
-      if (s == patience) atomicMin(head + 1, (row << 32) | (u64)(unsigned)i);
+      if (s == patience) s2f_ring_offer(head, 1, s2f_ring_event(row, i));
     }
-    // The row index above was read before this add: whoever draws the last ticket knows that every workgroup holds its own.
-    const u64 ticket = atomicAdd(head + 2, 1ull);
-    if (ticket == (u64)(n - 1)) {
-      __hip_atomic_store(head + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(head, row + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    s2f_ring_commit(head, row, n);
   }
 }
 

@@ -7,17 +7,17 @@
 //                          Adam step u of optim.hip in its fp32 expressions, accumulates per thread in fp64 and reduces over the
 //                          block in a fixed order; 8 words per span, plain stores.  Nothing floating-point crosses workgroups here.
 //   s2f_grad_log_rows      one wave per parameter: lane c < 8 combines column c of that parameter's spans IN SPAN ORDER (sums add,
-//                          max of max, counts add) and stores the row at head[0] % window; lane 0 moves the two streaks on and offers
-//                          the two latches by unsigned 64-bit atomicMin of row * 2^32 + index; head[0] advances by the ticket in
-//                          head[2] -- the scheme of firing_log_append_kernel.  The words of `head` see agent-scope atomics only.
+//                          max of max, counts add) and stores the row at head[0] % window; lane 0 moves the two streaks on, offers
+//                          the two latches head[1] and head[3] and advances head[0]: the head protocol of s2f_ring.h.
 // Both kernels only READ g, m, v, p, hyper and state.
 #include "s2f_common.h"
+#include "s2f_ring.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
+typedef s2f_u64 u64;
 
 constexpr int kSpan = 16384;          // elements per workgroup: 256 threads x 16 float4
 constexpr int kBlock = 256;
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(S2F_WAVE) void grad_log_rows_kernel(const int* __re
                                                                  int patience, u64* head) {
   const int i = blockIdx.x;          // (the grid is n workgroups of one wave)
   const int lane = threadIdx.x;
-  const u64 row = __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const u64 row = s2f_ring_row(head);
   // the first span of parameter i: the table is sorted by slot (the whole wave takes the same steps)
   int lo = 0, hi = nspans;
   while (lo < hi) {
@@ -175,15 +175,10 @@ __global__ __launch_bounds__(S2F_WAVE) void grad_log_rows_kernel(const int* __re
     b = bad > 0 ? b + 1 : 0;
     streak[2 * i] = s;
     streak[2 * i + 1] = b;
-    const u64 event = (row << 32) | (u64)(unsigned)i;
-    if (s == patience) atomicMin(head + 1, event);
-    if (b == 1) atomicMin(head + 3, event);
-    // The row index above was read before this add: whoever draws the last ticket knows that every workgroup holds its own.
-    const u64 ticket = atomicAdd(head + 2, 1ull);
-    if (ticket == (u64)(n - 1)) {
-      __hip_atomic_store(head + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(head, row + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const u64 event = s2f_ring_event(row, i);
+    if (s == patience) s2f_ring_offer(head, 1, event);
+    if (b == 1) s2f_ring_offer(head, 3, event);
+    s2f_ring_commit(head, row, n);
   }
 }
 

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .devring import DeviceRing, latch, unwrap
 from .neuron import LIFNode, Q_IFNode
 
 
@@ -88,11 +89,11 @@ class FiringRead(collections.namedtuple("FiringRead", "names sums elems count si
         return self._per_elem(1)
 
 
-class FiringLog:
+class FiringLog(DeviceRing):
     """Firing counters of every neuron for EVERY iteration of a captured step, without a host stop: the counters of all neurons
-    are slices of one allocation, `append()` is one launch (ops.firing_log_append, capturable) that adds each neuron's contention
-    slots up, writes the pair into the next row of a ring on the device, clears the counters and keeps a streak of silent rows per
-    neuron, latching the first neuron that stayed silent for `patience` rows.  `read()` is one device-to-host copy.
+    are slices of one allocation, `append()` is one launch (ops.firing_log_append) that adds each neuron's contention slots up,
+    writes the pair into the next row of a devring.DeviceRing (int64 [window, n, 2]), clears the counters and keeps a streak of
+    silent rows per neuron (the state words), latching in head[1] the first neuron that stayed silent for `patience` rows.
 
         firing = FiringLog(model, window=50)
         step = GraphedHungarianStep(..., firing=firing)        # attach, measure, append recorded as the step's last launch
@@ -103,6 +104,7 @@ class FiringLog:
 
     Attached counters change which kernels run: the memoised, pre-fired and fused-neuron routes test `stats is None` and step aside,
     as they do for `FiringRecorder` (which stays the tool for an evaluation table in the reference's format)."""
+    HEAD, prefix = (0, -1, 0, 0), "firing"
 
     def __init__(self, model, window=64, patience=200, quant=8, device=None):
         if window < 1 or patience < 1:
@@ -114,26 +116,15 @@ class FiringLog:
         if device is None:
             p = next(model.parameters(), None)
             device = p.device if p is not None else "cpu"
-        self.device = torch.device(device)
         n = self.n = len(self.nodes)
         self.names = list(self.nodes)
+        state, ring = self._allocate((n + 1) // 2, self.window * n * 2, device)          # (silent: padded to whole words)
+        self.silent, self.ring = state.view(torch.int32)[:n], ring.view(self.window, n, 2)
         self.counters = torch.zeros(n, ops.STAT_SLOTS, 2, dtype=torch.int64, device=self.device)
-        # head (int64 [4]), silent (int32 [n], padded to whole int64 words) and ring in ONE allocation: read() is one copy
-        pad = (n + 1) // 2
-        self._buf = torch.zeros(4 + pad + self.window * n * 2, dtype=torch.int64, device=self.device)
-        self.head = self._buf[:4]
-        self.silent = self._buf[4:4 + pad].view(torch.int32)[:n]
-        self.ring = self._buf[4 + pad:].view(self.window, n, 2)
-        self.head[1] = -1
-        self._host = torch.zeros_like(self._buf, device="cpu")
-        self._event = None
-        if self.device.type == "cuda":
-            self._host = self._host.pin_memory()
-            self._event = torch.cuda.Event()
+        self.clear()
         self.elems = torch.zeros(n, dtype=torch.int64)          # (host) elements per neuron in one forward; 0: not watched
         self.scale = np.array([quant / m.D for m in self.nodes.values()], np.float64)
         self.attached = False
-        self.base = 0          # the iterations that ran before row 0 (a resumed run)
 
     # ------------------------------------------------------------------------------------------------ the neurons' counters
     def attach(self):
@@ -169,12 +160,9 @@ class FiringLog:
 
     def clear(self):
         """counters, ring and head as new; the streaks of the watched neurons to 0.  Not under capture."""
-        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FiringLog.clear under capture")
+        super().clear()
         self.counters.zero_()
-        self.ring.zero_()
         self.silent.clamp_(max=0)          # (-1 stays)
-        self.head.copy_(torch.tensor([0, -1, 0, 0], dtype=torch.int64))
 
     # ------------------------------------------------------------------------------------------------ rows
     def append(self):
@@ -182,18 +170,32 @@ class FiringLog:
         ops.firing_log_append(self.counters, self.ring, self.silent, self.head, self.patience)
 
     def read(self):
-        """-> FiringRead.  One device-to-host copy on the current stream, and a wait for that copy."""
-        if self._event is not None:
-            self._host.copy_(self._buf, non_blocking=True)
-            self._event.record()
-            self._event.synchronize()
-        else:
-            self._host.copy_(self._buf)
-        n, pad = self.n, (self.n + 1) // 2
-        count, dead = int(self._host[0]), int(self._host[1])
-        k = min(count, self.window)
-        ring = self._host[4 + pad:].view(self.window, n, 2).numpy()
-        sums = np.stack([ring[(count - k + i) % self.window] for i in range(k)]) if k else np.zeros((0, n, 2), np.int64)
-        silent = self._host[4:4 + pad].view(torch.int32)[:n].numpy().copy()
-        first = None if dead < 0 else (dead >> 32, self.names[dead & 0xffffffff])
-        return FiringRead(list(self.names), sums.copy(), self.elems.numpy().copy(), count, silent, first, self.scale)
+        """-> FiringRead.  One `fetch()`."""
+        words = self.fetch()
+        n, pad, count = self.n, (self.n + 1) // 2, int(words[0])
+        sums = unwrap(words[4 + pad:].reshape(self.window, n, 2), count, self.window)
+        silent = words[4:4 + pad].view(np.int32)[:n].copy()
+        return FiringRead(list(self.names), sums, self.elems.numpy().copy(), count, silent, latch(words[1], self.names), self.scale)
+
+    def report(self, n, since, iteration_of=int):
+        """runner.LoggerHook's share of the log line of iteration `n`, over the rows since the line of iteration `since` -> (keys for
+        the line and scalars.json, the line of firing.jsonl or None, a warning or None).  Keys: the mean rate over the watched neurons,
+        the neuron with the lowest mean rate, the watched neurons that did not fire in the last row.  firing.jsonl: every watched
+        neuron's mean rate and non-zero share.  Warning: the latched first dead neuron and the iteration its streak reached `patience`."""
+        read = self.read()
+        k = min(n - since, len(read.sums), read.count)
+        watched = read.elems > 0
+        keys, items, warning = {}, None, None
+        if k > 0 and watched.any():
+            rates, nz = read.rates()[-k:].mean(0), read.nonzero()[-k:].mean(0)
+            low = int(np.flatnonzero(watched)[np.argmin(rates[watched])])
+            keys["firing/mean"] = float(rates[watched].mean())
+            keys["firing/min"], keys["firing/min_name"] = float(rates[low]), read.names[low]
+            keys["firing/silent"] = int((read.silent[watched] >= 1).sum())
+            idx = np.flatnonzero(watched)
+            items = dict(iter=n, rows=k, rates={read.names[i]: float(rates[i]) for i in idx},
+                         nonzero={read.names[i]: float(nz[i]) for i in idx})
+        if read.first_dead is not None:
+            row, name = read.first_dead
+            warning = f"neuron {name} has not fired for {self.patience} iterations, up to iteration {iteration_of(self.base + row + 1)}"
+        return keys, items, warning

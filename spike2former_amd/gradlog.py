@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .devring import DeviceRing, latch, unwrap
 
 
 class GradRead(collections.namedtuple("GradRead", "names cols count streak first_stalled first_nonfinite")):
@@ -36,14 +37,9 @@ class GradRead(collections.namedtuple("GradRead", "names cols count streak first
         buf = np.asarray(buf, dtype=np.int64)
         n = len(names)
         count = int(buf[0])
-        k = max(0, min(count - last, window))
-        ring = buf[4 + n:].reshape(window, n, 8)
-        cols = np.stack([ring[(count - k + i) % window] for i in range(k)]) if k else np.zeros((0, n, 8), np.int64)
+        cols = unwrap(buf[4 + n:].reshape(window, n, 8), count, window, last)
         streak = buf[4:4 + n].copy().view(np.int32).reshape(n, 2)
-
-        def event(word):
-            return None if word < 0 else (int(word >> 32), names[int(word & 0xffffffff)])
-        return cls(list(names), cols.copy(), count, streak, event(int(buf[1])), event(int(buf[3])))
+        return cls(list(names), cols, count, streak, latch(buf[1], names), latch(buf[3], names))
 
     def _f(self, c):
         return np.ascontiguousarray(self.cols[:, :, c]).view(np.float64)
@@ -100,11 +96,13 @@ class GradRead(collections.namedtuple("GradRead", "names cols count streak first
         return np.sqrt(self._f(0).sum(1))
 
 
-class GradLog:
-    """A ring of the last `window` iterations' per-parameter rows on the device, over a `train.FlatAdamW`.  `append()` is two launches
-    (ops.grad_log_append, capturable) that only read the optimizer's buffers and the parameters; `FlatAdamW.step()` calls it directly
-    behind the update once the log is attached, so a row is added wherever `step()` runs: captured with the step at world size 1, eager
-    behind the all-reduce at N > 1.  `read()` is one device-to-host copy.  Without a log the step launches what it always did."""
+class GradLog(DeviceRing):
+    """A devring.DeviceRing of the last `window` updates' per-parameter rows (int64 [window, n, 8]; state words: the streaks, int32
+    [n, 2]; head[1] latches the first stalled parameter, head[3] the first non-finite gradient) over a `train.FlatAdamW`.  `append()`
+    is two launches (ops.grad_log_append) that only read the optimizer's buffers and the parameters; `FlatAdamW.step()` calls it
+    directly behind the update once the log is attached, so a row is added wherever `step()` runs: captured with the step at world
+    size 1, eager behind the all-reduce at N > 1.  Without a log the step launches what it always did."""
+    HEAD, prefix = (0, -1, 0, -1), "grad"
 
     def __init__(self, optimizer, window=64, patience=200):
         if window < 1 or patience < 1:
@@ -114,21 +112,9 @@ class GradLog:
         n = self.n = len(self.names)
         if n < 1:
             raise ValueError("GradLog: the optimizer has no parameters")
-        self.device = optimizer.slots.device
-        # head (int64 [4]), the streaks (int32 [n, 2]: n whole words) and the ring in ONE allocation: read() is one copy
-        self._buf = torch.zeros(4 + n + self.window * n * 8, dtype=torch.int64, device=self.device)
-        self.head = self._buf[:4]
-        self.streak = self._buf[4:4 + n].view(torch.int32).view(n, 2)
-        self.ring = self._buf[4 + n:].view(self.window, n, 8)
-        self._host = torch.zeros_like(self._buf, device="cpu")
-        self._event = None
-        if self.device.type == "cuda":
-            self._host = self._host.pin_memory()
-            self._event = torch.cuda.Event()
-        self.base = 0          # the iterations that ran before row 0 (a resumed run)
-        self._last = 0         # the row count at the last read
-        self._slots = None
-        self.rebuild()
+        state, ring = self._allocate(n, self.window * n * 8, optimizer.slots.device)
+        self.streak, self.ring = state.view(torch.int32).view(n, 2), ring.view(self.window, n, 8)
+        self.rebuild()          # (-> clear(): `_last`, the row count at the last read, is 0)
 
     def rebuild(self):
         """the span table over the optimizer's CURRENT slot table (FlatAdamW.rebuild() re-lays the buffers and may reorder the
@@ -143,10 +129,8 @@ class GradLog:
 
     def clear(self):
         """ring, streaks and head as new.  Not under capture."""
-        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("GradLog.clear under capture")
-        self._buf.zero_()
-        self.head.copy_(torch.tensor([0, -1, 0, -1], dtype=torch.int64))
+        super().clear()
+        self.streak.zero_()
         self._last = 0
 
     def append(self):
@@ -158,15 +142,37 @@ class GradLog:
                             self.ring, self.streak, self.head, opt.eps, self.patience)
 
     def read(self, consume=True):
-        """-> GradRead over the rows since the last read.  One device-to-host copy on the current stream, and a wait for that copy.
-        `consume=False`: the next read sees these rows again."""
-        if self._event is not None:
-            self._host.copy_(self._buf, non_blocking=True)
-            self._event.record()
-            self._event.synchronize()
-        else:
-            self._host.copy_(self._buf)
-        read = GradRead.from_buffer(self._host.numpy(), self.names, self.window, self._last)
+        """-> GradRead over the rows since the last read.  One `fetch()`.  `consume=False`: the next read sees these rows again."""
+        read = GradRead.from_buffer(self.fetch(), self.names, self.window, self._last)
         if consume:
             self._last = read.count
         return read
+
+    def report(self, n, since, iteration_of):
+        """runner.LoggerHook's share of a log line, over the rows since the last read -> (keys for the line and scalars.json, the line
+        of grad.jsonl or None, a warning or None).  Keys: the parameter with the lowest mean gradient norm, the one holding the largest
+        share of sum g^2 (the one the clip is reacting to), the largest mean |u| / |p|, the share of gradient elements that are exactly
+        0, the parameters whose gradient was all zero in the last row.  grad.jsonl: every parameter's figures, under the iteration
+        of the last row (`iteration_of` a row number: the rows count updates).  Warning: the latched first stalled parameter."""
+        read = self.read()
+        k = len(read.cols)
+        keys, items, warning = {}, None, None
+        if k > 0:
+            sq = read.grad_sq.sum(0)
+            norm, ratio = read.grad_norm.mean(0), read.update_ratio.mean(0)
+            low, top, far = int(np.argmin(norm)), int(np.argmax(sq)), int(np.argmax(ratio))
+            elems = float(read.numel.sum())
+            keys["grad/min"], keys["grad/min_name"] = float(norm[low]), read.names[low]
+            keys["grad/max_share"], keys["grad/max_name"] = float(sq[top] / sq.sum()) if sq.sum() > 0 else 0.0, read.names[top]
+            keys["grad/update_ratio_max"], keys["grad/update_ratio_max_name"] = float(ratio[far]), read.names[far]
+            keys["grad/zero_share"] = float(read.cols[:, :, 4].sum()) / elems if elems else 0.0
+            keys["grad/stalled"] = int((read.streak[:, 0] >= 1).sum())
+            per = dict(grad_norm=norm, weight_norm=read.weight_norm.mean(0), update_ratio=ratio, grad_max=read.grad_max.max(0),
+                       zero_share=read.zero_share.mean(0))
+            items = dict(iter=iteration_of(self.base + read.count), rows=k,
+                         **{key: {name: float(v) for name, v in zip(read.names, vals)} for key, vals in per.items()})
+        if read.first_stalled is not None:
+            row, name = read.first_stalled
+            warning = (f"parameter {name} has had an all-zero gradient for {self.patience} iterations, up to iteration "
+                       f"{iteration_of(self.base + row + 1)}")
+        return keys, items, warning

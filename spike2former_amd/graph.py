@@ -41,10 +41,26 @@ def _world_size():
     return dist.get_world_size() if _process_group() else 1
 
 
+def step_tail(optimizer_in_step, accumulating, world):
+    """Who runs what follows the gradient packing of a training step -> (update, row): the parameter update and the row of the
+    step's log (runner.TrainLog), each "graph" (recorded into the step's last hipGraph), "call" (eager in the step's `__call__`,
+    behind the replay) or "caller" (runner.TrainLoop, behind the step: beyond one rank the all-reduce lies before the update, and
+    the row holds the update's grad_norm).  An accumulating optimizer (accumulative_counts > 1; always the step's own) updates on
+    some calls only, so never inside the graph.  (optimizer handed to the step, accumulating, world) -> update, row:
+        yes, no, 1   -> graph, graph         no, no, 1   -> caller, graph          yes, yes, 1   -> call, call
+        yes, no, > 1 -> graph, caller        no, no, > 1 -> caller, caller         yes, yes, > 1 -> caller, caller"""
+    if accumulating:
+        return ("call", "call") if world == 1 else ("caller", "caller")
+    return "graph" if optimizer_in_step else "caller", "graph" if world == 1 else "caller"
+
+
 class _Captured:
     """A step with static input `static_in`, recorded as one hipGraph per stage.  `red`: the flat gradient buffer
     (dist.FlatGradAllReduce) of the steps that pack into one; `optimizer`: a train.FlatAdamW captured behind the packing."""
     optimizer = log = firing = None
+
+    def _tail(self):
+        return step_tail(self.optimizer is not None, self.accum is not None, _world_size())
 
     @property
     def grad_log(self):
@@ -54,35 +70,36 @@ class _Captured:
 
     @property
     def accum(self):
-        """the optimizer's train.GradAccum (FlatAdamW(accumulative_counts=k), k > 1) or None.  With one, the update is NOT part of
-        the capture: the recorded stages end with the packing (plus the status and firing launches), and every call runs
-        `_accumulate()` eagerly behind the replay, on the same stream."""
+        """the optimizer's train.GradAccum (FlatAdamW(accumulative_counts=k), k > 1) or None.  With one, the recorded stages end with
+        the packing (plus the status and firing launches), and every call runs `_accumulate()` behind the replay, on the same stream."""
         return getattr(self.optimizer, "accum", None)
 
     def _update_in_graph(self):
-        return self.optimizer is not None and self.accum is None
+        return self._tail()[0] == "graph"
 
     def _accumulate(self):
-        """behind the last replay of a call, with an accumulating optimizer: `accum.add()` on every call; at world size 1 also, on the
-        iteration that closes a group, `optimizer.step()` and `accum.finish()`, and on every call the log's row -- the loss terms
-        of THIS iteration, and grad_norm, clip_coef, grad_sq_micro, grad_sq_accum as the last update left them: rows of iterations
-        without an update repeat the last update's four values (zeros before the first), as grad_norm does in mmengine's log.
-        At world size > 1 the step stops behind `add()`: the all-reduce lies before the update, the caller (runner.TrainLoop) runs
-        reduce, update, `finish()` and the append.  Nothing here waits for the GPU.  -> whether the weights were updated."""
-        last = self.accum.add()
-        if _world_size() > 1:
-            return False
-        if last:
+        """behind the last replay of a call, with an accumulating optimizer: `accum.add()`, then what `step_tail` gives to the "call"
+        (world size 1; beyond, the caller runs reduce, update, `finish()` and the append): on the iteration that closes a group,
+        `optimizer.step()` and `accum.finish()`, and on every call the log's row -- the loss terms of THIS iteration, and grad_norm,
+        clip_coef, grad_sq_micro, grad_sq_accum as the last update left them (zeros before the first), as grad_norm repeats in
+        mmengine's log.  Nothing here waits for the GPU.  -> whether the weights were updated."""
+        update, row = self._tail()
+        updated = self.accum.add() and update == "call"
+        if updated:
             self.optimizer.step(sync_hyper=False)          # (`_begin` uploaded the table; eager: bumps the weight versions itself)
             self.accum.finish()
-        if self.log is not None:
+        if self.log is not None and row == "call":
             self.log.append()
-        return last
+        return updated
 
-    def _clear_grad_log(self):
-        """once the capture has ended: the warm-up passes' rows are not row 0"""
-        if self.grad_log is not None:
-            self.grad_log.clear()
+    def _after_capture(self):
+        """once the capture has ended: the table the log's launch reads is uploaded (nothing may be while a capture records), and
+        the firing and gradient logs start afresh -- what the warm-up passes appended is not row 0"""
+        if self.log is not None and self._tail()[1] != "caller":
+            self.log.bind(self.log_terms)
+        for ring in (self.firing, self.grad_log):
+            if ring is not None:
+                ring.clear()
 
     def _capture(self, warm, warmup, stages, context=None):
         """`warmup` calls of `warm` on a side stream (allocator pools, lazy inits, caches), then each callable of `stages`
@@ -146,23 +163,17 @@ class _Captured:
     def _record_log(self, terms):
         """while the LAST stage is recorded, behind the optimizer's update: one row of `terms` ({name: static scalar}, plus this
         iteration's grad_norm and clip_coef of a captured optimizer) per replay into `self.log` (runner.TrainLog).  The launch
-        reads the scalars through a pointer table that `_bind_log` fills once the capture has ended."""
+        reads the scalars through a pointer table that `_after_capture` fills."""
         if self.optimizer is not None:
             terms = {**terms, "grad_norm": self.optimizer.grad_norm, "clip_coef": self.optimizer.clip_coef}
         if self.accum is not None:
             terms = {**terms, "grad_sq_micro": self.accum.stats[0:1], "grad_sq_accum": self.accum.stats[1:2]}
         self.log_terms = terms
-        # at world size > 1 the all-reduce and the update follow the replay eagerly: the row is appended behind them, by the caller
-        # (runner.TrainLoop), who also binds the optimizer's terms.  An accumulating optimizer's update is eager at every world
-        # size, and the row with it (`_accumulate`).
-        self.log_captured = _world_size() == 1 and self.accum is None
+        # (a row that is the caller's: runner.TrainLoop also binds the optimizer's terms; the call's: `_accumulate`)
+        self.log_captured = self._tail()[1] == "graph"
         if self.log_captured:
             self.log.declare(terms.keys())
             self.log.append()
-
-    def _bind_log(self):
-        if self.log is not None and (self.log_captured or (self.accum is not None and _world_size() == 1)):
-            self.log.bind(self.log_terms)
 
     def _watch_firing(self, forward):
         """before the warm-up passes: every neuron counts into `self.firing` (firing.FiringLog) from here on -- which changes the
@@ -175,8 +186,7 @@ class _Captured:
 
     def _record_firing(self):
         """while the LAST stage is recorded, as its last launch: one row of every neuron's counters per replay, at every world
-        size (the forward is inside the graph on every rank; each rank logs its own shard).  The caller clears the log once the
-        capture has ended: what the warm-up passes counted is not row 0."""
+        size (the forward is inside the graph on every rank; each rank logs its own shard)"""
         if self.firing is not None:
             self.firing.append()
 
@@ -196,10 +206,8 @@ class GraphedStep(_Captured):
     the gradient packing, so one replay is one training ITERATION (single process; with N > 1 the all-reduce sits between the step
     and the update, which the caller then runs eagerly: `step(); grad_buffer.reduce(); optimizer.step()`).  `log` (runner.TrainLog):
     every replay appends {loss, grad_norm, clip_coef} to it, at the end of the graph; None: the capture holds no such launch.
-    `firing` (firing.FiringLog): see GraphedHungarianStep.
-    An optimizer built with `accumulative_counts=k` (its `accum` is set): the capture ends with the packing, and `__call__` runs the
-    accumulation, every k-th call the update, and the log's row eagerly behind the replay (`_Captured._accumulate`);
-    `log_captured` is False."""
+    `firing` (firing.FiringLog): see GraphedHungarianStep.  `step_tail` is the table of who updates and who appends the log's row
+    (`log_captured`: the graph does), at every world size and for an optimizer built with `accumulative_counts=k`."""
 
     def __init__(self, model, loss_fn, example_input, grad_buffer=None, warmup=3, optimizer=None, log=None, firing=None):
         self.model, self.loss_fn, self.log, self.firing = model, loss_fn, log, firing
@@ -218,10 +226,7 @@ class GraphedStep(_Captured):
         # ops.GLUE_MODE: the residual aten calls of the step (autograd's gradient accumulation, scalar multiples, copies, fills, small
         # sums) are routed to csrc/glue.hip while the step is RECORDED -- the replay then consists of this package's kernels only
         self.graph, = self._capture(self._eager_step, warmup, [record], context=ops.glue_mode if ops.GLUE_MODE else None)
-        self._bind_log()
-        if self.firing is not None:
-            self.firing.clear()
-        self._clear_grad_log()
+        self._after_capture()
 
     def _eager_step(self):
         reset_net(self.model)
@@ -324,10 +329,9 @@ class GraphedHungarianStep(_Captured):
 
     `firing` (firing.FiringLog over `model`): every neuron counts its spikes into the log's counters, and the last graph ends with
     one launch that turns them into a row per replay -- per-neuron firing rates of EVERY iteration, and the first neuron that stays
-    silent for the log's `patience` iterations, read by runner.LoggerHook with the losses.  (With an optimizer whose `accum` is
-    set -- FlatAdamW(accumulative_counts=k) -- the update and the log's row are not captured: see GraphedStep.)  Counters change the launch structure of
+    silent for the log's `patience` iterations, read by runner.LoggerHook with the losses.  Counters change the launch structure of
     the step (the memoised, pre-fired and fused-neuron routes step aside for a neuron that has them); None: nothing is attached,
-    allocated or launched, the capture is the one without it."""
+    allocated or launched, the capture is the one without it.  (An accumulating optimizer: see GraphedStep and `step_tail`.)"""
 
     def __init__(self, model, example_input, example_seg, grad_buffer, warmup=3, ignore_index=None, optimizer=None, assign="host",
                  log=None, firing=None):
@@ -395,12 +399,9 @@ class GraphedHungarianStep(_Captured):
             head()
             tail()
         self._graphs = self._capture(warm, warmup, [head, tail] if self.two_graphs else [whole])
-        self._bind_log()
         for name, graph in zip(("graph", "graph_tail") if assign == "device" else ("graph_a", "graph_b"), self._graphs):
             setattr(self, name, graph)
-        if self.firing is not None:
-            self.firing.clear()                              # (the warm-up passes' spikes are not row 0)
-        self._clear_grad_log()
+        self._after_capture()
         if assign == "device":
             self.sticky.zero_()                              # (whatever the warm-up on the example inputs left is not a replay's)
             torch.cuda.synchronize()

@@ -112,11 +112,10 @@ def train_log_append(srcs, ring, head, table=None, n=None):
 
 def firing_log_append(counters, ring, silent, head, patience):
     """One row of firing counters (s2f_firing_log_append).  counters: int64 [n, STAT_SLOTS, 2], ONE contiguous allocation whose
-    slice i is neuron i's `stats`; ring: int64 [window, n, 2]; silent: int32 [n]; head: int64 [4] = {rows appended, first dead
-    neuron as row * 2^32 + i or -1, the kernel's ticket word (0 between launches), reserved}.  Per neuron: {sum of counts, non-zero
-    counts} over the slots -> ring[head[0] % window, i]; the counters are cleared; silent[i] == -1 (not watched) stays, otherwise
-    it counts the rows in a row whose sum was 0; the first neuron whose streak reaches `patience` is latched in head[1] (the lowest
-    index of the earliest row).  head[0] += 1.  One launch on the current stream, no synchronisation; capturable."""
+    slice i is neuron i's `stats`; ring: int64 [window, n, 2]; silent: int32 [n]; head: int64 [4], the head of devring.py.  Per
+    neuron: {sum of counts, non-zero counts} over the slots -> ring[head[0] % window, i]; the counters are cleared; silent[i] == -1
+    (not watched) stays, otherwise it counts the rows in a row whose sum was 0; the first neuron whose streak reaches `patience` is
+    latched in head[1] (the lowest index of the earliest row).  head[0] += 1.  One launch on the current stream; capturable."""
     if counters.dtype != torch.int64 or counters.dim() != 3 or tuple(counters.shape[1:]) != (STAT_SLOTS, 2) or not counters.is_contiguous():
         raise ValueError(f"firing_log_append: counters is a contiguous int64 [n, {STAT_SLOTS}, 2]")
     n = counters.shape[0]
@@ -169,8 +168,8 @@ def grad_log_append(slots, spans, hyper, state, flat, exp_avg, exp_avg_sq, parti
     """One row of per-parameter gradient figures (s2f_grad_log_partials -> s2f_grad_log_rows), behind s2f_adamw_step.  slots int64
     [n, 3], hyper fp32 [n, 2], state fp32 [>= 5], flat / exp_avg / exp_avg_sq fp32 flat buffers of one length: FlatAdamW's, after the
     update; spans: `grad_log_table(slots)`; partials int64 [nspans, 8] (workspace); ring int64 [window, n, 8]; streak int32 [n, 2];
-    head int64 [4] = {rows appended, first stalled parameter as row * 2^32 + i or -1, the kernel's ticket word, first parameter with
-    a non-finite gradient element or -1}.  Row head[0] % window <- per parameter {sum g^2, sum p^2, sum u^2, max |g| as doubles'
+    head int64 [4], the head of devring.py: head[1] latches the first stalled parameter, head[3] the first with a non-finite
+    gradient element.  Row head[0] % window <- per parameter {sum g^2, sum p^2, sum u^2, max |g| as doubles'
     bits; g == 0, non-finite g, non-finite p or u, numel} (include/s2f.h "gradient log"); head[0] += 1.  Two launches on the current
     stream, no synchronisation, capturable; everything but partials, ring, streak and head is only read.  HIP only: CPU tensors
     raise."""

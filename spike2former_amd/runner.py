@@ -9,8 +9,8 @@
 `graph.GraphedHungarianStep(assign="device", optimizer=FlatAdamW(...))` is a whole iteration that never waits for the GPU; three
 things a loop needs would each put a host stop back into it, and each has a device-side piece here instead:
 
-  * the losses `step()` returns are static tensors, valid until the next call: `TrainLog` is a ring ON THE DEVICE that the step's
-    last graph appends one row to per replay (ops.train_log_append); the host reads it back once per log interval, one copy;
+  * the losses `step()` returns are static tensors, valid until the next call: `TrainLog` is a ring on the device (devring.py) that
+    the step's last graph appends one row to per replay (ops.train_log_append);
   * a checkpoint of ~1 000 parameter and buffer tensors behind a pointer table: `TrainState.snapshot()` is ONE launch into a staging
     buffer (ops.state_copy) plus three device-to-device copies, all queued on the step's stream -- the next replay may start at
     once; the copy to pinned memory runs on a side stream, `torch.save` in a writer thread;
@@ -42,6 +42,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .devring import DeviceRing, unwrap
+from .graph import step_tail
 from .registry import HOOKS
 
 logger = logging.getLogger("spike2former_amd")
@@ -69,14 +71,15 @@ def noise_scale(micro_sq, accum_sq, small, big):
     return (s / g2 if g2 > 0 else None), g2, s
 
 
-class TrainLog:
-    """A ring of the last `window` iterations' scalars on the device.  `terms`: ordered {name: one-element fp32 tensor}, static
-    tensors of a captured step (its losses, their sum, the optimizer's grad_norm and clip_coef).  `append()` is one launch
-    (capturable) that copies them into the next row; `read()` is one device-to-host copy.
+class TrainLog(DeviceRing):
+    """A devring.DeviceRing of the last `window` iterations' scalars: fp32 [window, capacity], no state words; head[1] latches the
+    first row with a non-finite value.  `terms`: ordered {name: one-element fp32 tensor}, static tensors of a captured step (its
+    losses, their sum, the optimizer's grad_norm and clip_coef).  `append()` is one launch that copies them into the next row.
 
     A captured step knows its static tensors only while it is being recorded, where nothing may be uploaded: build the log without
     terms (`TrainLog(window=..., device=...)`, at most `capacity` of them), hand it to the step (`log=`), and the step `declare`s the
     names while recording -- the recorded launch reads a pointer table that `bind` fills after the capture."""
+    HEAD = (0, -1)
 
     def __init__(self, terms=None, window=64, device=None, capacity=64):
         if window < 1:
@@ -86,20 +89,13 @@ class TrainLog:
             device = next(iter(terms.values())).device if device is None else device
         if not 1 <= capacity <= ops.TRAIN_LOG_MAX_TERMS:
             raise ValueError(f"TrainLog: {capacity} terms outside 1 .. {ops.TRAIN_LOG_MAX_TERMS}")
-        self.device = torch.device("cuda" if device is None else device)
         self.window, self.stride = int(window), int(capacity)
-        # head (int64 [2], four words) and ring in ONE allocation: read() is one copy
-        self._buf = torch.zeros(4 + self.window * self.stride, dtype=torch.float32, device=self.device)
-        self.head, self.ring = self._buf[:4].view(torch.int64), self._buf[4:].view(self.window, self.stride)
-        self.head[1] = -1
-        self._host = torch.zeros_like(self._buf, device="cpu")
-        self._table = self._event = None
-        if self.device.type == "cuda":
-            self._host = self._host.pin_memory()
-            self._table = torch.zeros(self.stride, dtype=torch.int64, device=self.device)
-            self._event = torch.cuda.Event()
+        cells = self.window * self.stride
+        _, ring = self._allocate(0, (cells + 1) // 2, "cuda" if device is None else device)
+        self.ring = ring.view(torch.float32)[:cells].view(self.window, self.stride)
+        self.clear()
+        self._table = torch.zeros(self.stride, dtype=torch.int64, device=self.device) if self.device.type == "cuda" else None
         self.names, self._srcs = None, None
-        self.base = 0          # the iterations that ran before row 0 (a resumed run)
         if terms is not None:
             self.bind(terms)
 
@@ -122,24 +118,17 @@ class TrainLog:
             raise RuntimeError("TrainLog.append before its terms are declared")
         if self._table is None and self._srcs is None:
             raise RuntimeError("TrainLog.append on the CPU before its terms are bound")
-        ops.train_log_append(self._srcs, self.ring, self.head, table=self._table, n=len(self.names))
+        ops.train_log_append(self._srcs, self.ring, self.head[:2], table=self._table, n=len(self.names))
 
     def read(self):
         """-> LogRead(names, rows, count, first_nonfinite): the last min(count, window) rows, oldest first, as numpy fp32
         [rows, terms]; the number of rows appended so far; the index (from 0) of the first row that held a non-finite value, or
-        None.  One device-to-host copy on the current stream, and a wait for that copy."""
-        if self._event is not None:
-            self._host.copy_(self._buf, non_blocking=True)
-            self._event.record()
-            self._event.synchronize()
-        else:
-            self._host.copy_(self._buf)
-        head = self._host[:4].view(torch.int64)
-        count, bad = int(head[0]), int(head[1])
-        n, k = len(self.names or ()), min(count, self.window)
-        ring = self._host[4:].view(self.window, self.stride).numpy()
-        rows = np.stack([ring[(count - k + i) % self.window, :n] for i in range(k)]) if k else np.zeros((0, n), np.float32)
-        return LogRead(list(self.names or ()), rows.copy(), count, None if bad < 0 else bad)
+        None.  One `fetch()`."""
+        words = self.fetch()
+        count, bad = int(words[0]), int(words[1])
+        ring = words[4:].view(np.float32)[:self.window * self.stride].reshape(self.window, self.stride)
+        rows = unwrap(ring, count, self.window)[:, :len(self.names or ())]
+        return LogRead(list(self.names or ()), np.ascontiguousarray(rows), count, None if bad < 0 else bad)
 
 
 class TrainState:
@@ -410,21 +399,10 @@ class LoggerHook(_Hook):
     allocated device memory in MiB -- one line on the `spike2former_amd` logger and one JSON line in {work_dir}/vis_data/scalars.json.
     A non-finite value in ANY iteration since the last check raises FloatingPointError naming the first (TrainLoop.check_finite).
 
-    A step built with `firing=FiringLog(...)`: ONE `FiringLog.read()` more per log line.  Over the rows appended since the last
-    line (the ring holds at least `interval` of them) the line and scalars.json carry `firing/mean` (the mean rate over the watched
-    neurons), `firing/min` and `firing/min_name` (the neuron with the lowest mean rate) and `firing/silent` (the watched neurons
-    that did not fire in the last row); every neuron's mean rate and non-zero share go to {work_dir}/vis_data/firing.jsonl, one JSON
-    line per log line.  The first time a neuron has stayed silent for the log's `patience` iterations, ONE warning names it and the
-    iteration its streak reached the patience: a finding, not an error -- nothing is raised.  Every rank reads its own rank's
-    counters; rank 0 writes.
-
-    An optimizer built with `grad_log=...` (gradlog.GradLog): ONE `GradLog.read()` more per log line.  Over the rows appended since
-    the last line (the ring holds at least `interval` of them): `grad/min` and `grad/min_name` (the parameter with the lowest mean
-    gradient norm), `grad/max_share` and `grad/max_name` (the parameter holding the largest share of sum g^2: the one the clip is
-    reacting to), `grad/update_ratio_max` and `grad/update_ratio_max_name` (the largest mean |u| / |p|), `grad/zero_share` (the share
-    of gradient elements that are exactly 0) and `grad/stalled` (parameters whose gradient was all zero in the last row); every
-    parameter's figures go to {work_dir}/vis_data/grad.jsonl, one JSON line per log line.  The first time a parameter's gradient has
-    stayed all zero for the log's `patience` iterations, ONE warning names it; nothing is raised.
+    Every ring log of `loop.logs` (a step built with `firing=FiringLog(...)`, an optimizer built with `grad_log=...`): ONE read more
+    per log line, over the rows appended since the last line (the ring holds at least `interval` of them).  Its `report()` says what
+    the line and scalars.json carry (`firing/...`, `grad/...`), the JSON line that goes to {work_dir}/vis_data/{firing,grad}.jsonl
+    and what its latch warns of, ONCE: a finding, not an error -- nothing is raised.  Every rank reads its own rings; rank 0 writes.
 
     An optimizer built with `accumulative_counts=k`: the gradient log's rows count UPDATES (the warning and grad.jsonl name the
     iteration of the update), and the line carries `grad/accum` = k and `grad/noise_scale`, in images: `noise_scale()` of the means
@@ -446,69 +424,10 @@ class LoggerHook(_Hook):
     def before_run(self, loop):
         if loop.log is None:
             raise ValueError("LoggerHook needs a step built with log=TrainLog(...)")
-        if loop.log.window < self.window_size:
-            raise ValueError(f"LoggerHook(window_size={self.window_size}) over a TrainLog of {loop.log.window} rows")
-        if loop.firing is not None and loop.firing.window < self.interval:
-            raise ValueError(f"LoggerHook(interval={self.interval}) over a FiringLog of {loop.firing.window} rows")
-        if getattr(loop, "grad_log", None) is not None and loop.grad_log.window < self.interval:
-            raise ValueError(f"LoggerHook(interval={self.interval}) over a GradLog of {loop.grad_log.window} rows")
-        self._clock, self._last = time.perf_counter(), loop.iter
-        self._dead_seen = self._stalled_seen = False
-
-    def _firing(self, loop, n, record):
-        """the rows since the last line -> the record's firing/ keys and one line of firing.jsonl; the dead-neuron warning"""
-        fl = loop.firing
-        read = fl.read()
-        k = min(n - self._last, len(read.sums), read.count)
-        watched = read.elems > 0
-        if k > 0 and watched.any():
-            rates, nz = read.rates()[-k:].mean(0), read.nonzero()[-k:].mean(0)
-            low = int(np.flatnonzero(watched)[np.argmin(rates[watched])])
-            record["firing/mean"] = float(rates[watched].mean())
-            record["firing/min"], record["firing/min_name"] = float(rates[low]), read.names[low]
-            record["firing/silent"] = int((read.silent[watched] >= 1).sum())
-            if loop.work_dir is not None and loop.rank == 0:
-                path = os.path.join(loop.work_dir, "vis_data", "firing.jsonl")
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                idx = np.flatnonzero(watched)
-                with open(path, "a") as f:
-                    f.write(json.dumps(dict(iter=n, rows=k, rates={read.names[i]: float(rates[i]) for i in idx},
-                                            nonzero={read.names[i]: float(nz[i]) for i in idx})) + "\n")
-        if read.first_dead is not None and not self._dead_seen:
-            self._dead_seen = True
-            row, name = read.first_dead
-            logger.warning(f"neuron {name} has not fired for {fl.patience} iterations, up to iteration {fl.base + row + 1}")
-
-    def _grad(self, loop, n, record):
-        """the gradient log's rows since the last line -> the record's grad/ keys and one line of grad.jsonl; the stalled warning"""
-        gl = loop.grad_log
-        read = gl.read()
-        k = len(read.cols)
-        if loop.accum is not None:          # the rows count updates: the line is named after the last update it holds
-            n = loop.update_iteration(gl.base + read.count)
-        if k > 0:
-            sq = read.grad_sq.sum(0)
-            norm, ratio = read.grad_norm.mean(0), read.update_ratio.mean(0)
-            low, top, far = int(np.argmin(norm)), int(np.argmax(sq)), int(np.argmax(ratio))
-            elems = float(read.numel.sum())
-            record["grad/min"], record["grad/min_name"] = float(norm[low]), read.names[low]
-            record["grad/max_share"], record["grad/max_name"] = float(sq[top] / sq.sum()) if sq.sum() > 0 else 0.0, read.names[top]
-            record["grad/update_ratio_max"], record["grad/update_ratio_max_name"] = float(ratio[far]), read.names[far]
-            record["grad/zero_share"] = float(read.cols[:, :, 4].sum()) / elems if elems else 0.0
-            record["grad/stalled"] = int((read.streak[:, 0] >= 1).sum())
-            if loop.work_dir is not None and loop.rank == 0:
-                path = os.path.join(loop.work_dir, "vis_data", "grad.jsonl")
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                per = dict(grad_norm=norm, weight_norm=read.weight_norm.mean(0), update_ratio=ratio, grad_max=read.grad_max.max(0),
-                           zero_share=read.zero_share.mean(0))
-                with open(path, "a") as f:
-                    f.write(json.dumps(dict(iter=n, rows=k, **{key: {name: float(v) for name, v in zip(read.names, vals)}
-                                                               for key, vals in per.items()})) + "\n")
-        if read.first_stalled is not None and not self._stalled_seen:
-            self._stalled_seen = True
-            row, name = read.first_stalled
-            logger.warning(f"parameter {name} has had an all-zero gradient for {gl.patience} iterations, up to iteration "
-                           f"{loop.update_iteration(gl.base + row + 1)}")
+        for log, what, rows in ((loop.log, "window_size", self.window_size), *((log, "interval", self.interval) for log, _ in loop.logs)):
+            if log.window < rows:
+                raise ValueError(f"LoggerHook({what}={rows}) over a {type(log).__name__} of {log.window} rows")
+        self._clock, self._last, self._warned = time.perf_counter(), loop.iter, set()          # (the logs whose latch was reported)
 
     def _accum(self, loop, n, read, record):
         """grad/accum and grad/noise_scale (see the class); `read`: the TrainLog as of iteration n, whose last row is iteration n"""
@@ -527,13 +446,17 @@ class LoggerHook(_Hook):
         if ratio is not None:
             record["grad/noise_scale"] = float(ratio)
 
-    def _emit(self, loop, record, line):
-        logger.info(line)
+    def _write(self, loop, name, record):
+        """one JSON line more in {work_dir}/vis_data/{name}; rank 0 alone writes"""
         if loop.work_dir is not None and loop.rank == 0:
-            path = os.path.join(loop.work_dir, "vis_data", "scalars.json")
+            path = os.path.join(loop.work_dir, "vis_data", name)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             with open(path, "a") as f:
                 f.write(json.dumps(record) + "\n")
+
+    def _emit(self, loop, record, line):
+        logger.info(line)
+        self._write(loop, "scalars.json", record)
 
     def after_train_iter(self, loop):
         n = loop.iter + 1
@@ -548,10 +471,14 @@ class LoggerHook(_Hook):
         for j, name in enumerate(read.names):
             if name not in self.HIDDEN and len(rows):
                 record[name] = float(np.mean(np.ascontiguousarray(rows[:, j])))          # fp32, in the rows' order
-        if loop.firing is not None:
-            self._firing(loop, n, record)
-        if getattr(loop, "grad_log", None) is not None:
-            self._grad(loop, n, record)
+        for log, iteration_of in loop.logs:
+            keys, items, warning = log.report(n, self._last, iteration_of)
+            record.update(keys)
+            if items is not None:
+                self._write(loop, f"{log.prefix}.jsonl", items)
+            if warning is not None and log.prefix not in self._warned:
+                self._warned.add(log.prefix)
+                logger.warning(warning)
         if getattr(loop, "accum", None) is not None:
             self._accum(loop, n, read, record)
         self._clock, self._last = now, n
@@ -702,18 +629,19 @@ class TrainLoop:
         self.log = getattr(step, "log", None)
         self.firing = getattr(step, "firing", None)          # a firing.FiringLog the step appends a row to per replay
         self.grad_log = getattr(optimizer, "grad_log", None)          # a gradlog.GradLog `optimizer.step()` appends a row to
-        # a step that does not hold the optimizer (world size > 1: the all-reduce lies between the replay and the update) is
-        # followed by `step.red.reduce()` and `optimizer.step()` here, and the log's row by an eager append behind them
-        self.eager_update = hasattr(step, "red") and getattr(step, "optimizer", None) is None
-        self.eager_append = self.log is not None and not getattr(step, "log_captured", True)
         self.accum = getattr(optimizer, "accum", None)          # a train.GradAccum: FlatAdamW(accumulative_counts=k), k > 1
-        if self.accum is not None:
-            if getattr(step, "optimizer", None) is not optimizer:
-                raise ValueError("TrainLoop: an optimizer with accumulative_counts > 1 has to be the step's own (optimizer=...): "
-                                 "the step accumulates behind its packing")
-            # at world size 1 the step updates and appends by itself, behind its replay; beyond, it stops behind the accumulation
-            self.eager_update = self.world > 1
-            self.eager_append = self.log is not None and self.world > 1
+        own = getattr(step, "optimizer", None)
+        if self.accum is not None and own is not optimizer:
+            raise ValueError("TrainLoop: an optimizer with accumulative_counts > 1 has to be the step's own (optimizer=...): "
+                             "the step accumulates behind its packing")
+        # what graph.step_tail leaves to the caller: `step.red.reduce()`, `optimizer.step()` (`accum.finish()`), the log's row behind them
+        update, row = step_tail(own is not None, self.accum is not None, self.world)
+        if self.accum is None and hasattr(step, "log_captured"):          # (a step says itself whether its graph holds the row)
+            row = "graph" if step.log_captured else "caller"
+        self.eager_update = update == "caller" and (own is not None or hasattr(step, "red"))
+        self.eager_append = self.log is not None and row == "caller"
+        # the ring logs a LoggerHook reports, in the line's order: (log, the map from its row number to the iteration of that row)
+        self.logs = [(log, of) for log, of in ((self.firing, int), (self.grad_log, self.update_iteration)) if log is not None]
         if self.eager_append:
             self.log.bind({**step.log_terms, "grad_norm": optimizer.grad_norm, "clip_coef": optimizer.clip_coef})
         self.state = TrainState(step.model, optimizer, scheduler, augment, async_write=async_write)
@@ -801,12 +729,9 @@ class TrainLoop:
                     raise ValueError(f"TrainLoop: resumed at iteration {start}, inside a group of accumulative_counts={counts}: the "
                                      f"group's gradients are in no checkpoint")
                 self.accum.total, self.accum.count = self.max_iters, start
-            if self.log is not None:
-                self.log.base = start - self.log.read().count          # row 0 of a fresh log is iteration start + 1
-            if self.firing is not None:          # (the ring and the streaks are in no checkpoint: a resumed run starts them afresh)
-                self.firing.base = start - self.firing.read().count
-            if self.grad_log is not None:        # (neither is the gradient log's ring)
-                self.grad_log.base = start // counts - self.grad_log.read(consume=False).count          # (its rows count updates)
+            for log in (self.log, self.firing, self.grad_log):          # (no ring is in a checkpoint: a resumed run starts them afresh)
+                if log is not None:
+                    log.rebase(start, counts if log is self.grad_log else 1)          # (the gradient log's rows count updates)
             self._call("before_run")
             batches = _cycle(self.batches, start)
             out = (self.step.static_in, self.step.static_seg)

@@ -184,6 +184,7 @@ class FakeAugment:
 
 class FakeGradLog:
     """what the loop sees of a GradLog: scripted rows, one per iteration, read since the last read"""
+    prefix = "grad"
 
     def __init__(self, names, script, window, patience, stalled=None):
         self.names, self.script, self.window, self.patience, self.base = names, script, window, patience, 0
@@ -207,6 +208,13 @@ class FakeGradLog:
             self._last = read.count
             self.reads += 1
         return read
+
+    def rebase(self, start, unit=1):
+        self.base = start // unit - self.count
+
+    def report(self, *args):          # (GradLog's own, over this fake's read)
+        from spike2former_amd import GradLog
+        return GradLog.report(self, *args)
 
 
 class FakeStep:
