@@ -3,6 +3,7 @@ import torch
 
 from .config import cfg
 from .core import *          # noqa: F401,F403  (the shared plumbing: _ptr, _stream, check, lib, Spikes, ...)
+from .resize import upsample_bilinear
 
 
 # ------------------------------------------------------------------------------------------------ BN (+bias, +residual, +LIF)
@@ -95,9 +96,7 @@ class _BNAct(torch.autograd.Function):
         ctx.mark_non_differentiable(border, ydata, *[o for o, t in zip(outs, (u, y, v_out)) if t is None])
         if tok2.numel() == 0:
             ctx.mark_non_differentiable(tok2)
-        through = up_in if (up_in is not None and up_skip) else z.new_empty(0)
-        if through is not up_in:
-            ctx.mark_non_differentiable(through)
+        through = _pass_through(ctx, z if up_in is None else up_in, up_skip and up_in is not None)
         return tuple(outs) + (border, ydata, tok2, through)
 
     @staticmethod
@@ -249,7 +248,6 @@ def bn_act(z, conv_bias, gamma, beta, running_mean, running_var, nbt, training, 
         if bn_up_ok(z, residual_lo, training, D):
             up_lo = residual_lo
         else:
-            from .misc import upsample_bilinear
             residual = upsample_bilinear(residual_lo, z.shape[-2:], skip=lo_skip)
             if lo_skip:
                 residual, through = residual

@@ -125,17 +125,46 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _need_cuda(*ts, spikes=None):
-    for t in ts:
+def _need_cuda(*ts, spikes=None, fp32=True):
+    """every tensor given (None: skipped) lies in device memory and is fp32 -- `spikes`: fp32 or bf16; fp32=False: of any dtype"""
+    for t in ts + (spikes,):
         if t is not None and not t.is_cuda:
             raise RuntimeError("spike2former_amd ops run on the GPU only (HIP kernels); got a CPU tensor")
-        if t is not None and t.dtype != torch.float32:
+        if t is not None and t is spikes and t.dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError(f"a spike operand is fp32 or bf16; got {t.dtype}")
+        if t is not None and t is not spikes and fp32 and t.dtype != torch.float32:
             raise RuntimeError(f"spike2former_amd ops compute in fp32; got {t.dtype}")
-    if spikes is not None:
-        if not spikes.is_cuda:
-            raise RuntimeError("spike2former_amd ops run on the GPU only (HIP kernels); got a CPU tensor")
-        if spikes.dtype not in (torch.float32, torch.bfloat16):
-            raise RuntimeError(f"a spike operand is fp32 or bf16; got {spikes.dtype}")
+
+
+def _pass_through(ctx, x_in, skip):
+    """The forward half of the pass-through port (cfg.FANOUT_PORTS), a Function's last output: x_in as the op received it, for a second
+    reader whose gradient the op's adjoint kernel sums (autograd hands out a view of it), or without `skip` an empty stand-in."""
+    if skip:
+        return x_in
+    aux = x_in.new_empty(0)
+    ctx.mark_non_differentiable(aux)
+    return aux
+
+
+def _pass_through_function(name, doc, launch, launch_bwd_add):
+    """-> the autograd.Function `name` of an op whose only differentiable input is x: apply(x, skip, *args) -> (y, pass-through of x).
+    The whole protocol of the port is here; the op supplies  launch(x, *args) -> y  on a contiguous fp32 CUDA x and
+    launch_bwd_add(gy, gskip, gx, *args):  gx (of x's shape) <- the adjoint of y plus gskip (both contiguous; gskip None: a null addend)."""
+
+    def forward(ctx, x, skip, *args):
+        _need_cuda(x)
+        ctx.x_shape, ctx.args = x.shape, args
+        ctx.set_materialize_grads(False)
+        return launch(x.contiguous(), *args), _pass_through(ctx, x, skip)
+
+    def backward(ctx, gy, gskip):
+        if gy is None:          # only the pass-through sent a gradient
+            return (gskip, None) + (None,) * len(ctx.args)
+        gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=gy.device)
+        launch_bwd_add(gy.contiguous(), None if gskip is None else gskip.contiguous(), gx, *ctx.args)
+        return (gx, None) + (None,) * len(ctx.args)
+
+    return type(name, (torch.autograd.Function,), {"__doc__": doc, "forward": staticmethod(forward), "backward": staticmethod(backward)})
 
 
 # Gradient sinks: {parameter data_ptr: fp32 view of a pre-zeroed flat gradient buffer}.  When a weight has a sink, the
@@ -323,8 +352,6 @@ def branches(fns, inputs=()):
     return out
 
 
-
-
 def fork(which, fn, inputs=(), what=None):
     """Launch fn() on cfg.LONG_STREAMS[which] behind everything enqueued so far -> (result, handle); `join(handle, result)`
     before the current stream reads the result.  Without side streams: runs inline, handle None."""
@@ -487,8 +514,6 @@ def _grad_pair(ctx_has_tok, g):
     return (None, g) if ctx_has_tok else (g, None)
 
 
-
-
 # ------------------------------------------------------------------------------------------------ parameter groups
 def adjacent(ts):
     """True when the tensors lie back to back in ONE storage (same dtype / device, contiguous): their concatenation along
@@ -575,8 +600,6 @@ class _Split3(torch.autograd.Function):
 
 def split3(y):
     return _Split3.apply(y)
-
-
 
 
 # ------------------------------------------------------------------------------------------------ operand census taps

@@ -6,7 +6,8 @@ import torch
 
 from .config import cfg
 from .core import *          # noqa: F401,F403  (the shared plumbing: _ptr, _stream, check, lib, Spikes, ...)
-from .misc import channel_sum, transpose_last2
+from .layout import transpose_last2
+from .reduce import channel_sum
 from .wcache import pack_weight, pack_weight_conv3, split_weight          # the cached bf16 conversions of the weights
 
 

@@ -31,7 +31,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 from .._lib import check, lib
 from .config import cfg
-from .misc import _dense_flat
+from .reduce import _dense_flat
 
 aten = torch.ops.aten
 

@@ -3,7 +3,7 @@ import torch
 
 from .config import cfg
 from .core import *          # noqa: F401,F403  (the shared plumbing: _ptr, _stream, check, lib, Spikes, ...)
-from .misc import channel_sum, sum_lead
+from .reduce import channel_sum, sum_lead
 
 
 # ------------------------------------------------------------------------------------------------ LIF
@@ -36,7 +36,7 @@ class _LIF(torch.autograd.Function):
         if v_out is None:
             v_out = x.new_empty(0)
             ctx.mark_non_differentiable(v_out)
-        through = x_in if skip else aux          # (an input returned as it is: autograd hands out a view of it)
+        through = _pass_through(ctx, x_in, skip)
         if bf16:                       # (autograd handle, membrane, bf16 spikes, second handle, pass-through)
             ctx.mark_non_differentiable(y)
             return _new_tok(x), v_out, y, _new_tok(x), through
@@ -161,7 +161,7 @@ class _Sum2LIF(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         aux = x.new_empty(0)
         ctx.mark_non_differentiable(aux)
-        through = x_in if skip else aux
+        through = _pass_through(ctx, x_in, skip)
         if bf16:
             ctx.mark_non_differentiable(yk, yv)
             return _new_tok(x), _new_tok(x), yk, yv, _new_tok(x), _new_tok(x), through

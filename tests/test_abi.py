@@ -48,6 +48,28 @@ def test_ctypes_table_matches_header():
         assert len(args) == d[name], f"{name}: ctypes has {len(args)} args, header has {d[name]}"
 
 
+def test_mirrored_constants_match_the_header():
+    """The constants of include/s2f.h that the op layer copies by hand, each against its `#define S2F_<NAME> <integer>` line."""
+    import torch
+    from spike2former_amd import ops
+    src = open(os.path.join(ROOT, "include", "s2f.h")).read()
+    header = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define S2F_(\w+)[ \t]+(\d+)[ \t]*$", src, flags=re.M)}
+    mirrors = {
+        "STAT_SLOTS": ops.STAT_SLOTS, "RESIZE_ALIGN_CORNERS": ops.RESIZE_ALIGN_CORNERS, "RESIZE_SIGMOID": ops.RESIZE_SIGMOID,
+        "RESIZE_FLIP_H": ops.RESIZE_FLIP_H, "RESIZE_FLIP_V": ops.RESIZE_FLIP_V,
+        "SEG_HIST_MAX_CLASSES": ops.SEG_HIST_MAX_CLASSES, "SEG_CONF_LDS_BYTES": ops.SEG_CONF_LDS_BYTES,
+        "SEG_CONF_GLOBAL": ops._SEG_CONF_GLOBAL, "SEG_DRAW_BGR": ops._SEG_DRAW_BGR,
+        "AUG_CANDIDATES": ops.AUG_CANDIDATES, "AUG_MAX_CROP": ops.AUG_MAX_CROP, "LSA_MAX_QUERIES": ops.LSA_MAX_QUERIES,
+        "LSA_MAX_CLASSES": ops.LSA_MAX_CLASSES, "LSA_TILE_L2": ops.LSA_TILE_L2,
+        "CENSUS_FIELDS": ops.CENSUS_FIELDS, "CENSUS_F32": ops._CENSUS_DTYPES[torch.float32],
+        "CENSUS_BF16": ops._CENSUS_DTYPES[torch.bfloat16], "TRAIN_LOG_MAX_TERMS": ops.TRAIN_LOG_MAX_TERMS,
+    }
+    assert len(ops._CENSUS_DTYPES) == 2
+    for name, value in mirrors.items():
+        assert name in header, f"include/s2f.h has no integer #define S2F_{name}"
+        assert type(value) is int and value == header[name], f"ops mirrors S2F_{name} as {value!r}, include/s2f.h says {header[name]}"
+
+
 def test_argument_errors_are_reported_without_a_gpu():
     """Validation happens before any launch, so the error convention can be checked on CPU."""
     from spike2former_amd._lib import lib

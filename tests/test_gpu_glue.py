@@ -215,6 +215,59 @@ def test_upsample2x_pass_through_port(N, C, h, w):
     assert (out[1].double() - (xd.grad + gs.double())).abs().max().item() <= 2e-6
 
 
+def _port_transpose(ops, x):
+    return ops.transpose_last2(x, skip=True)
+
+
+def _port_up2x(ops, x):
+    return ops.upsample_bilinear(x, (2 * x.shape[-2], 2 * x.shape[-1]), skip=True)
+
+
+PORT_OPS = {
+    "transpose_16B_ragged": (_port_transpose, (2, 65, 68)),          # 16-byte form, ragged against the 64 x 64 tile both ways
+    "transpose_scalar": (_port_transpose, (2, 5, 7)),
+    "up2x_float4": (_port_up2x, (1, 2, 4, 8)),
+    "up2x_scalar": (_port_up2x, (1, 2, 3, 6)),
+    "resize": (lambda ops, x: ops.resize_bilinear(x, (9, 4), align_corners=False, skip=True), (1, 2, 5, 7)),
+    "resize_align_corners": (lambda ops, x: ops.resize_bilinear(x, (9, 4), align_corners=True, skip=True), (1, 2, 5, 7)),
+}
+
+
+@pytest.mark.parametrize("pattern", ["both", "y_only", "through_only"])
+@pytest.mark.parametrize("name", list(PORT_OPS))
+def test_pass_through_port_gradient_patterns(name, pattern):
+    """The three ops that share the pass-through protocol (transpose_last2, the exact-2x upsample_bilinear, resize_bilinear; skip=True)
+    with a gradient on both outputs, on y alone and on the pass-through alone: the input gradient with ops.FANOUT_PORTS on equals the
+    one with it off bit for bit.  Only y: both settings run the same adjoint kernel with a null addend; only the pass-through: both
+    return the incoming gradient; both: the adjoint kernel's sum is the engine's."""
+    from spike2former_amd import ops
+    op, shape = PORT_OPS[name]
+    g = torch.Generator().manual_seed(len(name) * 7 + len(pattern))
+    x = torch.randn(shape, generator=g)
+    out = []
+    for on in (False, True):
+        was = ops.FANOUT_PORTS
+        ops.FANOUT_PORTS = on
+        try:
+            xc = x.cuda().requires_grad_(True)
+            y, xs = op(ops, xc)
+            assert (xs is not xc) == on
+            if not out:
+                gy = (torch.randn(y.shape, generator=g) * 0.25).cuda()
+                gs = (torch.randn(shape, generator=g) * 0.25).cuda()
+            loss = 0.0
+            if pattern != "through_only":
+                loss = loss + (y * gy).sum()
+            if pattern != "y_only":
+                loss = loss + (xs * gs).sum()
+            loss.backward()
+            out.append(xc.grad.cpu())
+        finally:
+            ops.FANOUT_PORTS = was
+    assert torch.isfinite(out[0]).all() and out[0].abs().max().item() > 0
+    assert torch.equal(out[0].view(torch.int32), out[1].view(torch.int32))
+
+
 # ============================================================================================== section 2: every GlueMode route
 def _g():
     from spike2former_amd import ops
