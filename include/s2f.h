@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 51
+#define S2F_ABI_VERSION 52
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -1065,6 +1065,37 @@ int s2f_grad_log_partials(const int64_t* slots, const float* hyper, const int32_
                           const float* v, const float* state, float eps, int64_t* partials, void* stream);
 int s2f_grad_log_rows(const int32_t* spans, int nspans, const int64_t* partials, int n, int64_t* ring, int window, int32_t* streak,
                       int patience, int64_t* head, void* stream);
+
+/* ---- weight averaging: an exponential moving average of the parameters behind the update (csrc/ema.hip, ABI 52) -------------------
+ * mmengine's EMAHook with ExponentialMovingAverage / ExpMomentumEMA (custom_hooks = [dict(type='EMAHook', ...)]) is one lerp_ per
+ * parameter tensor and iteration on the host's side of the step; here it is one table-driven launch behind s2f_adamw_step, one
+ * workgroup per chunk.  slots int64 [nslots][3] = {parameter pointer (fp32, 4-byte aligned at least), slot offset in `ema` (elements,
+ * % 4 == 0), numel}, chunks int32 [nchunks][2] = {slot, first element}: the tables of s2f_adamw_step.  `ema`: an fp32 flat buffer in
+ * the layout of the moments, 16-byte aligned.  16-byte accesses where both addresses of a chunk are 16-byte aligned, word by word
+ * otherwise and in a chunk's last partial group; elements of `ema` outside the slots are never written.
+ *   s2f_ema_update   state: the optimizer's float[8]; behind s2f_adamw_prepare state[4] = t is the 1-based count of THIS update (an fp32
+ *                    holds it exactly up to 2^24 updates; past that the count, and with it the decision below, stops moving).  Every
+ *                    workgroup derives the same decision from t, begin and interval (mmengine 0.8.4: EMAHook._ema_started,
+ *                    BaseAveragedModel.update_parameters):
+ *                        c = t - max(begin, 1)            the started updates before this one
+ *                        c <= 0                           e = p, bit for bit (not started, or the first started update)
+ *                        c > 0, c % interval != 0         nothing is touched: ema and partials stay as they were
+ *                        otherwise                        m = table[min(c, ntable - 1)];  e = fl(e + fl(m * fl(p - e)))
+ *                    -- three fp32 operations, each rounded to nearest even on its own (never contracted), denormals kept; a NaN
+ *                    result is stored as the ONE quiet NaN 0x7fc00000, whatever the operands' payloads were, so that the result's bits
+ *                    are a function of the operands' VALUES alone.  table: fp32 [ntable] momenta, computed by the host in fp64 and
+ *                    rounded once; the device evaluates no exp.  partials?: double [nchunks][2], row i <- {sum ((double)p - (double)e)^2,
+ *                    sum (double)e^2} over chunk i's elements after the update (fp64 per thread, a tree of fixed shape, plain stores:
+ *                    bit-repeatable); overwritten by every update that is not skipped.
+ *                    S2F_EINVAL: null pointer, nchunks < 1, ntable < 1, begin < 0, interval < 1; S2F_EALIGN: ema not 16-byte, partials
+ *                    not 8-byte aligned.
+ *   s2f_ema_swap     every parameter <-> its slot of `ema`.  Bits: no arithmetic, NaN payloads survive; twice is the identity.
+ *                    S2F_EINVAL: null pointer, nchunks < 1; S2F_EALIGN: ema not 16-byte aligned.
+ * Loading and saving the buffer needs no entry point of its own: for fp32 parameters s2f_state_copy's word-counted tables ARE these
+ * tables.  Neither call allocates, synchronises or uses atomics: both can be captured. */
+int s2f_ema_update(const int64_t* slots, const int32_t* chunks, int nchunks, float* ema, const float* state, const float* table,
+                   int ntable, int begin, int interval, double* partials, void* stream);
+int s2f_ema_swap(const int64_t* slots, const int32_t* chunks, int nchunks, float* ema, void* stream);
 
 /* ---- operand census: what a synaptic op really reads (csrc/opcensus.hip, ABI 49) -----------------------------------------------------
  * The reference's tools/cal_firing_num.py stops at firing rates per neuron (fr_rate.csv) and leaves operations and energy to a

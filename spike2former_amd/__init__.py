@@ -25,6 +25,7 @@ from .metrics import ConfusionMatrix, IoUMetric, evaluate  # noqa: F401
 from .augment import TestAugment, TrainAugment  # noqa: F401
 from .visualization import SegLocalVisualizer, SegVisualizationHook  # noqa: F401
 from .train import LinearThenPoly, OptimWrapper, parse_losses, train_step  # noqa: F401
-from .runner import CheckpointHook, LoggerHook, ParamSchedulerHook, TrainLog, TrainLoop, TrainState  # noqa: F401
+from .ema import WeightEMA  # noqa: F401
+from .runner import CheckpointHook, EMAHook, LoggerHook, ParamSchedulerHook, TrainLog, TrainLoop, TrainState  # noqa: F401
 
 __version__ = "0.1.0"

@@ -175,6 +175,8 @@ SIGNATURES = {
     "s2f_bmm_f32": (_i, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _p]),
     "s2f_adamw_step": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, ctypes.c_double, ctypes.c_double, _f, _p]),
     "s2f_state_copy": (_i, [_p, _p, _i, _p, _i, _p]),
+    "s2f_ema_update": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "s2f_ema_swap": (_i, [_p, _p, _i, _p, _p]),
     "s2f_train_log_append": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "s2f_firing_log_append": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
     "s2f_operand_census": (_i, [_p, _i, _i64, _i, _p, _p]),

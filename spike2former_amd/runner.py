@@ -140,7 +140,13 @@ class TrainState:
     replay of the step may be queued at once: it can overtake nothing, the stagings are written before it in stream order.
     `write(path, meta)` hands the pinned buffers to ONE writer thread, which waits for the side stream's event and `torch.save`s
     views of them; a following `snapshot()`, `load()` or `close()` joins a write still running (`async_write=False`: written by
-    the caller)."""
+    the caller).
+
+    An optimizer with a weight average (`FlatAdamW(ema=...)`): the snapshot also copies the average's flat buffer, exactly like the
+    moments, and the file follows mmengine's EMAHook rule -- `state_dict` holds the AVERAGED parameters next to the model's buffers
+    (what `load_from` and inference read), `ema_state_dict` holds `module.<name>` = the training value of every `state_dict` entry
+    and `steps`.  `load(resume=True)` restores both; a file without `ema_state_dict`, and every load without `resume`, starts the
+    average from the loaded weights.  No snapshot while the average is swapped in.  Without an average the file is what it was."""
 
     def __init__(self, model, optimizer, scheduler=None, augment=None, async_write=True):
         self.model, self.optimizer, self.scheduler, self.augment = model, optimizer, scheduler, augment
@@ -153,6 +159,15 @@ class TrainState:
         if optimizer is not None:
             self._opt_dev = [torch.empty_like(t) for t in (optimizer.exp_avg, optimizer.exp_avg_sq, optimizer.state)]
             self._opt_host = [self._pinned(torch.zeros_like(t, device="cpu")) for t in self._opt_dev]
+        self._ema_dev = self._ema_host = None
+        if self.ema is not None:
+            self._ema_dev = torch.empty_like(self.ema.ema)
+            self._ema_host = self._pinned(torch.zeros_like(self._ema_dev, device="cpu"))
+
+    @property
+    def ema(self):
+        """the optimizer's ema.WeightEMA (FlatAdamW(ema=...)), or None"""
+        return getattr(self.optimizer, "ema", None)
 
     # ------------------------------------------------------------------------------------------------ tables
     def _tensors(self):
@@ -207,6 +222,9 @@ class TrainState:
         """Queue a copy of the whole state as it is in stream order NOW.  `tag`: a snapshot with the tag of the last one (not None)
         is that one -- two files of one iteration share one copy.  `rng`: what `host_state()` returned (default: it is called
         here, which at world size > 1 every rank has to do)."""
+        ema = self.ema
+        if ema is not None and ema.swapped:
+            raise RuntimeError("TrainState.snapshot while the averaged weights are swapped in (WeightEMA.restore() first)")
         if tag is not None and tag == self._tag:
             return
         self.join()          # the views of the file being written alias the pinned buffers
@@ -223,6 +241,10 @@ class TrainState:
                 raise RuntimeError("TrainState: the optimizer's buffers were laid out again (FlatAdamW.rebuild()); build a new TrainState")
             for dst, src in zip(self._opt_dev, (opt.exp_avg, opt.exp_avg_sq, opt.state)):
                 dst.copy_(src, non_blocking=True)
+        if ema is not None:
+            if self._ema_dev.shape != ema.ema.shape:
+                raise RuntimeError("TrainState: the weight average was laid out again (FlatAdamW.rebuild()); build a new TrainState")
+            self._ema_dev.copy_(ema.ema, non_blocking=True)
         if cuda:
             if self._side is None:
                 self._side, self._staged, self._copied = torch.cuda.Stream(), torch.cuda.Event(), torch.cuda.Event()
@@ -233,17 +255,21 @@ class TrainState:
                 if opt is not None:
                     for dst, src in zip(self._opt_host, self._opt_dev):
                         dst.copy_(src, non_blocking=True)
+                if ema is not None:
+                    self._ema_host.copy_(self._ema_dev, non_blocking=True)
                 self._copied.record(self._side)
         else:
             self.host_flat.copy_(self.flat)
             if opt is not None:
                 for dst, src in zip(self._opt_host, self._opt_dev):
                     dst.copy_(src)
+            if ema is not None:
+                self._ema_host.copy_(self._ema_dev)
         # what lives on the host is taken now: the loop moves both on while the file is written
         self._host_side = dict(t=None if self.scheduler is None else int(self.scheduler.t),
                                rng=self.host_state() if rng is None else rng,
                                names=list(self.names), spans=list(self._spans),
-                               shapes=[(tuple(t.shape), t.dtype) for t in self.tensors],
+                               shapes=[(tuple(t.shape), t.dtype) for t in self.tensors], ema=ema is not None,
                                opt=None if opt is None else [(g["name"], off, tuple(p.shape))
                                                              for g, p, off in zip(opt.param_groups, opt.params, opt.red.offsets)])
         self._tag = tag
@@ -262,6 +288,17 @@ class TrainState:
             out["optimizer"] = dict(step=int(st[4]), state={name: {"exp_avg": m[off:off + int(np.prod(shape))].view(shape),
                                                                    "exp_avg_sq": v[off:off + int(np.prod(shape))].view(shape)}
                                                             for name, off, shape in s["opt"]})
+        if s["ema"]:
+            # mmengine's EMAHook.before_save_checkpoint: `state_dict` is what inference reads, the average; the training values
+            # move to `ema_state_dict` under the averaged model's `module.` prefix, next to its `steps`
+            slot = {name: (off, int(np.prod(shape)), shape) for name, off, shape in s["opt"]}
+            train = collections.OrderedDict(steps=torch.tensor(self.ema.steps(int(self._opt_host[2][4])), dtype=torch.long))
+            for name, t in list(sd.items()):
+                train[f"module.{name}"] = t
+                if name in slot:
+                    off, n, shape = slot[name]
+                    sd[name] = self._ema_host[off:off + n].view(shape)
+            out["ema_state_dict"] = train
         out["param_schedulers"] = [] if s["t"] is None else [dict(t=s["t"])]
         out["augment"] = s["rng"]
         out["best"] = best
@@ -326,14 +363,34 @@ class TrainState:
             shapes += [f"optimizer:{g['name']}: {tuple(om[g['name']][k].shape)} in the file, {tuple(p.shape)} in the model"
                        for g, p in zip(opt.param_groups, opt.params) if g["name"] in om
                        for k in ("exp_avg", "exp_avg_sq") if tuple(om[g["name"]][k].shape) != tuple(p.shape)]
+        # a run with a weight average resumes BOTH copies: the file's `state_dict` is the average, the training values are in its
+        # `ema_state_dict` (see the class); every other load takes `state_dict` and starts the average from it
+        ema = self.ema
+        if ema is not None and ema.swapped:
+            raise RuntimeError("TrainState.load while the averaged weights are swapped in (WeightEMA.restore() first)")
+        esd = ck.get("ema_state_dict") if resume and ema is not None and isinstance(ck, dict) else None
+        src = sd
+        if esd is not None:
+            missing += [f"ema_state_dict:module.{n}" for n in self.names if f"module.{n}" not in esd]
+            shapes += [f"ema_state_dict:module.{n}: {tuple(esd[f'module.{n}'].shape)} in the file, {tuple(t.shape)} in the model"
+                       for n, t in zip(self.names, self.tensors)
+                       if f"module.{n}" in esd and tuple(esd[f"module.{n}"].shape) != tuple(t.shape)]
+            src = {n: esd.get(f"module.{n}") for n in self.names}
         if missing or unexpected or shapes:
             raise RuntimeError(f"{path} does not fit the model -- missing: {missing}; unexpected: {unexpected}; mis-shaped: {shapes}")
         if self._copied is not None:
             self._copied.synchronize()
         for name, t, (off, n) in zip(self.names, self.tensors, self._spans):
-            self.host_flat[off:off + n].copy_(sd[name].to(t.dtype).contiguous().reshape(-1).view(torch.int32))
+            self.host_flat[off:off + n].copy_(src[name].to(t.dtype).contiguous().reshape(-1).view(torch.int32))
         self.flat.copy_(self.host_flat, non_blocking=True)
         ops.state_copy(self.tensors, self.slots, self.chunks, self.flat, to_params=True)
+        if esd is not None:
+            self._ema_host.zero_()
+            for g, p, off in zip(opt.param_groups, opt.params, opt.red.offsets):
+                self._ema_host[off:off + p.numel()].copy_(sd[g["name"]].to(torch.float32).reshape(-1))
+            ema.ema.copy_(self._ema_host, non_blocking=True)
+        elif ema is not None:
+            ema.reset()          # (one launch behind the copy above: the average starts from the loaded weights)
         if resume:
             m, v, _ = self._opt_host
             m.zero_(), v.zero_()
@@ -365,7 +422,7 @@ class TrainState:
         if self.device.type == "cuda":
             torch.cuda.current_stream().synchronize()          # the pinned buffers are free again
         self._tag = None
-        return {k: v for k, v in ck.items() if k not in ("state_dict", "optimizer")} if isinstance(ck, dict) and "state_dict" in ck else {}
+        return {k: v for k, v in ck.items() if k not in ("state_dict", "optimizer", "ema_state_dict")} if isinstance(ck, dict) and "state_dict" in ck else {}
 
 
 # ---------------------------------------------------------------------------------------------------- hooks
@@ -410,7 +467,10 @@ class LoggerHook(_Hook):
     (|g|^2 of the accumulated and all-reduced gradient, k b W images) over the rows of UPDATE iterations since the last line that
     the TrainLog's ring still holds; omitted where no such row is in reach or the estimate of |G|^2 is not positive.  A diagnostic
     without a counterpart in the reference, and approximate: train-mode BatchNorm and the matching couple the images of a
-    micro-batch; at world size > 1 the micro-batch term is this rank's."""
+    micro-batch; at world size > 1 the micro-batch term is this rank's.
+
+    An optimizer built with `ema=...`: the line carries `ema/drift` (|p - e| / |e| over all parameters, as of the last update that
+    touched the average) and `ema/momentum` (that update's), one read of the average's partial sums (ema.WeightEMA.report)."""
     priority = 60
     HIDDEN = ("clip_coef", "grad_sq_micro", "grad_sq_accum")
 
@@ -481,6 +541,9 @@ class LoggerHook(_Hook):
                 logger.warning(warning)
         if getattr(loop, "accum", None) is not None:
             self._accum(loop, n, read, record)
+        ema = getattr(loop.optimizer, "ema", None)
+        if ema is not None:          # ema/drift, ema/momentum: one read of the average's partial sums
+            record.update(ema.report(loop.updates_done(n)))
         self._clock, self._last = now, n
         record.update(iter=n, step=n)
         eta = str(datetime.timedelta(seconds=int(record["eta"])))
@@ -582,6 +645,50 @@ class CheckpointHook(_Hook):
         loop.state.write(self.best_path, meta=loop.meta(), best=self._best(), done=replaced)
 
 
+@HOOKS.register_module()
+class EMAHook(_Hook):
+    """mmengine's EMAHook for a captured step: validation and the checkpoints' `state_dict` use an exponential moving average of
+    the weights (ema.WeightEMA).  The average itself lives in the optimizer -- `FlatAdamW(..., ema=dict(...))` records its launch
+    behind the update, inside the captured step, and a graph holds the launches it was recorded with -- so the hook attaches
+    nothing: `before_run` checks that the optimizer's average is there and was built with THESE arguments (`ema_type` is the
+    average's `type`), `before_val` swaps the averaged weights in and `after_val` swaps the training weights back (TrainLoop
+    guarantees the way back when validation raises).  What the file holds: TrainState."""
+    priority = 50
+
+    def __init__(self, ema_type="ExponentialMovingAverage", momentum=0.0002, gamma=2000, interval=1, begin_iter=0,
+                 update_buffers=False, strict_load=False, **unknown):
+        from .ema import momentum_table
+        if unknown.pop("begin_epoch", 0):
+            raise NotImplementedError("EMAHook(begin_epoch=...): the loop counts iterations")
+        if unknown:
+            raise TypeError(f"EMAHook: unexpected arguments {sorted(unknown)}")
+        if update_buffers:
+            raise NotImplementedError("EMAHook(update_buffers=True): buffers are not averaged")
+        if int(interval) < 1 or int(begin_iter) < 0:
+            raise ValueError(f"EMAHook: interval {interval} below 1 or begin_iter {begin_iter} below 0")
+        momentum_table(ema_type, momentum, gamma)          # (raises for the type, the momentum and a schedule too long for a table)
+        self.args = dict(type=ema_type, momentum=float(momentum), gamma=float(gamma), interval=int(interval),
+                         begin_iter=int(begin_iter), update_buffers=False)
+        self.ema = None
+
+    def before_run(self, loop):
+        ema = getattr(loop.optimizer, "ema", None)
+        want = {k: v for k, v in self.args.items() if k != "gamma" or self.args["type"] == "ExpMomentumEMA"}
+        if ema is None or any(ema.args[k] != v for k, v in want.items()):
+            have = None if ema is None else ema.args
+            raise ValueError(f"EMAHook: the average is recorded with the optimizer's update and cannot be attached to a built step; "
+                             f"build the optimizer as FlatAdamW(ema=dict({', '.join(f'{k}={v!r}' for k, v in want.items())})) "
+                             f"(it has ema={have})")
+        self.ema = ema
+
+    def before_val(self, loop):
+        self.ema.swap()
+
+    def after_val(self, loop, metrics):
+        if self.ema.swapped:
+            self.ema.restore()
+
+
 # ---------------------------------------------------------------------------------------------------- the loop
 def _cycle(batches, skip):
     """the batches, restarted when exhausted, from the `skip`-th on (a resumed run continues where the data stood)"""
@@ -614,7 +721,9 @@ class TrainLoop:
     iterations.  The scheduler steps every iteration, as mmengine's ParamSchedulerHook does.  A run resumed inside a group raises
     (the partial group's gradients are in no file; mmengine only warns).  Nothing in an iteration reads the device; the log,
     validation and checkpoint iterations do (one `TrainLog.read()`, `step.check()`).  Every `val_interval` iterations and after the
-    last, `validate()` -> a metric dictionary (a closure over `evaluate(...)`), handed to the hooks' `after_val`.
+    last, `validate()` -> a metric dictionary (a closure over `evaluate(...)`), handed to the hooks' `after_val`; the hooks'
+    `before_val` runs ahead of it -- an `EMAHook` (optimizer built with `ema=...`) swaps the averaged weights in there and the
+    training weights back in `after_val`, and the loop itself swaps back behind anything that raises in between.
 
     `hooks`: objects or the configs' dictionaries (`dict(type='LoggerHook', interval=50)`), run in ascending `priority`.
     `load_from`: a checkpoint whose weights are loaded before the first iteration; with `resume` also the optimizer, the scheduler,
@@ -663,6 +772,12 @@ class TrainLoop:
         """the iteration (from 1) whose update was the `updates`-th (from 1): every accumulative_counts-th, and the last one"""
         return updates if self.accum is None else min(updates * self.accum.counts, self.max_iters)
 
+    def updates_done(self, n):
+        """the updates of the first `n` iterations: one per closed group, the run's last iteration closes its own"""
+        if self.accum is None:
+            return n
+        return n // self.accum.counts + (1 if n == self.max_iters and n % self.accum.counts else 0)
+
     def check_finite(self):
         """-> the log as of this iteration (read once per iteration, whoever asks), after raising for what went wrong on the device
         since the last look: FloatingPointError naming the FIRST iteration with a non-finite term, carrying the step's own status
@@ -701,15 +816,21 @@ class TrainLoop:
         watching = self.firing is not None and self.firing.attached
         if watching:
             self.firing.detach()          # a validation forward's spikes are not the next iteration's
+        ema = getattr(self.optimizer, "ema", None)
         try:
-            metrics = self.validate()
+            try:
+                self._call("before_val")          # (an EMAHook swaps the averaged weights in; hooks without the method are passed over)
+                metrics = self.validate()
+            finally:
+                if watching:
+                    self.firing.attach()          # (the same counters at the same addresses: the captured launches still hold)
+            if training:
+                model.train()
+            self.val_metrics = metrics
+            self._call("after_val", metrics)          # (the EMAHook swaps back, ahead of the logger and the checkpoint)
         finally:
-            if watching:
-                self.firing.attach()          # (the same counters at the same addresses: the captured launches still hold)
-        if training:
-            model.train()
-        self.val_metrics = metrics
-        self._call("after_val", metrics)
+            if ema is not None and ema.swapped:
+                ema.restore()          # whatever was raised above, the next iteration trains the training weights
 
     def run(self):
         start = 0

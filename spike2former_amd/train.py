@@ -182,10 +182,17 @@ class FlatAdamW:
     `accumulative_counts` (mmengine's OptimWrapper argument): 1 (default) -- `self.accum` is None, nothing is allocated, the class is
     what it is without the argument; k > 1 -- `self.accum = GradAccum(grad_buffer, k)`: whoever drives the step calls
     `accum.add()` behind the packing of EVERY iteration and `step(); accum.finish()` behind the one that closes a group
-    (graph.GraphedStep / GraphedHungarianStep and runner.TrainLoop do)."""
+    (graph.GraphedStep / GraphedHungarianStep and runner.TrainLoop do).
+
+    `ema`: None (default: `self.ema` is None, nothing is allocated or launched), True or a dictionary of `ema.WeightEMA` arguments
+    (mmengine's EMAHook's: `dict(type='ExpMomentumEMA', momentum=0.0002, gamma=2000, begin_iter=...)`): `step()` records the
+    average's ONE launch directly behind s2f_adamw_step, before the gradient log's -- captured with the update at world size 1,
+    launched eagerly behind the all-reduce otherwise (no communication: every rank applies a deterministic function of identical
+    weights).  With `accumulative_counts=k` the average moves once per update.  A step that was captured before holds the launches
+    it was recorded with: the average cannot be attached afterwards (runner.EMAHook checks that it is there)."""
 
     def __init__(self, model, grad_buffer, lr=0.001, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.005, paramwise_cfg=None,
-                 clip_grad=None, grad_log=None, accumulative_counts=1):
+                 clip_grad=None, grad_log=None, accumulative_counts=1, ema=None):
         from ._lib import lib
         self.red, self.betas, self.eps = grad_buffer, (float(betas[0]), float(betas[1])), float(eps)
         self.max_norm = float((clip_grad or {}).get("max_norm", 0.0)) if clip_grad else 0.0
@@ -211,6 +218,10 @@ class FlatAdamW:
         if int(accumulative_counts) != 1:
             self.accum = GradAccum(grad_buffer, accumulative_counts)          # (raises for a count below 1)
             self.accum.partials = self.partials
+        self.ema = None
+        if ema is not None and ema is not False:
+            from .ema import WeightEMA
+            self.ema = WeightEMA(self, **({} if ema is True else dict(ema)))
         self.grad_log = None
         if grad_log is not None and grad_log is not False:
             from .gradlog import GradLog
@@ -285,6 +296,8 @@ class FlatAdamW:
         check(lib.s2f_adamw_step(self.slots.data_ptr(), self.hyper.data_ptr(), self.chunks.data_ptr(), self.chunks.shape[0],
                                  flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.state.data_ptr(),
                                  b1, b2, self.eps, s), "s2f_adamw_step")
+        if self.ema is not None:
+            self.ema.update()
         if self.grad_log is not None:
             self.grad_log.append()
         # the kernels wrote the parameters behind autograd's back: bump their version counters so that every cache keyed on a
@@ -310,6 +323,8 @@ class FlatAdamW:
         self._build_tables()
         if self.accum is not None:
             self.accum.rebuild()                     # (only at a group boundary: raises inside a group)
+        if self.ema is not None:
+            self.ema.rebuild()                       # (the average follows the moments' layout, values kept per parameter)
         if self.grad_log is not None:
             self.grad_log.rebuild()                  # (its span table follows the slot table; its rows start afresh)
 
