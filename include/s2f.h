@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 52
+#define S2F_ABI_VERSION 53
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -1096,6 +1096,50 @@ int s2f_grad_log_rows(const int32_t* spans, int nspans, const int64_t* partials,
 int s2f_ema_update(const int64_t* slots, const int32_t* chunks, int nchunks, float* ema, const float* state, const float* table,
                    int ntable, int begin, int interval, double* partials, void* stream);
 int s2f_ema_swap(const int64_t* slots, const int32_t* chunks, int nchunks, float* ema, void* stream);
+
+/* ---- segmentation log: train-crop accuracy and mIoU from inside the captured step (csrc/seglog.hip, ABI 53) -------------------------
+ * mmseg's BaseDecodeHead logs decode.acc_seg with every loss; the reference's MaskFormerHead logs losses only.  The step holds the
+ * decoder's class scores, its mask logits and the label map on the device, so the score is two launches of the step and a ring the
+ * host reads once per log line.  Per scored layer l, image b and pixel p = (y, x) of the h x w mask prediction
+ *     P[q][k]  = softmax(cls[l][b][q][0 .. K])[k], k < K            (the void column is dropped: MaskFormerHead.predict)
+ *     score[k] = sum over q, ascending, of P[q][k] * sigmoid(mask[b][l*Q + q][p])           (fp32, one fma per term)
+ *     pred     = the first maximum of score (NaN larger than any number: s2f_seg_argmax's rule)
+ *     label    = seg[b][2y][2x]                                     (the sub-sampling of the matching costs; 255 = ignored)
+ * and a pixel with label < K adds 1 to label[label], 1 to pred[pred] and, where pred == label, 1 to intersect[label]; any other pixel
+ * counts nowhere.  A row of the ring is int64 [nl][3][K] = {intersect, pred, label} per scored layer: the totals of
+ * IoUMetric.intersect_and_union over the batch, at the MASK resolution (predict scores the up-sampled masks: a training diagnostic,
+ * not the validation metric).
+ *   s2f_seg_log_tile_pixels  the pixels one workgroup of s2f_seg_log_partials scores (256).
+ *   s2f_seg_log_partials     mask fp32 [B][L*Q][h*w], the head's own buffer; cls fp32 [L][B][Q][K+1]; seg uint8 [B][2h][2w], read with
+ *                            stride 2; layers: HOST memory, int32 [nl], the scored layers (read and checked during the call, passed
+ *                            to the kernel by value: nl <= S2F_SEG_LOG_MAX_LAYERS).  One workgroup per tile of
+ *                            s2f_seg_log_tile_pixels() pixels of one (scored layer, image); the softmax table is built in LDS in
+ *                            chunks of 32, 76 or 128 classes (chosen by K) x 128 or 64 queries (at most 38 KB whatever Q and K are; a row's
+ *                            sum of exponentials in fp64),
+ *                            the Q mask logits of a pixel are re-read per class chunk.  partials int32 [nl * B * tiles][3][K], tiles =
+ *                            ceil(h*w / s2f_seg_log_tile_pixels()): slice (i*B + b)*tiles + t <- the counts of tile t of image b in
+ *                            scored layer i, plain stores (every word is written).
+ *                            S2F_EINVAL: null pointer, K outside 1 .. 254, Q < 1, L < 1, B outside 1 .. 65535, w odd or h*w % 4 != 0,
+ *                            nl outside 1 .. S2F_SEG_LOG_MAX_LAYERS, a layer outside 0 .. L-1; S2F_EALIGN: mask / cls / partials not
+ *                            4-byte aligned.
+ *   s2f_seg_log_rows         one workgroup per scored layer i of nl adds its per_layer (= B * tiles) partials (sixteen waves, each
+ *                            every sixteenth partial; integers, so the order does not matter) ->
+ *                            ring int64 [window][nl][3][K] at row head[0] % window: overwritten, never accumulated into.  streak int32
+ *                            [K], from the LAST scored layer's totals: streak[c] = 0 where intersect[c] > 0, + 1 where label[c] > 0
+ *                            and intersect[c] == 0, unchanged where the class is absent.  head int64 [4], initialised by the caller
+ *                            to {0, -1, 0, 0}: where streak[c] REACHES `patience` the event head[0] * 2^32 + c is offered to head[1],
+ *                            which keeps the minimum under UNSIGNED comparison (-1: none yet).  head[0] advances exactly once per
+ *                            launch by the ticket in head[2] (0 at entry and on exit), as in s2f_firing_log_append.
+ *                            S2F_EINVAL: null pointer, K outside 1 .. 254, nl outside 1 .. S2F_SEG_LOG_MAX_LAYERS, per_layer / window /
+ *                            patience < 1; S2F_EALIGN: ring / head not 8-byte, partials / streak not 4-byte aligned.
+ * Both launches only READ mask, cls and seg; no global atomics on the rows (LDS counters inside a workgroup, the head's words as
+ * above); nothing allocates or synchronises: capturable behind the step's last launch. */
+#define S2F_SEG_LOG_MAX_LAYERS 32
+int s2f_seg_log_tile_pixels(void);
+int s2f_seg_log_partials(const float* mask, const float* cls, const uint8_t* seg, const int32_t* layers, int nl, int L, int B, int Q,
+                         int K, int h, int w, int32_t* partials, void* stream);
+int s2f_seg_log_rows(const int32_t* partials, int nl, int per_layer, int K, int64_t* ring, int window, int32_t* streak, int patience,
+                     int64_t* head, void* stream);
 
 /* ---- operand census: what a synaptic op really reads (csrc/opcensus.hip, ABI 49) -----------------------------------------------------
  * The reference's tools/cal_firing_num.py stops at firing rates per neuron (fr_rate.csv) and leaves operations and energy to a

@@ -22,6 +22,7 @@ from .graph import CapturePolicy, GraphedPredict  # noqa: F401
 from .segmentor import EncoderDecoder, ResetModelHook, headline_loss  # noqa: F401
 from .tta import SegTTAModel  # noqa: F401
 from .metrics import ConfusionMatrix, IoUMetric, evaluate  # noqa: F401
+from .seglog import SegLog, SegRead  # noqa: F401
 from .augment import TestAugment, TrainAugment  # noqa: F401
 from .visualization import SegLocalVisualizer, SegVisualizationHook  # noqa: F401
 from .train import LinearThenPoly, OptimWrapper, parse_losses, train_step  # noqa: F401

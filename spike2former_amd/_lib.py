@@ -183,6 +183,9 @@ SIGNATURES = {
     "s2f_grad_log_span_elems": (_i, []),
     "s2f_grad_log_partials": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _f, _p, _p]),
     "s2f_grad_log_rows": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _p]),
+    "s2f_seg_log_tile_pixels": (_i, []),
+    "s2f_seg_log_partials": (_i, [_p, _p, _p, _p] + [_i] * 7 + [_p, _p]),
+    "s2f_seg_log_rows": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p, _p]),
 }
 
 

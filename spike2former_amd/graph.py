@@ -57,7 +57,7 @@ def step_tail(optimizer_in_step, accumulating, world):
 class _Captured:
     """A step with static input `static_in`, recorded as one hipGraph per stage.  `red`: the flat gradient buffer
     (dist.FlatGradAllReduce) of the steps that pack into one; `optimizer`: a train.FlatAdamW captured behind the packing."""
-    optimizer = log = firing = None
+    optimizer = log = firing = seg_log = None
 
     def _tail(self):
         return step_tail(self.optimizer is not None, self.accum is not None, _world_size())
@@ -94,10 +94,10 @@ class _Captured:
 
     def _after_capture(self):
         """once the capture has ended: the table the log's launch reads is uploaded (nothing may be while a capture records), and
-        the firing and gradient logs start afresh -- what the warm-up passes appended is not row 0"""
+        the firing, gradient and segmentation logs start afresh -- what the warm-up passes appended is not row 0"""
         if self.log is not None and self._tail()[1] != "caller":
             self.log.bind(self.log_terms)
-        for ring in (self.firing, self.grad_log):
+        for ring in (self.firing, self.grad_log, self.seg_log):
             if ring is not None:
                 ring.clear()
 
@@ -331,16 +331,22 @@ class GraphedHungarianStep(_Captured):
     one launch that turns them into a row per replay -- per-neuron firing rates of EVERY iteration, and the first neuron that stays
     silent for the log's `patience` iterations, read by runner.LoggerHook with the losses.  Counters change the launch structure of
     the step (the memoised, pre-fired and fused-neuron routes step aside for a neuron that has them); None: nothing is attached,
-    allocated or launched, the capture is the one without it.  (An accumulating optimizer: see GraphedStep and `step_tail`.)"""
+    allocated or launched, the capture is the one without it.  (An accumulating optimizer: see GraphedStep and `step_tail`.)
+
+    `seg_log` (seglog.SegLog): the last graph ends with two more launches that score the step's own outputs -- the class scores and
+    mask logits of the scored decoder layers, detached -- against `static_seg` at the mask resolution and append the per-class areas
+    of intersect_and_union to a ring: train-crop accuracy and mIoU of EVERY iteration (a micro-batch, with an accumulating
+    optimizer), read by runner.LoggerHook with the losses; in the one-graph and the two-graph forms alike, and at every world size
+    (each rank scores its own crops).  None: nothing is allocated, launched or captured."""
 
     def __init__(self, model, example_input, example_seg, grad_buffer, warmup=3, ignore_index=None, optimizer=None, assign="host",
-                 log=None, firing=None):
+                 log=None, firing=None, seg_log=None):
         if assign not in ("host", "device"):
             raise ValueError(f"assign must be 'host' or 'device', got {assign!r}")
         if assign == "device" and not (example_input.is_cuda and example_seg.is_cuda):
             raise RuntimeError("GraphedHungarianStep(assign='device') needs CUDA tensors: the device assignment is a HIP kernel and "
                                "has no host fall-back")
-        self.assign, self.log, self.firing = assign, log, firing
+        self.assign, self.log, self.firing, self.seg_log = assign, log, firing, seg_log
         head = model.decode_head
         self.optimizer = optimizer
         if optimizer is not None:
@@ -356,6 +362,10 @@ class GraphedHungarianStep(_Captured):
         if not self.crit.semantic_ok(masks, self.static_seg):
             raise RuntimeError("GraphedHungarianStep needs semantic maps at twice the mask predictions' resolution")
         L, B, Q = cls.shape[:3]
+        if seg_log is not None:
+            if seg_log.K != self.crit.num_classes:
+                raise ValueError(f"GraphedHungarianStep: a SegLog of {seg_log.K} classes on a head of {self.crit.num_classes}")
+            seg_log.bind(L, B, Q, *masks.shape[-2:], device=dev)
         del cls, masks
         self.tgt_labels = torch.full((L, B, Q), self.crit.num_classes, dtype=torch.int64, device=dev)
         self.row_class = torch.full((B, L * Q), -1, dtype=torch.int32, device=dev)
@@ -394,6 +404,8 @@ class GraphedHungarianStep(_Captured):
                 self.sticky.bitwise_or_(self.status)
                 self.host_status.copy_(self.sticky, non_blocking=True)
             self._record_firing()
+            if self.seg_log is not None:          # the step's own prediction against its own labels: two launches, one row
+                self.seg_log.append(self.outs[0], self.outs[1], self.static_seg)
 
         def whole():
             head()
