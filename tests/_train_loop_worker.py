@@ -20,7 +20,7 @@ from spike2former_amd.dist import FlatGradAllReduce, broadcast_params, init_proc
 from spike2former_amd.graph import GraphedHungarianStep                     # noqa: E402
 from spike2former_amd.init_utils import seeded_init                         # noqa: E402
 from spike2former_amd.train import FlatAdamW, LinearThenPoly                # noqa: E402
-from test_gpu_train_loop import CLIP, NORM, make_batches, region_map         # noqa: E402
+from step_rig import CLIP, NORM, examples, make_batches                     # noqa: E402
 
 rank, world, local = init_process_group()
 assert world == 2 and dist.get_backend() == "gloo"
@@ -41,8 +41,7 @@ sched = LinearThenPoly(opt, warmup=4, total=20, start_factor=0.1)
 aug = TrainAugment(crop_size=crop, scale=(2 * crop[1], crop[0]), ratio_range=(0.5, 2.0), cat_max_ratio=0.75, photometric=True,
                    batch_size=2, max_source_pixels=70 * 90, seed=11, rank=rank, **NORM)
 log = s2f.TrainLog(window=8)
-example_in = torch.randn(2, 3, *crop, generator=torch.Generator().manual_seed(5)).to(dev)
-example_seg = torch.from_numpy(np.stack([region_map(*crop, [1, 2, 3]), region_map(*crop, [4, 5])])).to(dev)
+example_in, example_seg = (t.to(dev) for t in examples(crop))
 step = GraphedHungarianStep(model, example_in, example_seg, red, warmup=1, log=log)
 assert step.two_graphs and step.optimizer is None and step.log_captured is False
 batches = make_batches(w["K"])[rank:] + make_batches(w["K"])[:rank]          # each rank its own pictures

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import aug_ref as R  # noqa: E402
+from step_rig import region_map  # noqa: E402
 from test_augment_host import CROP_CASES, crop_scene, window  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -335,14 +336,6 @@ def test_graph_replays_follow_the_static_buffers():
 
 
 # ------------------------------------------------------------------------------------------------ 8. the training step
-def region_map(h, w, classes):
-    seg = np.empty((h, w), np.uint8)
-    for i, (y, x) in enumerate((y, x) for y in range(0, h, 16) for x in range(0, w, 16)):
-        seg[y:y + 16, x:x + 16] = classes[i % len(classes)]
-    seg[:2, 3:17] = 255
-    return seg
-
-
 def test_training_step_fed_in_place():
     """GraphedHungarianStep(assign="device") on the tiny configuration, fed through out=(static_in, static_seg): finite losses,
     bit-equal to the same step fed with the restatement's tensors"""

@@ -1,9 +1,8 @@
 """GPU: the firing log -- s2f_firing_log_append (csrc/firinglog.hip) against the numpy restatement tests/firing_ref.py in exact
 integers, its streaks and its latch, the launch inside a captured graph, and FiringLog inside GraphedHungarianStep and TrainLoop on
-the tiny configuration C1_64 (the rig of tests/test_gpu_train_loop.py, with a FiringLog).  Rigs are built once for the module:
+the tiny configuration C1_64 (the rig of tests/step_rig.py, with a FiringLog).  Rigs are built once for the module:
     still -- optimizer=None: the weights stand still (the BatchNorm running statistics, which the forward reads, still move)
     train -- with a FlatAdamW, a TrainLog and a FiringLog: what TrainLoop drives"""
-import gc
 import json
 import logging
 import os
@@ -16,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import firing_ref as R  # noqa: E402
-import test_gpu_train_loop as T  # noqa: E402  (region_map, make_batches, NORM, SHAPES, CLIP: the rig's ingredients)
+from step_rig import reset, rigs_fixture  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -159,64 +158,9 @@ def test_append_in_a_captured_graph_equals_eager():
 DEAD_BN, DEAD_NEURON = "backbone.ConvBlock1_1.0.Conv.bn1", "backbone.ConvBlock1_1.0.Conv.spike2"
 
 
-def build(kind):
-    import spike2former_amd as s2f
-    from spike2former_amd.augment import TrainAugment
-    from spike2former_amd.dist import FlatGradAllReduce
-    from spike2former_amd.graph import GraphedHungarianStep
-    from spike2former_amd.init_utils import seeded_init
-    from spike2former_amd.train import FlatAdamW, LinearThenPoly
-    w = s2f.WORKLOADS["C1_64"]
-    crop = (w["H"], w["W"])
-    model = seeded_init(s2f.MODELS.build(s2f.model_cfg("C1_64"))).cuda().train()
-    s2f.set_keep_membrane(model, False)
-    r = types.SimpleNamespace(model=model, K=w["K"], crop=crop, seed=0)
-    r.sd0 = {k: v.clone() for k, v in model.state_dict().items()}
-    r.red = FlatGradAllReduce(model.parameters(), 1)
-    r.opt = r.sched = r.log = None
-    if kind != "still":
-        r.opt = FlatAdamW(model, r.red, lr=0.001, weight_decay=0.005, clip_grad=T.CLIP,
-                          paramwise_cfg=dict(custom_keys={"backbone": dict(lr_mult=0.1, decay_mult=1.0)}))
-        r.sched = LinearThenPoly(r.opt, warmup=4, total=20, start_factor=0.1)
-        r.log = s2f.TrainLog(window=8)
-    r.aug = TrainAugment(crop_size=crop, scale=(2 * crop[1], crop[0]), ratio_range=(0.5, 2.0), cat_max_ratio=0.75, photometric=True,
-                         batch_size=2, max_source_pixels=70 * 90, seed=11, rank=0, **T.NORM)
-    r.firing = s2f.FiringLog(model, window=8, patience=3) if kind != "plain" else None
-    example_in = torch.randn(2, 3, *crop, generator=torch.Generator().manual_seed(5)).cuda()
-    example_seg = torch.from_numpy(np.stack([T.region_map(*crop, [1, 2, 3]), T.region_map(*crop, [4, 5])])).cuda()
-    r.step = GraphedHungarianStep(model, example_in, example_seg, r.red, warmup=1, optimizer=r.opt, assign="device", log=r.log,
-                                  firing=r.firing)
-    reset(r)
-    return r
-
-
-def reset(r):
-    r.model.load_state_dict(r.sd0)
-    if r.opt is not None:
-        T.reset(r)
-    if r.firing is not None:
-        r.firing.clear()
-    torch.cuda.synchronize()
-
-
-@pytest.fixture(scope="module")
-def rigs():
-    import spike2former_amd as s2f
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = build(name)
-        return cache[name]
-    get.batches = T.make_batches(s2f.WORKLOADS["C1_64"]["K"])
-    yield get
-    for r in cache.values():
-        if r.firing is not None:
-            r.firing.detach()
-        for p in r.model.parameters():
-            p.grad = None
-    cache.clear()
-    gc.collect()
+FIRING = dict(window=8, patience=3)
+recipes = dict(still=dict(optimizer=False, log=False, firing=FIRING), train=dict(firing=FIRING))
+rigs = rigs_fixture(recipes)
 
 
 def test_row_zero_is_the_forward_of_the_step(rigs):

@@ -1,8 +1,7 @@
 """GPU: gradient accumulation (FlatAdamW(accumulative_counts=k), train.GradAccum) -- the two kernels of csrc/optim.hip against the
 numpy restatement of tests/accum_ref.py by bits, the captured step on the tiny configuration C1_64 against two oracles, the
 default path against a rig built without the argument, TrainLoop at counts 3 over 7 iterations with a resume on a group boundary,
-and two ranks on one GPU.  The rigs are those of tests/test_gpu_train_loop.py (same pictures, seeds and schedule), built here."""
-import gc
+and two ranks on one GPU.  The rigs are tests/step_rig.py's (the pictures, seeds and schedule of tests/test_gpu_train_loop.py)."""
 import json
 import os
 import socket
@@ -16,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import accum_ref as ref          # noqa: E402
-from test_gpu_train_loop import CLIP, NORM, make_batches, region_map          # noqa: E402
+from step_rig import CLIP, KINDS, Elementwise, feed, gaps, new_loop, reset, rigs_fixture, scramble, state_of          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -190,104 +189,9 @@ def test_stats_equal_the_restatement_by_bits(rows, nparts):
 
 
 # ---------------------------------------------------------------------------------------------------- the captured step
-def build(counts=None, step_optimizer=True, log=True, grad_log=None, seed=0):
-    """tests/test_gpu_train_loop.py's rig; `counts`: FlatAdamW(accumulative_counts=counts) (None: built WITHOUT the argument);
-    `step_optimizer` False: the plain step, without an optimizer -- the rig's FlatAdamW is then stepped by the caller"""
-    import spike2former_amd as s2f
-    from spike2former_amd.augment import TrainAugment
-    from spike2former_amd.dist import FlatGradAllReduce
-    from spike2former_amd.graph import GraphedHungarianStep
-    from spike2former_amd.init_utils import seeded_init
-    from spike2former_amd.train import FlatAdamW, LinearThenPoly
-    w = s2f.WORKLOADS["C1_64"]
-    crop = (w["H"], w["W"])
-    model = seeded_init(s2f.MODELS.build(s2f.model_cfg("C1_64"))).cuda().train()
-    s2f.set_keep_membrane(model, False)
-    r = types.SimpleNamespace(model=model, K=w["K"], crop=crop, seed=seed)
-    r.sd0 = {k: v.clone() for k, v in model.state_dict().items()}
-    r.red = FlatGradAllReduce(model.parameters(), 1)
-    extra = {} if counts is None else dict(accumulative_counts=counts)
-    r.opt = FlatAdamW(model, r.red, lr=0.001, weight_decay=0.005, clip_grad=CLIP, grad_log=grad_log,
-                      paramwise_cfg=dict(custom_keys={"backbone": dict(lr_mult=0.1, decay_mult=1.0)}), **extra)
-    r.sched = LinearThenPoly(r.opt, warmup=4, total=20, start_factor=0.1)
-    r.aug = TrainAugment(crop_size=crop, scale=(2 * crop[1], crop[0]), ratio_range=(0.5, 2.0), cat_max_ratio=0.75, photometric=True,
-                         batch_size=2, max_source_pixels=70 * 90, seed=11 + seed, rank=0, **NORM)
-    r.log = s2f.TrainLog(window=8) if log else None
-    example_in = torch.randn(2, 3, *crop, generator=torch.Generator().manual_seed(5)).cuda()
-    example_seg = torch.from_numpy(np.stack([region_map(*crop, [1, 2, 3]), region_map(*crop, [4, 5])])).cuda()
-    r.step = GraphedHungarianStep(model, example_in, example_seg, r.red, warmup=1, optimizer=r.opt if step_optimizer else None,
-                                  assign="device", log=r.log)
-    reset(r)
-    return r
-
-
-def reset(r):
-    r.model.load_state_dict(r.sd0)
-    r.opt.exp_avg.zero_(), r.opt.exp_avg_sq.zero_(), r.opt.state.zero_()
-    r.sched.t = 0
-    r.sched._apply()
-    r.aug.rng = np.random.default_rng(np.random.SeedSequence([r.aug.seed, r.aug.rank]))
-    if r.opt.accum is not None:
-        r.opt.accum.count, r.opt.accum.total = 0, None
-        r.opt.accum.stats.zero_()
-    r.opt.mark_updated()
-    torch.cuda.synchronize()
-
-
-def scramble(r):
-    reset(r)
-    with torch.no_grad():
-        for t in r.model.state_dict().values():
-            t.add_(3) if t.dtype == torch.int64 else t.mul_(1.25)
-    r.opt.exp_avg.fill_(0.5), r.opt.exp_avg_sq.fill_(0.25), r.opt.state.fill_(7.0)
-    r.sched.t = 9
-    r.sched._apply()
-    r.aug.rng.random(5)
-
-
-def feed(r, batch):
-    images, segs = batch
-    r.aug(images, segs, out=(r.step.static_in, r.step.static_seg))
-
-
-def state_of(r):
-    torch.cuda.synchronize()
-    out = {f"model:{k}": v.clone() for k, v in r.model.state_dict().items()}
-    for p, off, g in zip(r.opt.params, r.red.offsets, r.opt.param_groups):
-        out[f"exp_avg:{g['name']}"] = r.opt.exp_avg[off:off + p.numel()].clone()
-        out[f"exp_avg_sq:{g['name']}"] = r.opt.exp_avg_sq[off:off + p.numel()].clone()
-    out["step:"] = r.opt.state[4:5].clone()
-    return out
-
-
-KINDS = ("model:", "exp_avg:", "exp_avg_sq:", "step:")
-
-
-def gaps(a, b):
-    """largest absolute difference per kind of tensor"""
-    assert list(a) == list(b)
-    return {kind: max(float((a[k].double() - b[k].double()).abs().max()) for k in a if k.startswith(kind) and a[k].numel())
-            for kind in KINDS}
-
-
-@pytest.fixture(scope="module")
-def rigs():
-    import spike2former_amd as s2f
-    cache = {}
-    recipes = dict(acc2=dict(counts=2), plain=dict(step_optimizer=False, log=False), one=dict(counts=1, log=False),
-                   none=dict(log=False), acc3=dict(counts=3, grad_log=dict(window=8, patience=200)))
-
-    def get(name):
-        if name not in cache:
-            cache[name] = build(**recipes[name])
-        return cache[name]
-    get.batches = make_batches(s2f.WORKLOADS["C1_64"]["K"])
-    yield get
-    for r in cache.values():
-        for p in r.model.parameters():
-            p.grad = None
-    cache.clear()
-    gc.collect()
+recipes = dict(acc2=dict(counts=2), plain=dict(step_optimizer=False, log=False), one=dict(counts=1, log=False),
+               none=dict(log=False), acc3=dict(counts=3, grad_log=dict(window=8, patience=200)))
+rigs = rigs_fixture(recipes)
 
 
 @pytest.fixture(scope="module")
@@ -440,20 +344,6 @@ def test_counts_one_updates_bit_equal_from_equal_gradients():
         assert torch.equal(a, b)
 
 
-class Elementwise(torch.nn.Module):
-    """a model whose step IS bit-repeatable: element-wise products and torch's fixed-order sums, no atomics anywhere"""
-
-    def __init__(self):
-        super().__init__()
-        g = torch.Generator().manual_seed(4)
-        self.backbone_w = torch.nn.Parameter(torch.randn(3, 33, 35, generator=g))
-        self.b = torch.nn.Parameter(torch.randn(35, generator=g))
-        self.gain = torch.nn.Parameter(torch.randn(1, generator=g))
-
-    def forward(self, x):
-        return (torch.tanh(x * self.backbone_w + self.b) * self.gain,)
-
-
 def test_counts_one_is_the_step_without_the_argument():
     """Three iterations of the captured step (GraphedStep with the update inside the graph) leave weights and moments BIT-equal to
     a rig built without the argument.  Bit equality between two rigs presupposes a step that repeats itself bit for bit, which
@@ -500,11 +390,6 @@ def test_counts_one_is_the_step_without_the_argument():
 
 
 # ---------------------------------------------------------------------------------------------------- the loop
-def new_loop(r, batches, max_iters, hooks=(), **kw):
-    import spike2former_amd as s2f
-    return s2f.TrainLoop(r.step, r.opt, r.sched, r.aug, batches, max_iters=max_iters, hooks=list(hooks), **kw)
-
-
 def test_train_loop_counts_3_over_7_iterations(rigs, tmp_path):
     r = rigs("acc3")
     reset(r)

@@ -1,7 +1,7 @@
 """GPU: the gradient log -- s2f_grad_log_partials + s2f_grad_log_rows (csrc/gradlog.hip) through ops.grad_log_append on a synthetic
 slot table against the numpy restatement tests/gradlog_ref.py (counts and the maximum exactly, the three sums of squares to the
 rounding of an fp64 sum in another order), the ring, the streaks and both latches; then GradLog behind FlatAdamW.step() on the tiny
-configuration C1_64, eager and inside GraphedHungarianStep (the rig of tests/test_gpu_train_loop.py, with a grad_log).
+configuration C1_64, eager and inside GraphedHungarianStep (the rig of tests/step_rig.py, with a grad_log).
 
 The scenario of the kernel tests -- five appends into a ring of three rows, patience 2 -- runs ONCE for the module; what every append
 left on the device is kept on the host next to the restatement's state, and the tests read those records."""
@@ -16,7 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gradlog_ref as R  # noqa: E402
-import test_gpu_train_loop as T  # noqa: E402  (region_map, make_batches, NORM, CLIP, reset: the rig's ingredients)
+import step_rig as rig  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -217,8 +217,7 @@ def tiny(grad_log):
     from spike2former_amd.train import FlatAdamW
     model = seeded_init(s2f.MODELS.build(s2f.model_cfg("C1_64"))).cuda().train()
     red = FlatGradAllReduce(model.parameters(), 1)
-    opt = FlatAdamW(model, red, lr=0.001, weight_decay=0.005, clip_grad=T.CLIP, grad_log=grad_log,
-                    paramwise_cfg=dict(custom_keys={"backbone": dict(lr_mult=0.1, decay_mult=1.0)}))
+    opt = FlatAdamW(model, red, lr=0.001, weight_decay=0.005, clip_grad=rig.CLIP, grad_log=grad_log, paramwise_cfg=rig.PARAMWISE)
     return model, red, opt
 
 
@@ -293,24 +292,12 @@ def test_the_log_follows_a_rebuilt_optimizer():
 
 
 def test_rows_of_the_captured_step_match_the_train_log():
-    import spike2former_amd as s2f
-    from spike2former_amd.augment import TrainAugment
-    from spike2former_amd.graph import GraphedHungarianStep
-    model, red, opt = tiny(dict(window=8, patience=3))
-    s2f.set_keep_membrane(model, False)
-    w = s2f.WORKLOADS["C1_64"]
-    crop = (w["H"], w["W"])
-    aug = TrainAugment(crop_size=crop, scale=(2 * crop[1], crop[0]), ratio_range=(0.5, 2.0), cat_max_ratio=0.75, photometric=True,
-                       batch_size=2, max_source_pixels=70 * 90, seed=11, rank=0, **T.NORM)
-    log = s2f.TrainLog(window=8)
-    example_in = torch.randn(2, 3, *crop, generator=torch.Generator().manual_seed(5)).cuda()
-    example_seg = torch.from_numpy(np.stack([T.region_map(*crop, [1, 2, 3]), T.region_map(*crop, [4, 5])])).cuda()
-    step = GraphedHungarianStep(model, example_in, example_seg, red, warmup=1, optimizer=opt, assign="device", log=log)
+    r = rig.build(grad_log=dict(window=8, patience=3))
+    model, opt, log, step = r.model, r.opt, r.log, r.step
     assert step.grad_log is opt.grad_log and step.grad_log.read().count == 0          # the capture's passes are not row 0
-    batches = T.make_batches(w["K"])
-    for it in range(3):
-        images, segs = batches[it]
-        aug(images, segs, out=(step.static_in, step.static_seg))
+    batches = rig.make_batches(r.K)
+    for it in range(3):          # (nobody steps the schedule: the rate stays the warm-up's first)
+        rig.feed(r, batches[it])
         step()
     step.check()
     read, rows = step.grad_log.read(), log.read()
@@ -322,5 +309,5 @@ def test_rows_of_the_captured_step_match_the_train_log():
     assert (read.numel[0] == np.array([p.numel() for p in opt.params])).all()
     for p in model.parameters():
         p.grad = None
-    del step
+    del step, r
     gc.collect()

@@ -1,18 +1,16 @@
 """GPU: the segmentation log -- s2f_seg_log_partials / s2f_seg_log_rows (csrc/seglog.hip) against the fp64 restatement
 tests/seglog_ref.py in exact integers, saturated inputs, the ring and its latch, the launches inside a captured graph, and SegLog
-inside GraphedHungarianStep and TrainLoop on the tiny configuration C1_64 (the rig of tests/test_gpu_train_loop.py).
+inside GraphedHungarianStep and TrainLoop on the tiny configuration C1_64 (the rig of tests/step_rig.py).
 
 Where fp32 may legitimately pick another class than fp64 -- a pixel whose fp64 top-two score gap is below 4 Q 2^-24 max(1, max score),
 the accumulation bound of Q products <= 1 -- the pixel's label is set to 255 in the input handed to BOTH the kernel and the
 restatement, so it counts nowhere; at most 0.5 % of the pixels may be such (asserted; the seeded inputs below have none)."""
 import ctypes
 import functools
-import gc
 import json
 import logging
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -20,7 +18,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import seglog_ref as R  # noqa: E402
-import test_gpu_train_loop as T  # noqa: E402  (region_map, make_batches, NORM, CLIP, reset: the rig's ingredients)
+import step_rig as rig  # noqa: E402
+from step_rig import reset, rigs_fixture  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -208,78 +207,21 @@ def node_types(graph):
     return out
 
 
-def build(kind):
-    """plain: the rig of tests/test_gpu_train_loop.py (FlatAdamW, TrainLog, assign="device"); seg: the same with a SegLog over all
-    layers.  The captured graphs are kept (keep_graph=True) so that their nodes can be counted."""
-    import spike2former_amd as s2f
-    from spike2former_amd.augment import TrainAugment
-    from spike2former_amd.dist import FlatGradAllReduce
-    from spike2former_amd.graph import GraphedHungarianStep
-    from spike2former_amd.init_utils import seeded_init
-    from spike2former_amd.train import FlatAdamW, LinearThenPoly
-    w = s2f.WORKLOADS["C1_64"]
-    crop = (w["H"], w["W"])
-    model = seeded_init(s2f.MODELS.build(s2f.model_cfg("C1_64"))).cuda().train()
-    s2f.set_keep_membrane(model, False)
-    r = types.SimpleNamespace(model=model, K=w["K"], crop=crop, seed=0)
-    r.sd0 = {k: v.clone() for k, v in model.state_dict().items()}
-    r.red = FlatGradAllReduce(model.parameters(), 1)
-    r.opt = FlatAdamW(model, r.red, lr=0.001, weight_decay=0.005, clip_grad=T.CLIP,
-                      paramwise_cfg=dict(custom_keys={"backbone": dict(lr_mult=0.1, decay_mult=1.0)}))
-    r.sched = LinearThenPoly(r.opt, warmup=4, total=20, start_factor=0.1)
-    r.log = s2f.TrainLog(window=8)
-    r.aug = TrainAugment(crop_size=crop, scale=(2 * crop[1], crop[0]), ratio_range=(0.5, 2.0), cat_max_ratio=0.75, photometric=True,
-                         batch_size=2, max_source_pixels=70 * 90, seed=11, rank=0, **T.NORM)
-    r.seg_log = s2f.SegLog(r.K, window=8, patience=2, layers="all") if kind == "seg" else None
-    example_in = torch.randn(2, 3, *crop, generator=torch.Generator().manual_seed(5)).cuda()
-    example_seg = torch.from_numpy(np.stack([T.region_map(*crop, [1, 2, 3]), T.region_map(*crop, [4, 5])])).cuda()
-    plain_graph = torch.cuda.CUDAGraph
-    torch.cuda.CUDAGraph = lambda: plain_graph(keep_graph=True)
-    try:
-        kw = dict(seg_log=r.seg_log) if kind == "seg" else {}
-        r.step = GraphedHungarianStep(model, example_in, example_seg, r.red, warmup=1, optimizer=r.opt, assign="device", log=r.log, **kw)
-    finally:
-        torch.cuda.CUDAGraph = plain_graph
-    reset(r)
-    return r
-
-
-def reset(r):
-    T.reset(r)
-    if r.seg_log is not None:
-        r.seg_log.clear()
-    torch.cuda.synchronize()
-
-
-@pytest.fixture(scope="module")
-def rigs():
-    import spike2former_amd as s2f
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = build(name)
-        return cache[name]
-    get.batches = T.make_batches(s2f.WORKLOADS["C1_64"]["K"])
-    yield get
-    for r in cache.values():
-        for p in r.model.parameters():
-            p.grad = None
-    cache.clear()
-    gc.collect()
+# plain: the rig of tests/step_rig.py (FlatAdamW, TrainLog, assign="device"); seg: the same with a SegLog over all layers.  The
+# captured graphs are kept so that their nodes can be counted.
+recipes = dict(plain=dict(keep_graph=True), seg=dict(keep_graph=True, seg_log=dict(window=8, patience=2, layers="all")))
+rigs = rigs_fixture(recipes)
 
 
 def run(r, batches, count):
     """`count` iterations from the reset rig -> per iteration the loss dictionary's values as fp32 bit patterns {term: int}"""
     reset(r)
     out = []
-    for it in range(count):
-        images, segs = batches[it % len(batches)]
-        r.aug(images, segs, out=(r.step.static_in, r.step.static_seg))
-        losses = r.step()
-        r.sched.step()
+
+    def behind(it):
         torch.cuda.synchronize()
-        out.append({k: float(v) for k, v in losses.items()})
+        out.append({k: float(v) for k, v in r.step.losses.items()})          # (the dictionary the step returns)
+    rig.iterate(r, batches, 0, count, behind)
     return out
 
 
@@ -329,7 +271,7 @@ def test_the_two_graph_form_appends_the_row_too():
     red = FlatGradAllReduce(model.parameters(), 1)
     sl = s2f.SegLog(w["K"], window=2, patience=1)
     x = torch.randn(2, 3, *crop, generator=torch.Generator().manual_seed(5)).cuda()
-    seg = torch.from_numpy(np.stack([T.region_map(*crop, [1, 2, 3]), T.region_map(*crop, [4, 5])])).cuda()
+    seg = torch.from_numpy(np.stack([rig.region_map(*crop, [1, 2, 3]), rig.region_map(*crop, [4, 5])])).cuda()
     step = GraphedHungarianStep(model, x, seg, red, warmup=1, assign="host", seg_log=sl)
     try:
         assert step.two_graphs and sl.read().count == 0 and sl.layers == [step.outs[0].shape[0] - 1]
@@ -405,7 +347,7 @@ def test_the_loop_writes_the_rows_it_read_and_a_resumed_one_rebases(rigs, tmp_pa
         assert 0.0 <= sc["decode.acc_seg"] <= 100.0
     assert sum("Iter(train)" in x.message and "decode.acc_seg" in x.message for x in caplog.records) == 2
     # a resumed run starts the ring afresh: row 0 is iteration 5
-    T.scramble(r)
+    rig.scramble(r)
     r.seg_log.clear()
     again = s2f.TrainLoop(r.step, r.opt, r.sched, r.aug, rigs.batches, max_iters=6, hooks=hooks, work_dir=str(tmp_path), resume=True)
     again.run()

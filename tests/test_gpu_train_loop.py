@@ -4,142 +4,28 @@ scheduler, augmentation, captured step) are built once for the module:
     plain  -- log=None: the step as it was before the loop existed; the yardstick of the continuation test
     first  -- with a TrainLog
     second -- with a TrainLog, from other seeds: what a run is resumed INTO
-A rig is put back to its start between tests by code that predates the loop (load_state_dict, zeroed moments, a fresh generator)."""
+The rig itself is tests/step_rig.py's; a rig is put back to its start between tests by code that predates the loop
+(load_state_dict, zeroed moments, a fresh generator)."""
 import copy
-import gc
 import json
 import os
 import socket
 import subprocess
 import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from step_rig import NORM, SHAPES, iterate, new_loop, reset, rigs_fixture, scramble, state_of          # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-NORM = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], bgr_to_rgb=True)
-SHAPES = ((70, 90), (64, 48))
-CLIP = dict(max_norm=0.01, norm_type=2)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def region_map(h, w, classes):
-    seg = np.empty((h, w), np.uint8)
-    for i, (y, x) in enumerate((y, x) for y in range(0, h, 16) for x in range(0, w, 16)):
-        seg[y:y + 16, x:x + 16] = classes[i % len(classes)]
-    seg[:2, 3:17] = 255
-    return seg
-
-
-def make_batches(K):
-    rng = np.random.default_rng(50)
-    out = []
-    for b in range(3):
-        images = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in SHAPES]
-        segs = [region_map(h, w, rng.permutation(K)[:4 + i + b]) for i, (h, w) in enumerate(SHAPES)]
-        out.append((images, segs))
-    return out
-
-
-def build(seed, log):
-    import spike2former_amd as s2f
-    from spike2former_amd.augment import TrainAugment
-    from spike2former_amd.dist import FlatGradAllReduce
-    from spike2former_amd.graph import GraphedHungarianStep
-    from spike2former_amd.init_utils import seeded_init
-    from spike2former_amd.train import FlatAdamW, LinearThenPoly
-    w = s2f.WORKLOADS["C1_64"]
-    crop = (w["H"], w["W"])
-    model = seeded_init(s2f.MODELS.build(s2f.model_cfg("C1_64")))
-    if seed:          # other weights than the other rigs'
-        g = torch.Generator().manual_seed(seed)
-        with torch.no_grad():
-            for p in model.parameters():
-                p.mul_(1.0 + 0.05 * torch.randn(p.shape, generator=g))
-    model = model.cuda().train()
-    s2f.set_keep_membrane(model, False)
-    r = types.SimpleNamespace(model=model, K=w["K"], crop=crop, seed=seed)
-    r.sd0 = {k: v.clone() for k, v in model.state_dict().items()}
-    r.red = FlatGradAllReduce(model.parameters(), 1)
-    r.opt = FlatAdamW(model, r.red, lr=0.001, weight_decay=0.005, clip_grad=CLIP,
-                      paramwise_cfg=dict(custom_keys={"backbone": dict(lr_mult=0.1, decay_mult=1.0)}))
-    r.sched = LinearThenPoly(r.opt, warmup=4, total=20, start_factor=0.1)
-    r.aug = TrainAugment(crop_size=crop, scale=(2 * crop[1], crop[0]), ratio_range=(0.5, 2.0), cat_max_ratio=0.75, photometric=True,
-                         batch_size=2, max_source_pixels=70 * 90, seed=11 + seed, rank=0, **NORM)
-    r.log = s2f.TrainLog(window=8) if log else None
-    example_in = torch.randn(2, 3, *crop, generator=torch.Generator().manual_seed(5)).cuda()
-    example_seg = torch.from_numpy(np.stack([region_map(*crop, [1, 2, 3]), region_map(*crop, [4, 5])])).cuda()
-    r.step = GraphedHungarianStep(model, example_in, example_seg, r.red, warmup=1, optimizer=r.opt, assign="device", log=r.log)
-    reset(r)
-    return r
-
-
-def reset(r):
-    """the rig at its start, by code that predates the loop"""
-    r.model.load_state_dict(r.sd0)
-    r.opt.exp_avg.zero_(), r.opt.exp_avg_sq.zero_(), r.opt.state.zero_()
-    r.sched.t = 0
-    r.sched._apply()
-    r.aug.rng = np.random.default_rng(np.random.SeedSequence([r.aug.seed, r.aug.rank]))
-    r.opt.mark_updated()
-    torch.cuda.synchronize()
-
-
-def scramble(r):
-    """a rig that has been somewhere else: nothing of what a resume restores is at its start"""
-    reset(r)
-    with torch.no_grad():
-        for t in r.model.state_dict().values():
-            t.add_(3) if t.dtype == torch.int64 else t.mul_(1.25)
-    r.opt.exp_avg.fill_(0.5), r.opt.exp_avg_sq.fill_(0.25), r.opt.state.fill_(7.0)
-    r.sched.t = 9
-    r.sched._apply()
-    r.aug.rng.random(5)
-
-
-def iterate(r, batches, first, count):
-    """`count` iterations from the `first`-th, as a caller wrote them before the loop existed"""
-    for it in range(first, first + count):
-        images, segs = batches[it % len(batches)]
-        r.aug(images, segs, out=(r.step.static_in, r.step.static_seg))
-        r.step()
-        r.sched.step()
-
-
-def state_of(r):
-    torch.cuda.synchronize()
-    out = {f"model:{k}": v.clone() for k, v in r.model.state_dict().items()}
-    for p, off, g in zip(r.opt.params, r.red.offsets, r.opt.param_groups):
-        out[f"exp_avg:{g['name']}"] = r.opt.exp_avg[off:off + p.numel()].clone()
-        out[f"exp_avg_sq:{g['name']}"] = r.opt.exp_avg_sq[off:off + p.numel()].clone()
-    out["step:"] = r.opt.state[4:5].clone()
-    return out
-
-
-@pytest.fixture(scope="module")
-def rigs():
-    import spike2former_amd as s2f
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = build(dict(plain=0, first=0, second=3)[name], log=name != "plain")
-        return cache[name]
-    get.batches = make_batches(s2f.WORKLOADS["C1_64"]["K"])
-    yield get
-    for r in cache.values():
-        for p in r.model.parameters():
-            p.grad = None
-    cache.clear()
-    gc.collect()
-
-
-def new_loop(r, batches, max_iters, hooks=(), **kw):
-    import spike2former_amd as s2f
-    return s2f.TrainLoop(r.step, r.opt, r.sched, r.aug, batches, max_iters=max_iters, hooks=list(hooks), **kw)
+recipes = dict(plain=dict(log=False), first=dict(), second=dict(seed=3))
+rigs = rigs_fixture(recipes)
 
 
 def test_the_loop_logs_what_the_step_computed(rigs, tmp_path):

@@ -1,9 +1,7 @@
 """GPU: the weight average (csrc/ema.hip, ema.WeightEMA, FlatAdamW(ema=...), runner.EMAHook) -- the two kernels on synthetic parameter
 lists against the numpy restatement of tests/ema_ref.py by bits, eager and as replays of captured launches; the average inside the
-optimizer's update on the tiny configuration C1_64 (the rigs of tests/test_gpu_train_loop.py, built here), eager and under
-GraphedHungarianStep replay, with and without accumulative_counts; TrainLoop with EMAHook: what validation sees, what the checkpoint
-holds, resume and load_from."""
-import gc
+optimizer's update on the tiny configuration C1_64 (the rigs of tests/step_rig.py), eager and under GraphedHungarianStep replay, with
+and without accumulative_counts; TrainLoop with EMAHook: what validation sees, what the checkpoint holds, resume and load_from."""
 import os
 import sys
 import types
@@ -14,13 +12,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ema_ref as ref          # noqa: E402
-from test_gpu_train_loop import CLIP, NORM, make_batches, region_map          # noqa: E402
+import step_rig as rig          # noqa: E402
+from step_rig import CLIP, KINDS, PARAMWISE, Elementwise, gaps, new_loop, reset, rigs_fixture, scramble, state_of          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 GUARD = -7.25
 EMA_CFG = dict(momentum=0.25, begin_iter=2)
-PARAMWISE = dict(custom_keys={"backbone": dict(lr_mult=0.1, decay_mult=1.0)})
 
 
 # ---------------------------------------------------------------------------------------------------- the kernels
@@ -234,67 +232,6 @@ def test_state_copy_serves_the_average(table):
 
 
 # ---------------------------------------------------------------------------------------------------- through the optimizer
-def build(ema=None, counts=None, step_optimizer=True, log=True, seed=0):
-    """tests/test_gpu_train_loop.py's rig; `ema`: FlatAdamW(ema=ema) (None: built WITHOUT the argument); `counts` likewise
-    accumulative_counts; `step_optimizer` False: the plain step -- the caller steps the optimizer eagerly"""
-    import spike2former_amd as s2f
-    from spike2former_amd.augment import TrainAugment
-    from spike2former_amd.dist import FlatGradAllReduce
-    from spike2former_amd.graph import GraphedHungarianStep
-    from spike2former_amd.init_utils import seeded_init
-    from spike2former_amd.train import FlatAdamW, LinearThenPoly
-    w = s2f.WORKLOADS["C1_64"]
-    crop = (w["H"], w["W"])
-    model = seeded_init(s2f.MODELS.build(s2f.model_cfg("C1_64"))).cuda().train()
-    s2f.set_keep_membrane(model, False)
-    r = types.SimpleNamespace(model=model, K=w["K"], crop=crop, seed=seed, eager=not step_optimizer)
-    r.sd0 = {k: v.clone() for k, v in model.state_dict().items()}
-    r.red = FlatGradAllReduce(model.parameters(), 1)
-    extra = {} if counts is None else dict(accumulative_counts=counts)
-    if ema is not None:
-        extra["ema"] = ema
-    r.opt = FlatAdamW(model, r.red, lr=0.001, weight_decay=0.005, clip_grad=CLIP, paramwise_cfg=PARAMWISE, **extra)
-    r.sched = LinearThenPoly(r.opt, warmup=4, total=20, start_factor=0.1)
-    r.aug = TrainAugment(crop_size=crop, scale=(2 * crop[1], crop[0]), ratio_range=(0.5, 2.0), cat_max_ratio=0.75, photometric=True,
-                         batch_size=2, max_source_pixels=70 * 90, seed=11 + seed, rank=0, **NORM)
-    r.log = s2f.TrainLog(window=8) if log else None
-    example_in = torch.randn(2, 3, *crop, generator=torch.Generator().manual_seed(5)).cuda()
-    example_seg = torch.from_numpy(np.stack([region_map(*crop, [1, 2, 3]), region_map(*crop, [4, 5])])).cuda()
-    r.step = GraphedHungarianStep(model, example_in, example_seg, r.red, warmup=1, optimizer=r.opt if step_optimizer else None,
-                                  assign="device", log=r.log)
-    reset(r)
-    return r
-
-
-def reset(r):
-    r.model.load_state_dict(r.sd0)
-    r.opt.exp_avg.zero_(), r.opt.exp_avg_sq.zero_(), r.opt.state.zero_()
-    r.sched.t = 0
-    r.sched._apply()
-    r.aug.rng = np.random.default_rng(np.random.SeedSequence([r.aug.seed, r.aug.rank]))
-    if r.opt.accum is not None:
-        r.opt.accum.count, r.opt.accum.total = 0, None
-        r.opt.accum.stats.zero_()
-    if r.opt.ema is not None:
-        r.opt.ema.reset()
-        r.opt.ema.partials.zero_()
-    r.opt.mark_updated()
-    torch.cuda.synchronize()
-
-
-def scramble(r):
-    reset(r)
-    with torch.no_grad():
-        for t in r.model.state_dict().values():
-            t.add_(3) if t.dtype == torch.int64 else t.mul_(1.25)
-    r.opt.exp_avg.fill_(0.5), r.opt.exp_avg_sq.fill_(0.25), r.opt.state.fill_(7.0)
-    if r.opt.ema is not None:
-        r.opt.ema.ema.fill_(0.125)
-    r.sched.t = 9
-    r.sched._apply()
-    r.aug.rng.random(5)
-
-
 def params_of(r):
     torch.cuda.synchronize()
     return [p.detach().cpu().numpy().reshape(-1).copy() for p in r.opt.params]
@@ -306,42 +243,19 @@ def average_of(r):
     return [flat[off:off + p.numel()].copy() for p, off in zip(r.opt.params, r.red.offsets)]
 
 
-def state_of(r):
-    torch.cuda.synchronize()
-    out = {f"model:{k}": v.clone() for k, v in r.model.state_dict().items()}
-    for p, off, g in zip(r.opt.params, r.red.offsets, r.opt.param_groups):
-        out[f"exp_avg:{g['name']}"] = r.opt.exp_avg[off:off + p.numel()].clone()
-        out[f"exp_avg_sq:{g['name']}"] = r.opt.exp_avg_sq[off:off + p.numel()].clone()
-    out["step:"] = r.opt.state[4:5].clone()
-    return out
-
-
-KINDS = ("model:", "exp_avg:", "exp_avg_sq:", "step:", "loss:")
-
-
-def gaps(a, b):
-    assert list(a) == list(b)
-    return {kind: max([float((a[k].double() - b[k].double()).abs().max()) for k in a if k.startswith(kind) and a[k].numel()] or [0.0])
-            for kind in KINDS}
-
-
 def iterate(r, batches, iterations, watch=None):
-    """`iterations` iterations from the rig's start, as a caller writes them; an eager rig's update is launched here.  -> the state,
-    with the loss terms of every iteration; `watch(iteration, updated)` runs behind each"""
+    """`iterations` iterations from the rig's start (step_rig.iterate: an eager rig's update is launched there) -> the state, with
+    the loss terms of every iteration; `watch(iteration, updated)` runs behind each"""
     reset(r)
     counts = 1 if r.opt.accum is None else r.opt.accum.counts
     losses = {}
-    for it in range(iterations):
-        images, segs = batches[it % len(batches)]
-        r.aug(images, segs, out=(r.step.static_in, r.step.static_seg))
-        r.step()
-        if r.eager:
-            r.opt.step()
-        r.sched.step()
+
+    def behind(it):
         for k, v in r.step.losses.items():
             losses[f"loss:{it}:{k}"] = v.detach().clone().reshape(-1)
         if watch is not None:
             watch(it, (it + 1) % counts == 0)
+    rig.iterate(r, batches, 0, iterations, behind)
     return {**state_of(r), **losses}
 
 
@@ -369,25 +283,9 @@ def follow(r, batches, iterations, begin_iter=2, momentum=0.25):
     return out
 
 
-@pytest.fixture(scope="module")
-def rigs():
-    import spike2former_amd as s2f
-    cache = {}
-    recipes = dict(ema=dict(ema=EMA_CFG), eager=dict(ema=EMA_CFG, step_optimizer=False, log=False), none=dict(),
-                   ema_acc2=dict(ema=EMA_CFG, counts=2), acc2=dict(counts=2))
-
-    def get(name):
-        if name not in cache:
-            cache[name] = build(**recipes[name])
-        return cache[name]
-    get.batches = make_batches(s2f.WORKLOADS["C1_64"]["K"])
-    get.runs = {}
-    yield get
-    for r in cache.values():
-        for p in r.model.parameters():
-            p.grad = None
-    cache.clear()
-    gc.collect()
+recipes = dict(ema=dict(ema=EMA_CFG), eager=dict(ema=EMA_CFG, step_optimizer=False, log=False), none=dict(),
+               ema_acc2=dict(ema=EMA_CFG, counts=2), acc2=dict(counts=2))
+rigs = rigs_fixture(recipes)
 
 
 def test_without_the_argument_nothing_is_allocated(rigs):
@@ -437,20 +335,6 @@ def test_the_step_is_what_it_is_without_the_average(rigs, pair):
             assert torch.equal(a[k], b[k]), k
         elif a[k].numel():
             assert float((a[k].double() - b[k].double()).abs().max()) <= 2.0 * d0[kind], (k, d0[kind])
-
-
-class Elementwise(torch.nn.Module):
-    """a model whose step IS bit-repeatable (tests/test_gpu_grad_accum.py's): element-wise products and torch's fixed-order sums"""
-
-    def __init__(self):
-        super().__init__()
-        g = torch.Generator().manual_seed(4)
-        self.backbone_w = torch.nn.Parameter(torch.randn(3, 33, 35, generator=g))
-        self.b = torch.nn.Parameter(torch.randn(35, generator=g))
-        self.gain = torch.nn.Parameter(torch.randn(1, generator=g))
-
-    def forward(self, x):
-        return (torch.tanh(x * self.backbone_w + self.b) * self.gain,)
 
 
 def test_a_step_without_atomics_is_bit_equal_with_and_without_the_average():
@@ -505,11 +389,6 @@ def test_a_step_without_atomics_is_bit_equal_with_and_without_the_average():
 
 # ---------------------------------------------------------------------------------------------------- through the loop
 HOOKS = [dict(type="EMAHook", **EMA_CFG), dict(type="LoggerHook", interval=3, window_size=2), dict(type="CheckpointHook", interval=3)]
-
-
-def new_loop(r, batches, max_iters, hooks=(), **kw):
-    import spike2former_amd as s2f
-    return s2f.TrainLoop(r.step, r.opt, r.sched, r.aug, batches, max_iters=max_iters, hooks=list(hooks), **kw)
 
 
 class Spy:
