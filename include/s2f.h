@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 53
+#define S2F_ABI_VERSION 54
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -939,6 +939,41 @@ int s2f_dcnv3_fwd_cm(const float* input, const float* offset, const float* mask,
 int s2f_dcnv3_bwd_cm(const float* input, const float* offset, const float* mask, const float* grad_output, float* grad_input,
                      float* grad_offset, float* grad_mask, int N, int H, int W, int G, int Cg, int Kh, int Kw, int stride_h,
                      int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, float offset_scale, void* stream);
+/* Which kernels the four entry points above run for a geometry (ABI 54) -- the very function they dispatch on; launches nothing,
+ * needs no device.  `aligned16`: the maps read and written in 16-byte vectors (input and output in the forward, input and grad_output in the
+ * backward) start at multiples of 16 bytes.  Writes S2F_DCN_ROUTE_FIELDS integers to `out`:
+ *   [0] the [N, H, W, C] forward kernel                       S2F_DCN_FWD_*
+ *   [1] the [N, H, W, C] backward route                       S2F_DCN_BWD_*
+ *   [2] workgroups per (n, group) slice of that backward:     1 (LDS), the band count (BANDED), 0 (global atomics)
+ *   [3] the channel-major entry points take the geometry      1 / 0 (= s2f_dcnv3_cm_ok); [4] .. [6] are 0 without it
+ *   [4] the channel-major forward kernel                      S2F_DCN_CM_FWD_*
+ *   [5] floats per staged pixel row of that kernel            Cg or Cg + 4
+ *   [6] the channel-major backward kernel's form              S2F_DCN_CM_BWD_*
+ * The backward route depends on the environment variable S2F_DCN_FORCE_BANDS (tests: a value b > 1 bands a map that would fit one
+ * workgroup into b bands), which is read here, per call.  The route ids, every one a distinct number:
+ *   FWD_K3C8     the 3x3 / Cg = 8 geometry unrolled, 16-byte accesses
+ *   FWD_VEC4     the generic loops, four channels at a time;   FWD_SCALAR  one at a time (Cg % 4 != 0, or a map off the 16-byte grid)
+ *   BWD_LDS      one workgroup per (n, group) slice, the scatter-add in LDS in fixed point
+ *   BWD_BANDED   several workgroups per slice, each owning a band of input rows
+ *   BWD_ATOMIC_VEC4 / _SCALAR   fp32 global atomics after a memset, four channels / one channel at a time
+ *   CM_FWD_K3C8 / CM_FWD_GENERIC   the channel-major forward with the 3x3 / Cg = 8 sizes compiled in / with the generic loops
+ *   CM_BWD_PLAIN one global round trip per 256-pixel chunk;  CM_BWD_PIPE  the next chunk prefetched into registers;
+ *   CM_BWD_PIPE_K3C8  the same with the 3x3 / Cg = 8 sizes compiled in */
+#define S2F_DCN_ROUTE_FIELDS 7
+#define S2F_DCN_FWD_K3C8 1
+#define S2F_DCN_FWD_VEC4 2
+#define S2F_DCN_FWD_SCALAR 3
+#define S2F_DCN_BWD_LDS 11
+#define S2F_DCN_BWD_BANDED 12
+#define S2F_DCN_BWD_ATOMIC_VEC4 13
+#define S2F_DCN_BWD_ATOMIC_SCALAR 14
+#define S2F_DCN_CM_FWD_K3C8 21
+#define S2F_DCN_CM_FWD_GENERIC 22
+#define S2F_DCN_CM_BWD_PLAIN 31
+#define S2F_DCN_CM_BWD_PIPE 32
+#define S2F_DCN_CM_BWD_PIPE_K3C8 33
+int s2f_dcnv3_route(int N, int H, int W, int G, int Cg, int Kh, int Kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                    int dil_w, int aligned16, int* out);
 
 /* ---- f2: one training iteration's parameter update (csrc/optim.hip, round 5) -------------------------------------------
  * Replaces mmengine OptimWrapper.update_params for the Spike2Former configs

@@ -154,6 +154,7 @@ SIGNATURES = {
     "s2f_dcnv3_cm_ok": (_i, [_i] * 13),
     "s2f_dcnv3_fwd_cm": (_i, [_p] * 4 + [_i] * 13 + [_f, _p]),
     "s2f_dcnv3_bwd_cm": (_i, [_p] * 7 + [_i] * 13 + [_f, _p]),
+    "s2f_dcnv3_route": (_i, [_i] * 14 + [ctypes.POINTER(_i)]),
     "s2f_grad_sqnorm_parts": (_i64, [_i64]),
     "s2f_grad_sqnorm": (_i, [_p, _i64, _p, _p]),
     "s2f_adamw_prepare": (_i, [_p, _i, _f, ctypes.c_double, ctypes.c_double, _p, _p]),

@@ -1,4 +1,6 @@
 """The spike-driven attention core (csrc/sdsa.hip) and the DCNv3 sampling core (csrc/dcnv3.hip)."""
+import ctypes
+
 import torch
 
 from .config import cfg
@@ -344,6 +346,23 @@ class _DCNv3CM(torch.autograd.Function):
 def dcnv3_cm_ok(N, H, W, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg):
     """An (image, group) slice of this geometry fits one workgroup's LDS: dcnv3_core_cm takes it (no launch)."""
     return bool(lib.s2f_dcnv3_cm_ok(N, H, W, G, Cg, kh, kw, sh, sw, ph, pw, dh, dw))
+
+
+# include/s2f.h: the route ids of s2f_dcnv3_route (tests/test_abi.py holds every one against its #define)
+DCN_ROUTE_FIELDS = 7
+DCN_FWD_K3C8, DCN_FWD_VEC4, DCN_FWD_SCALAR = 1, 2, 3
+DCN_BWD_LDS, DCN_BWD_BANDED, DCN_BWD_ATOMIC_VEC4, DCN_BWD_ATOMIC_SCALAR = 11, 12, 13, 14
+DCN_CM_FWD_K3C8, DCN_CM_FWD_GENERIC = 21, 22
+DCN_CM_BWD_PLAIN, DCN_CM_BWD_PIPE, DCN_CM_BWD_PIPE_K3C8 = 31, 32, 33
+
+
+def dcnv3_route(N, H, W, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, aligned16=True):
+    """The kernels dcnv3_core / dcnv3_core_cm run for this geometry, from the function the entry points dispatch on (no launch):
+    {fwd, bwd, bands, cm, cm_fwd, cm_rs, cm_bwd} with the DCN_* ids above; `aligned16`: the maps start at multiples of 16 bytes
+    (every tensor the allocator hands out does)."""
+    out = (ctypes.c_int * DCN_ROUTE_FIELDS)()
+    check(lib.s2f_dcnv3_route(N, H, W, G, Cg, kh, kw, sh, sw, ph, pw, dh, dw, int(bool(aligned16)), out), "s2f_dcnv3_route")
+    return dict(zip(("fwd", "bwd", "bands", "cm", "cm_fwd", "cm_rs", "cm_bwd"), out))
 
 
 def dcnv3_core_cm(x, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg, offset_scale):

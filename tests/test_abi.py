@@ -63,7 +63,17 @@ def test_mirrored_constants_match_the_header():
         "LSA_MAX_CLASSES": ops.LSA_MAX_CLASSES, "LSA_TILE_L2": ops.LSA_TILE_L2,
         "CENSUS_FIELDS": ops.CENSUS_FIELDS, "CENSUS_F32": ops._CENSUS_DTYPES[torch.float32],
         "CENSUS_BF16": ops._CENSUS_DTYPES[torch.bfloat16], "TRAIN_LOG_MAX_TERMS": ops.TRAIN_LOG_MAX_TERMS,
+        "DCN_ROUTE_FIELDS": ops.DCN_ROUTE_FIELDS, "DCN_FWD_K3C8": ops.DCN_FWD_K3C8, "DCN_FWD_VEC4": ops.DCN_FWD_VEC4,
+        "DCN_FWD_SCALAR": ops.DCN_FWD_SCALAR, "DCN_BWD_LDS": ops.DCN_BWD_LDS, "DCN_BWD_BANDED": ops.DCN_BWD_BANDED,
+        "DCN_BWD_ATOMIC_VEC4": ops.DCN_BWD_ATOMIC_VEC4, "DCN_BWD_ATOMIC_SCALAR": ops.DCN_BWD_ATOMIC_SCALAR,
+        "DCN_CM_FWD_K3C8": ops.DCN_CM_FWD_K3C8, "DCN_CM_FWD_GENERIC": ops.DCN_CM_FWD_GENERIC, "DCN_CM_BWD_PLAIN": ops.DCN_CM_BWD_PLAIN,
+        "DCN_CM_BWD_PIPE": ops.DCN_CM_BWD_PIPE, "DCN_CM_BWD_PIPE_K3C8": ops.DCN_CM_BWD_PIPE_K3C8,
     }
+    # every S2F_DCN_* id of the header is mirrored, and no two routes share a number
+    dcn = {k: v for k, v in header.items() if k.startswith("DCN_")}
+    assert set(dcn) == {k for k in mirrors if k.startswith("DCN_")}
+    ids = [v for k, v in dcn.items() if k != "DCN_ROUTE_FIELDS"]
+    assert len(set(ids)) == len(ids) == 12
     assert len(ops._CENSUS_DTYPES) == 2
     for name, value in mirrors.items():
         assert name in header, f"include/s2f.h has no integer #define S2F_{name}"
