@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 54
+#define S2F_ABI_VERSION 55
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -1218,6 +1218,53 @@ int s2f_seg_log_rows(const int32_t* partials, int nl, int per_layer, int K, int6
 #define S2F_CENSUS_BF16 1
 #define S2F_CENSUS_FIELDS 8
 int s2f_operand_census(const void* x, int dtype, int64_t n, int D, int64_t* row, void* stream);
+
+/* ---- firing maps: where in the picture a neuron fires (csrc/firingmap.hip, ABI 55) ---------------------------------------------------
+ * The figures above are one number per neuron; these are one per neuron AND pixel (spike2former_amd/firingmaps.py: FiringMaps).
+ *   s2f_firing_map    x: TB C P contiguous elements read as [TB][C][P], fp32 (S2F_CENSUS_F32) or bf16 (S2F_CENSUS_BF16), aligned to
+ *                     the element only (any element offset into a larger buffer; nothing outside x[0 .. TB C P) is read).  Row n of
+ *                     the leading dimension belongs to image n % B (t-major: the memory of a [T, B, C, H, W], [T B, C, H, W],
+ *                     [T, B, C, N] or [T B, C, N] tensor); TB % B == 0.  stats: int32 [B][4][P], 4-byte aligned.  For image b and
+ *                     pixel p, over all (n, c) with n % B == b:
+ *                       plane 0 += sum level(x)
+ *                       plane 1 += #{x != 0}           (-0.0 counts as zero)
+ *                       plane 2  = max(old, max level)
+ *                       plane 3 += #{x off the grid}
+ *                     level(x) and "off the grid" are the operand census's (below, "operand census"): ONE fp32 multiply of x (a bf16
+ *                     element widened exactly) by D converted to fp32, the integer test on that rounded product, the range
+ *                     0 .. 65535, a subnormal or non-finite x off the grid, level 0 where off the grid -- one device function for
+ *                     both kernels (csrc/census_level.h).
+ *                     flags: S2F_FIRING_MAP_ASSIGN -- the four planes are WRITTEN (plane 2 = the max level) instead of added to:
+ *                     the first pass needs no clear launch.  Any other bit is S2F_EINVAL.
+ *                     All sums are integers and one workgroup owns its pixels: no global atomics, two runs give the same bits,
+ *                     nothing outside stats[0 .. 4 B P) is written.  Consecutive lanes read consecutive pixels of one (n, c) plane,
+ *                     16 / 8 bytes per lane where P % 4 == 0 and x is aligned to four elements, one element per lane otherwise; for
+ *                     a small P the planes of a pixel tile are split over the waves of the workgroup and combined in LDS (the rule:
+ *                     the header of csrc/firingmap.hip).
+ *                     S2F_EINVAL before any launch: null pointer; TB, B or C < 1; TB % B != 0; P < 0; D < 1; unknown dtype or flags;
+ *                     (TB / B) C 65535 >= 2^31 (one pass could leave int32; the HOST keeps passes * that product inside the same
+ *                     bound).  S2F_EALIGN: x not aligned to its element, stats not to 4 bytes.  P == 0 launches nothing.  Nothing
+ *                     allocates or synchronises.
+ *   s2f_firing_draw   ONE launch per tile of a panel: plane, int32 [h][w] (4-byte aligned), is resampled to the picture's H x W,
+ *                     looked up in lut, uint8 [256][3] RGB, and blended into image, uint8 [H][W][3].  For output pixel (Y, X), all
+ *                     in int64:
+ *                       ny = max(0, (2 Y + 1) h - H);  y0 = ny / (2 H);  fy = ((ny - y0 2 H) 256) / (2 H);  y1 = min(y0 + 1, h - 1)
+ *                       the same for x                (the half-pixel centres of align_corners=False, weights in 1/256)
+ *                       s_ij = max(0, plane[y_i][x_j])
+ *                       v    = (256 - fy) ((256 - fx) s00 + fx s01) + fy ((256 - fx) s10 + fx s11)
+ *                       idx  = min(255, (255 v + 32768 full) / (65536 full));  col = lut[idx]
+ *                       out[ch] = (img[ch] (256 - a8) + col[ch] a8 + 128) >> 8
+ *                     This table and this resampling are the package's own specification (not OpenCV's applyColorMap / resize).
+ *                     flags: S2F_SEG_DRAW_BGR -- the picture's channels are swapped on read, as in s2f_seg_draw; out is always RGB.
+ *                     Row Y of out starts at byte Y out_row_bytes (>= 3 W): a tile is written straight into a panel of several.
+ *                     image and out may start at ANY byte (aligned words through LDS, the first and last word of a piece peeled);
+ *                     only the H rows of 3 W bytes are written.  S2F_EINVAL before any launch: null pointer; h, w, H or W < 1;
+ *                     H W >= 2^31 - 8 or h w >= 2^31; a8 outside 0 .. 256; full outside 1 .. 2^40; unknown flags;
+ *                     out_row_bytes < 3 W.  S2F_EALIGN: plane.  Nothing allocates or synchronises. */
+#define S2F_FIRING_MAP_ASSIGN 1
+int s2f_firing_map(const void* x, int dtype, int TB, int B, int C, int64_t P, int D, int32_t* stats, int flags, void* stream);
+int s2f_firing_draw(const uint8_t* image, const int32_t* plane, int h, int w, int64_t full, const uint8_t* lut, int a8, int flags, int H,
+                    int W, uint8_t* out, int64_t out_row_bytes, void* stream);
 
 /* ---- general strided fp32 product on the vector ALUs (csrc/bmm.hip, round 6) -----------------------------------------------
  * C[b][m][n] = sum_k A[b][m][k] B[b][k][n], every operand with explicit ELEMENT strides (a transposed or broadcast operand is a

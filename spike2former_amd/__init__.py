@@ -10,6 +10,7 @@ from .configs import WORKLOADS, model_cfg  # noqa: F401
 from .data_preprocessor import SegDataPreProcessor, SegDataSample  # noqa: F401
 from .devring import DeviceRing  # noqa: F401
 from .firing import FiringLog, FiringRead, FiringRecorder  # noqa: F401
+from .firingmaps import FiringMapRead, FiringMaps  # noqa: F401
 from .gradlog import GradLog, GradRead  # noqa: F401
 from .energy import EnergyReport, OpCensus  # noqa: F401
 from .loss import MaskFormerLoss, seg_to_instances  # noqa: F401
@@ -24,7 +25,7 @@ from .tta import SegTTAModel  # noqa: F401
 from .metrics import ConfusionMatrix, IoUMetric, evaluate  # noqa: F401
 from .seglog import SegLog, SegRead  # noqa: F401
 from .augment import TestAugment, TrainAugment  # noqa: F401
-from .visualization import SegLocalVisualizer, SegVisualizationHook  # noqa: F401
+from .visualization import FiringMapHook, SegLocalVisualizer, SegVisualizationHook  # noqa: F401
 from .train import LinearThenPoly, OptimWrapper, parse_losses, train_step  # noqa: F401
 from .ema import WeightEMA  # noqa: F401
 from .runner import CheckpointHook, EMAHook, LoggerHook, ParamSchedulerHook, TrainLog, TrainLoop, TrainState  # noqa: F401

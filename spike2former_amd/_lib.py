@@ -181,6 +181,8 @@ SIGNATURES = {
     "s2f_train_log_append": (_i, [_p, _i, _p, _i, _i, _p, _p]),
     "s2f_firing_log_append": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
     "s2f_operand_census": (_i, [_p, _i, _i64, _i, _p, _p]),
+    "s2f_firing_map": (_i, [_p, _i, _i, _i, _i, _i64, _i, _p, _i, _p]),
+    "s2f_firing_draw": (_i, [_p, _p, _i, _i, _i64, _p, _i, _i, _i, _i, _p, _i64, _p]),
     "s2f_grad_log_span_elems": (_i, []),
     "s2f_grad_log_partials": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _f, _p, _p]),
     "s2f_grad_log_rows": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _p]),

@@ -18,6 +18,7 @@
 //                        Partial sums: 32-bit over the at most 8 elements of one 16-byte group (8 * 65535 < 2^32), folded into
 //                        64-bit sums per thread after every group; everything from there on is 64-bit.
 #include "s2f_common.h"
+#include "census_level.h"
 
 namespace {
 
@@ -44,21 +45,14 @@ struct Acc {
   }
 };
 
-// One element, given as the bits of its fp32 value (a bf16 element: its 16 bits in the high half, which IS its fp32 value).
-// The product x * D is ONE fp32 multiply, rounded to nearest (exact for the powers of two every shipped config uses).  A subnormal x
-// is off the grid by its bits: x * D lies strictly between 0 and 1 there, and the verdict must not hang on the denormal mode.
+// One element, given as the bits of its fp32 value (census_level.h: the level and the grid test, shared with firingmap.hip).
 __device__ __forceinline__ void census_one(unsigned bits, float Df, Group& a) {
-  const unsigned mag = bits & 0x7fffffffu;
-  const float p = __uint_as_float(bits) * Df;
-  const bool finite = mag < 0x7f800000u;
-  const bool subnormal = mag != 0u && mag < 0x00800000u;
-  const bool on = finite && !subnormal && p >= 0.0f && p <= 65535.0f && p == truncf(p);
-  const unsigned level = on ? (unsigned)p : 0u;
-  a.level += level;
-  a.nonzero += mag != 0u;
-  a.off += !on;
-  a.nonfinite += !finite;
-  a.max_level = level > a.max_level ? level : a.max_level;
+  const S2fLevel e = s2f_census_level(bits, Df);
+  a.level += e.level;
+  a.nonzero += e.nonzero;
+  a.off += !e.on;
+  a.nonfinite += !e.finite;
+  a.max_level = e.level > a.max_level ? e.level : a.max_level;
 }
 
 __device__ __forceinline__ u64 wave_sum_u64(u64 v) {

@@ -12,8 +12,15 @@ the prediction there); the panel stays a device tensor and is read back only whe
     evaluate(SegTTAModel(model), batches, metric,
              hooks=[SegVisualizationHook(draw=True, interval=50, visualizer=vis, source=aug)])
 
+`SegLocalVisualizer.draw_firing` and `FiringMapHook` draw the firing maps of firingmaps.FiringMaps the same way: one tile per
+neuron, the picture under that neuron's heat map, ONE `ops.firing_draw` launch (s2f_firing_draw, csrc/firingmap.hip) per tile straight
+into a grid panel, in integer arithmetic throughout.
+
 Stated deviations: no window (`show`), no back end but LocalVisBackend, no palettes by data-set name, files
-written with PIL; a negative label paints nothing."""
+written with PIL; a negative label paints nothing; the firing maps' colour table and resampling are this package's own specification
+(not OpenCV's applyColorMap / mmengine's draw_featmap) and carry no legend text."""
+import json
+import math
 import os
 import os.path as osp
 import warnings
@@ -155,6 +162,85 @@ class SegLocalVisualizer:
         return drawn
 
 
+    # ---- firing maps
+    @staticmethod
+    def default_firing_lut():
+        """uint8 [256, 3] RGB, blue -> cyan -> yellow -> red: for v = i / 255 and k = 3, 2, 1 for r, g, b the byte
+        floor(255 clip(1.5 - |4 v - k|, 0, 1) + 0.5), in float64 on the host"""
+        v = np.arange(256, dtype=np.float64)[:, None] / 255.0
+        c = np.clip(1.5 - np.abs(4.0 * v - np.array([3.0, 2.0, 1.0])), 0.0, 1.0)
+        return np.floor(255.0 * c + 0.5).astype(np.uint8)
+
+    def _firing_lut_on(self, device, lut):
+        """uint8 [256, 3] on `device`; the default table is built once and uploaded once per device, any other one per call"""
+        if lut is not None:
+            t = _tensor(lut)
+            if t.dtype != torch.uint8 or tuple(t.shape) != (256, 3):
+                raise ValueError("draw_firing: lut is uint8 [256, 3]")
+            return t.to(device)
+        cache = self.__dict__.setdefault("_firing_lut_dev", {})
+        device = torch.device(device)
+        if device not in cache:
+            cache[device] = torch.from_numpy(self.default_firing_lut()).to(device)
+        return cache[device]
+
+    @staticmethod
+    def firing_full(read, name, image, which="rate", vmax=None):
+        """the plane value that maps to the last row of the colour table, an integer >= 1: the tile's own maximum (vmax None) or the
+        plane value of the absolute rate / active share `vmax` -> (plane index, full)"""
+        if which not in ("rate", "active"):
+            raise ValueError(f"draw_firing: which={which!r}: 'rate' (plane 0) or 'active' (plane 1)")
+        k = 0 if which == "rate" else 1
+        if vmax is None:
+            return k, max(1, int(read.planes[name][image, k].max()))
+        T, C, D, passes = read.meta[name]
+        return k, max(1, int(math.floor(float(vmax) * T * C * passes * (D if k == 0 else 1) + 0.5)))
+
+    def draw_firing(self, picture, read, image=0, names=None, which="rate", arrangement=None, alpha=0.5, vmax=None, lut=None,
+                    image_is_bgr=False, out_file=None, name="firing", step=0):
+        """One tile per neuron of `read` (a firingmaps.FiringMapRead; `names`: a subset, in this order): `picture` -- uint8
+        [H, W, 3], RGB or BGR with image_is_bgr -- under the heat map of image `image` of that neuron, plane 0 (`which="rate"`) or 1
+        ("active") resampled to H x W.  The tiles fill a grid row by row: `arrangement=(rows, cols)`, default the smallest near-square
+        one (cols = ceil(sqrt(n))); unused tiles stay black.  `vmax`: None -- every tile is scaled to its own maximum --, or one
+        absolute rate (share, for "active") for all tiles, so that layers and pictures compare.  `lut`: uint8 [256, 3] RGB (default:
+        default_firing_lut).  ONE ops.firing_draw launch per tile, written straight into the panel.  The panel goes to out_file, else,
+        with a save_dir, to {save_dir}/vis_image/{name}_{step}.png.  -> the panel, uint8 [rows H, cols W, 3] RGB on the device."""
+        names = list(read.names if names is None else names)
+        if not names:
+            raise ValueError("draw_firing: no neuron to draw (the read holds no map)")
+        missing = [n for n in names if n not in read.planes]
+        if missing:
+            raise KeyError(f"draw_firing: no map of {missing[0]!r} in the read")
+        picture = _tensor(picture)
+        if picture.dtype != torch.uint8 or picture.dim() != 3 or picture.shape[2] != 3:
+            raise ValueError("draw_firing: picture is uint8 [H, W, 3]")
+        if not picture.is_cuda and torch.cuda.is_available():
+            picture = picture.cuda(non_blocking=True)
+        device, (H, W) = picture.device, picture.shape[:2]
+        n = len(names)
+        if arrangement is None:
+            cols = int(math.ceil(math.sqrt(n)))
+            rows = (n + cols - 1) // cols
+        else:
+            rows, cols = (int(v) for v in arrangement)
+            if rows < 1 or cols < 1 or rows * cols < n:
+                raise ValueError(f"draw_firing: arrangement {tuple(arrangement)} holds fewer than {n} tiles")
+        table = self._firing_lut_on(device, lut)
+        panel = torch.zeros(rows * H, cols * W, 3, dtype=torch.uint8, device=device)
+        for i, neuron in enumerate(names):
+            k, full = self.firing_full(read, neuron, image, which, vmax)
+            plane = torch.from_numpy(np.ascontiguousarray(read.planes[neuron][image, k])).to(device, non_blocking=True)
+            r, c = divmod(i, cols)
+            ops.firing_draw(picture, plane, full, table, alpha, bgr=image_is_bgr, out=panel[r * H:(r + 1) * H, c * W:(c + 1) * W])
+        if out_file is None and self.save_dir is not None:
+            out_file = osp.join(self.save_dir, "vis_image", f"{name}_{step}.png")
+        if out_file is not None:
+            from PIL import Image
+            os.makedirs(osp.dirname(osp.abspath(out_file)), exist_ok=True)
+            Image.fromarray(panel.cpu().numpy()).save(out_file)
+        return panel
+
+
 @HOOKS.register_module()
 class SegVisualizationHook:
     """draw / interval / show / wait_time / backend_args as the reference; `visualizer`: the SegLocalVisualizer to draw with
@@ -209,6 +295,64 @@ class SegVisualizationHook:
             name = f"{mode}_{osp.basename(metrics._meta(output, 'img_path'))}"
             self.visualizer.add_datasample(name, picture, data_sample=output, show=self.show, wait_time=self.wait_time,
                                            step=self.step, image_is_bgr=bgr)
+
+    def after_val_iter(self, batch_idx, data_batch=None, outputs=None):
+        self._after_iter(batch_idx, data_batch, outputs, "val")
+
+    def after_test_iter(self, batch_idx, data_batch=None, outputs=None):
+        self._after_iter(batch_idx, data_batch, outputs, "test")
+
+
+@HOOKS.register_module()
+class FiringMapHook:
+    """For `evaluate(..., hooks=[...])`: the firing maps of `maps` (a firingmaps.FiringMaps) of every batch with (batch_idx + 1) %
+    interval == 0, as SegVisualizationHook picks its batches -- per sample one `draw_firing` panel named {mode}_{basename}_firing
+    (draw=False: none), the pictures taken from `source` by SegVisualizationHook's rules, and one line of the read's `summary()` per
+    drawn batch appended to {save_dir}/vis_data/firing_maps.jsonl; then the maps are cleared.  The neurons are hooked ONLY for the
+    batches that will be drawn: the hook attaches `maps` after the batch in front of a due one (at construction when the first batch
+    is due) and detaches it after drawing, so every other batch runs the fast routes and GraphedPredict's replays.  `draw_kwargs` go to
+    `draw_firing` (names, which, arrangement, alpha, vmax, lut)."""
+
+    def __init__(self, maps, interval=50, visualizer=None, source=None, draw=True, **draw_kwargs):
+        self.maps, self.interval, self.draw, self.source = maps, int(interval), bool(draw), source
+        self._visualizer = visualizer
+        self.draw_kwargs = draw_kwargs
+        self.step = 0
+        if self.interval < 1:
+            raise ValueError(f"FiringMapHook: interval {interval} is at least 1")
+        if self._due(0):
+            maps.attach()
+        else:
+            maps.detach()
+
+    visualizer = SegVisualizationHook.visualizer
+    _pictures = SegVisualizationHook._pictures
+
+    def _due(self, batch_idx):
+        return (batch_idx + 1) % self.interval == 0
+
+    def _after_iter(self, batch_idx, data_batch, outputs, mode):
+        if self._due(batch_idx) and self.maps.attached:
+            read = self.maps.read()
+            main = metrics._is_main_process() and bool(read.names)
+            if main and self.draw:
+                pictures, bgr = self._pictures(data_batch, outputs)          # (the source sees the neurons still hooked)
+            self.maps.detach()
+            self.maps.clear()
+            if main:
+                vis = self.visualizer
+                names = [f"{mode}_{osp.basename(metrics._meta(o, 'img_path'))}_firing" for o in outputs]
+                if self.draw:
+                    for i, (picture, name) in enumerate(zip(pictures, names)):
+                        vis.draw_firing(picture, read, image=i, image_is_bgr=bgr, name=name, step=self.step, **self.draw_kwargs)
+                if vis.save_dir is not None:
+                    path = osp.join(vis.save_dir, "vis_data", "firing_maps.jsonl")
+                    os.makedirs(osp.dirname(path), exist_ok=True)
+                    with open(path, "a") as f:
+                        f.write(json.dumps(dict(batch=batch_idx, step=self.step, samples=names, maps=read.summary())) + "\n")
+        if self._due(batch_idx + 1):
+            self.maps.clear()
+            self.maps.attach()
 
     def after_val_iter(self, batch_idx, data_batch=None, outputs=None):
         self._after_iter(batch_idx, data_batch, outputs, "val")
