@@ -74,7 +74,6 @@ class _SDSASpikes(torch.autograd.Function):
         kv = torch.empty(TB, heads, d, d, dtype=torch.float32, device=dev)
         ctx.cfg = (TB, C, Nq, Nk, d, heads, scale, packed, fuse, D, (qs, ks, vs))
         ctx.ptrs_of = (kp - qp, vp - qp)
-        ctx.set_materialize_grads(False)
         need = any(ctx.needs_input_grad[3:6])
         if fuse:
             y = torch.empty(TB, C, Nq, dtype=torch.bfloat16, device=dev)
@@ -84,22 +83,19 @@ class _SDSASpikes(torch.autograd.Function):
             check(lib.s2f_sdsa_lif_fwd_bf16(qp, kp, vp, qs, ks, vs, _ptr(y), _ptr(mask), _ptr(stats), _ptr(kv), TB, heads, d, Nq,
                                             scale, vth, D, _stream()), "s2f_sdsa_lif_fwd_bf16")
             ctx.save_for_backward(qd, kd, vd, kv, mask)
-            ctx.mark_non_differentiable(y)
-            return _new_tok(y), y
+            return _Outputs(ctx, kv).spikes(y, True, spare=False).done()
         o = torch.empty(TB, C, Nq, dtype=torch.float32, device=dev)
         check(lib.s2f_sdsa_fwd_bf16(qp, kp, vp, qs, ks, vs, _ptr(o), _ptr(kv), TB, heads, d, Nq, Nk, scale, _stream()),
               "s2f_sdsa_fwd_bf16")
         ctx.save_for_backward(qd, kd, vd, kv, None)
-        aux = o.new_empty(0)
-        ctx.mark_non_differentiable(aux)
-        return o, aux
+        return _Outputs(ctx, kv).spikes(o, False).done()
 
     @staticmethod
-    def backward(ctx, g, _g1):
+    def backward(ctx, g, _gdata, _g2):
         qd, kd, vd, kv, mask = ctx.saved_tensors
         TB, C, Nq, Nk, d, heads, scale, packed, fuse, D, (qs, ks, vs) = ctx.cfg
         if g is None:
-            return (None,) * 13
+            return _grads(ctx)
         g = g.contiguous()
         dev = g.device
         qp = qd.data_ptr()
@@ -126,7 +122,7 @@ class _SDSASpikes(torch.autograd.Function):
         ws = torch.empty_like(kv)
         check(lib.s2f_sdsa_bwd_bf16(qp, kp, vp, qs, ks, vs, _ptr(kv), _ptr(g), _ptr(mask) if fuse else 0, D, gq, gk, gv, *gs,
                                     _ptr(ws), TB, heads, d, Nq, Nk, scale, _stream()), "s2f_sdsa_bwd_bf16")
-        return (None, None, None) + out + (None,) * 7
+        return _grads(ctx, None, None, None, *out)
 
 
 class _SDSAMasked(torch.autograd.Function):
@@ -258,14 +254,14 @@ def _sdsa_spikes(qd, kd, vd, qt, kt, vt, heads, scale, packed, lif):
                                                _ptr(kv), TB, heads, d, Nq, Nk, scale, lif.v_threshold, lif.D, _stream()),
               "s2f_sdsa_lif_fwd_bf16_nomask")
         lif.v = 0.0
-        return Spikes(y, _new_tok(y))
+        return _spikes(None, y)
     if fuse and lif.stats is not None:
         lif.stats_elems += (qd.shape[1] if packed == 2 else qd.shape[0]) * C * Nq
-    o, ydata = _SDSASpikes.apply(qd, kd, vd, qt, kt, vt, heads, scale, packed, fuse, lif.D if fuse else 8,
-                                 lif.v_threshold if fuse else 1.0, lif.stats if fuse else None)
+    o, ydata, _ = _SDSASpikes.apply(qd, kd, vd, qt, kt, vt, heads, scale, packed, fuse, lif.D if fuse else 8,
+                                    lif.v_threshold if fuse else 1.0, lif.stats if fuse else None)
     if fuse:
         lif.v = 0.0
-        return Spikes(ydata, o)
+        return _spikes(o, ydata)
     return o if lif is None else lif.fire(o)
 
 
@@ -297,7 +293,7 @@ class _DCNv3(torch.autograd.Function):
         goff, gm = torch.empty_like(offset), torch.empty_like(mask)
         check(lib.s2f_dcnv3_bwd(_ptr(x), _ptr(offset), _ptr(mask), _ptr(go), _ptr(gx), _ptr(goff), _ptr(gm), *ctx.geo,
                                 ctx.osc, _stream()), "s2f_dcnv3_bwd")
-        return (gx, goff, gm) + (None,) * 11
+        return _grads(ctx, gx, goff, gm)
 
 
 def _tap_dcnv3(x, offset, mask, kh, kw, G, Cg):
@@ -340,7 +336,7 @@ class _DCNv3CM(torch.autograd.Function):
         goff, gm = torch.empty_like(offset), torch.empty_like(mask)
         check(lib.s2f_dcnv3_bwd_cm(_ptr(x), _ptr(offset), _ptr(mask), _ptr(go), _ptr(gx), _ptr(goff), _ptr(gm), *ctx.geo,
                                    ctx.osc, _stream()), "s2f_dcnv3_bwd_cm")
-        return (gx, goff, gm) + (None,) * 11
+        return _grads(ctx, gx, goff, gm)
 
 
 def dcnv3_cm_ok(N, H, W, kh, kw, sh, sw, ph, pw, dh, dw, G, Cg):

@@ -9,7 +9,8 @@ from .resize import upsample_bilinear
 # ------------------------------------------------------------------------------------------------ BN (+bias, +residual, +LIF)
 class _BNAct(torch.autograd.Function):
     """t = z + conv_bias ; u = BatchNorm(t) [+ residual] ; y = Q_IFNode(u)   in two streaming kernels forward
-    (statistics, apply) and two backward (reduce, apply).  Returns (u, y, v_out); unrequested ones are empty.
+    (statistics, apply) and two backward (reduce, apply).  Returns (u, y as the triple of _Outputs.spikes, v_out, border = BN(0),
+    pass-through of up_lo); unrequested ones are empty.
     up_lo: the residual given as the low-resolution map [N, C, H/2, W/2] whose exact-2x bilinear up-sampling is added -- formed inside
     the apply kernel (s2f_bn_act_up_fwd; the caller has asked s2f_bn_up_ok), its gradient returned through the up-sampling's adjoint.
     up_skip: also hand up_lo back as a pass-through for a second reader, whose gradient that adjoint sums (as ops.upsample_bilinear).
@@ -61,7 +62,7 @@ class _BNAct(torch.autograd.Function):
         u = torch.empty_like(z) if want_pre else None
         y = torch.empty(z.shape, dtype=torch.bfloat16 if bf16 else torch.float32, device=dev) if lif_on else None
         v_out = torch.empty_like(z) if (lif_on and keep_v) else None
-        need_grad = any(ctx.needs_input_grad[:5]) or (up_lo is not None and ctx.needs_input_grad[20])
+        need_grad = any(ctx.needs_input_grad[:5]) or (up_lo is not None and ctx.needs_input_grad[_UP_LO])
         # (training-mode short rows keep a per-channel mask layout of their own: s2f_bn_mask_words)
         nmask = int(lib.s2f_bn_mask_words(N, C, L)) if training else mask_words(z.numel())
         mask = torch.empty(nmask, dtype=torch.int64, device=dev) if (lif_on and need_grad) else None
@@ -84,20 +85,8 @@ class _BNAct(torch.autograd.Function):
         ctx.save_for_backward(z, conv_bias, gamma, stat, mask)
         ctx.cfg = (N, C, L, bool(training), D, vth, residual is not None, conv_bias is not None)
         ctx.up = None if up_lo is None else (z.shape[2] // 2, z.shape[3] // 2)
-        ctx.set_materialize_grads(False)
-        # bf16 spikes: slot 1 carries the autograd handle, slot 4 the (non-differentiable) bf16 tensor
-        ydata = z.new_empty(0)
-        tok2 = z.new_empty(0)          # bf16 spikes: a second handle for a second reader of the spike map (ops.Spikes.second)
-        if bf16:
-            ydata, y = y, _new_tok(z)
-            if cfg.FANOUT_PORTS:
-                tok2 = _new_tok(z)
-        outs = [t if t is not None else z.new_empty(0) for t in (u, y, v_out)]
-        ctx.mark_non_differentiable(border, ydata, *[o for o, t in zip(outs, (u, y, v_out)) if t is None])
-        if tok2.numel() == 0:
-            ctx.mark_non_differentiable(tok2)
-        through = _pass_through(ctx, z if up_in is None else up_in, up_skip and up_in is not None)
-        return tuple(outs) + (border, ydata, tok2, through)
+        return (_Outputs(ctx, z).grad(u).spikes(y, bf16).grad(v_out).fixed(border)
+                .through(up_in, up_skip and up_in is not None).done())
 
     @staticmethod
     def _forward_siblings(ctx, z, conv_bias, gamma, beta, running_mean, running_var, momentum, eps, lif_on, want_pre, D, vth, bf16,
@@ -123,26 +112,17 @@ class _BNAct(torch.autograd.Function):
         ctx.save_for_backward(z, conv_bias, gamma, stat, mask)
         ctx.cfg = (N, C, L, True, D, vth, False, conv_bias is not None)
         ctx.up = None
-        ctx.set_materialize_grads(False)
         border = stat.view(G, 3, C)[:, 2]
-        ydata, tok2, through = z.new_empty(0), z.new_empty(0), z.new_empty(0)
-        if bf16:
-            ydata, y = y, _new_tok(z)
-        outs = [t if t is not None else z.new_empty(0) for t in (u, y, None)]
-        ctx.mark_non_differentiable(border, ydata, tok2, through, *[o for o, t in zip(outs, (u, y, None)) if t is None])
-        return tuple(outs) + (border, ydata, tok2, through)
+        return _Outputs(ctx, z).grad(u).spikes(y, bf16, spare=False).grad(None).fixed(border).grad(None).done()
 
     @staticmethod
-    def backward(ctx, g_u, g_y, g_v, g_border, _g_ydata, g_y2, g_through=None):
+    def backward(ctx, g_u, g_y, _g_ydata, g_y2, g_v, _g_border, g_through):
         z, conv_bias, gamma, stat, mask = ctx.saved_tensors
         N, C, L, training, D, vth, has_res, has_bias = ctx.cfg
-
-        def prep(g):
-            return None if (g is None or g.numel() == 0) else g.contiguous()
-        g_u, g_y, g_v, g_y2 = prep(g_u), prep(g_y), prep(g_v), prep(g_y2)
+        g_u, g_y, g_v, g_y2 = _grad_in(g_u), _grad_in(g_y), _grad_in(g_v), _grad_in(g_y2)
         if ctx.groups > 1:
             if g_u is None and g_y is None:
-                return (None,) * 23
+                return _grads(ctx)
             G = ctx.groups
             gz = torch.empty_like(z)
             dgamma = torch.empty(G * C, dtype=torch.float32, device=z.device)
@@ -152,16 +132,16 @@ class _BNAct(torch.autograd.Function):
             check(lib.s2f_bn_act_bwd_grouped(_ptr(z), _ptr(conv_bias), _ptr(stat), _ptr(gamma), _ptr(g_u), _ptr(g_y), _ptr(mask),
                                              _ptr(gz), _ptr(dgamma), _ptr(dbeta), G, N, C, L, vth, D, _stream()),
                   "s2f_bn_act_bwd_grouped")
-            return (gz, None, dgamma, dbeta) + (None,) * 19          # (train mode: the conv bias has no gradient, as below)
+            return _grads(ctx, gz, None, dgamma, dbeta)          # (train mode: the conv bias has no gradient, as below)
         if g_y is None:
             g_y, g_y2 = g_y2, None
         if g_y2 is not None and not lib.s2f_bn_bwd_ports_ok(N, C, L, int(training), D):
             g_y, g_y2 = g_y + g_y2, None          # (a kernel form without the second port: the add the autograd engine would have made)
         if g_u is None and g_y is None and g_v is None:
-            return (None,) * 20 + (g_through, None, None)
+            return _grads(ctx, at={_UP_LO: g_through})
         dev = z.device
         gz = torch.empty_like(z)
-        g_res = torch.empty_like(z) if ((has_res and ctx.needs_input_grad[4]) or (ctx.up is not None and ctx.needs_input_grad[20])) else None
+        g_res = torch.empty_like(z) if ((has_res and ctx.needs_input_grad[4]) or (ctx.up is not None and ctx.needs_input_grad[_UP_LO])) else None
         dgamma = torch.empty(C, dtype=torch.float32, device=dev)
         dbeta = torch.empty(C, dtype=torch.float32, device=dev)
         ws = None if (training and lib.s2f_bn_single_pass(N, C, L)) else _take_zeroed(2 * C, dev)
@@ -186,8 +166,11 @@ class _BNAct(torch.autograd.Function):
                 g_lo = torch.empty(N, C, h, w, dtype=torch.float32, device=dev)
                 check(lib.s2f_upsample2x_bwd_add(_ptr(g_res), _ptr(None if g_through is None else g_through.contiguous()), _ptr(g_lo),
                                                  N * C, h, w, _stream()), "s2f_upsample2x_bwd_add")
-            return (gz, g_bias, dgamma, dbeta, None) + (None,) * 15 + (g_lo, None, None)
-        return (gz, g_bias, dgamma, dbeta, g_res) + (None,) * 18
+            return _grads(ctx, gz, g_bias, dgamma, dbeta, at={_UP_LO: g_lo})
+        return _grads(ctx, gz, g_bias, dgamma, dbeta, g_res)
+
+
+_UP_LO = _BNAct.forward.__code__.co_varnames.index("up_lo") - 1          # where `up_lo` stands among the inputs of _BNAct.apply
 
 
 def _partial_slots(z):
@@ -221,12 +204,9 @@ def bn_act_siblings(z, conv_bias, gamma, beta, running_mean, running_var, moment
     ops.cat_buffers); the running statistics are updated in place, num_batches_tracked is the caller's to count.
     -> (u [G, N, C, L] or None, y as Spikes [G, N, C, L] or None); slice g is what bn_act gives for z[g], bit for bit."""
     bf16 = bool(lif) and spikes_bf16_ok(D) and z[0].numel() % 4 == 0
-    u, y, _v, _border, ydata, _tok2, _thr = _BNAct.apply(z, conv_bias, gamma, beta, None, None, running_mean, running_var, None, True,
-                                                         momentum, eps, lif, want_pre, False, D, vth, None, bf16, None, None, False,
-                                                         int(z.shape[0]))
-    if lif:
-        y = Spikes(ydata, y) if bf16 else Spikes(y, None)
-    return (u if want_pre else None), (y if lif else None)
+    u, y, ydata, *_ = _BNAct.apply(z, conv_bias, gamma, beta, None, None, running_mean, running_var, None, True, momentum, eps, lif,
+                                   want_pre, False, D, vth, None, bf16, None, None, False, int(z.shape[0]))
+    return (u if want_pre else None), (_spikes(y, ydata) if lif else None)
 
 
 def bn_act(z, conv_bias, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, residual=None,
@@ -252,14 +232,12 @@ def bn_act(z, conv_bias, gamma, beta, running_mean, running_var, nbt, training, 
             if lo_skip:
                 residual, through = residual
     port = bool(up_lo is not None and lo_skip and cfg.FANOUT_PORTS)
-    u, y, v, border, ydata, tok2, thr = _BNAct.apply(z, conv_bias, gamma, beta, residual, v_in, running_mean, running_var, nbt,
+    u, y, ydata, tok2, v, border, thr = _BNAct.apply(z, conv_bias, gamma, beta, residual, v_in, running_mean, running_var, nbt,
                                                      training, momentum, eps, lif, want_pre, keep_v, D, vth, stats, bf16, partials,
                                                      up_lo, port)
     if port:
         through = thr
-    if lif:
-        y = Spikes(ydata, y, tok2 if tok2.numel() else None) if bf16 else Spikes(y, None)
-    out = (u if want_pre else None), (y if lif else None), (v if (lif and keep_v) else None)
+    out = (u if want_pre else None), (_spikes(y, ydata, tok2) if lif else None), (v if (lif and keep_v) else None)
     if want_border:
         out += (border,)
     return out + (through,) if residual_lo is not None else out
@@ -298,24 +276,15 @@ class _BN2Act(torch.autograd.Function):
                                   _ptr(v_out), _ptr(mask), _ptr(stats), N, C, L, vth, D, int(bf16), _stream()), "s2f_bn2_act_fwd")
         ctx.save_for_backward(z, g1, g2, stat, mask)
         ctx.cfg = (N, C, L, D, vth, residual is not None, eps2)
-        ctx.set_materialize_grads(False)
-        ydata = z.new_empty(0)
-        if bf16:
-            ydata, y = y, _new_tok(z)
-        outs = [t if t is not None else z.new_empty(0) for t in (u, y, v_out)]
-        ctx.mark_non_differentiable(ydata, *[o for o, t in zip(outs, (u, y, v_out)) if t is None])
-        return tuple(outs) + (ydata,)
+        return _Outputs(ctx, z).grad(u).spikes(y, bf16, spare=False).grad(v_out).done()
 
     @staticmethod
-    def backward(ctx, g_u, g_y, g_v, _g_ydata):
+    def backward(ctx, g_u, g_y, _g_ydata, _g_y2, g_v):
         z, g1, g2, stat, mask = ctx.saved_tensors
         N, C, L, D, vth, has_res, eps2 = ctx.cfg
-
-        def prep(g):
-            return None if (g is None or g.numel() == 0) else g.contiguous()
-        g_u, g_y, g_v = prep(g_u), prep(g_y), prep(g_v)
+        g_u, g_y, g_v = _grad_in(g_u), _grad_in(g_y), _grad_in(g_v)
         if g_u is None and g_y is None and g_v is None:
-            return (None,) * 24
+            return _grads(ctx)
         dev = z.device
         gz = torch.empty_like(z)
         g_res = torch.empty_like(z) if (has_res and ctx.needs_input_grad[5]) else None
@@ -327,7 +296,7 @@ class _BN2Act(torch.autograd.Function):
               "s2f_bn2_act_bwd")
         if ctx.needs_input_grad[6]:
             raise RuntimeError("gradient w.r.t. the incoming membrane is not supported by the fused BN+LIF op")
-        return (gz, d[0], d[1], d[2], d[3], g_res) + (None,) * 18
+        return _grads(ctx, gz, d[0], d[1], d[2], d[3], g_res)
 
 
 def bn2_act_ok(z):
@@ -339,12 +308,10 @@ def bn2_act(z, bn1, bn2, residual=None, lif=False, want_pre=True, v_in=None, kee
     """bn1 / bn2: objects with weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps (nn.BatchNorm or the
     concatenated twins of the batched q / k / v chain) -> (u or None, y (Spikes) or None, v_out or None)"""
     bf16 = bool(lif) and spikes_bf16_ok(D) and z.numel() % 4 == 0
-    u, y, v, ydata = _BN2Act.apply(z, bn1.weight, bn1.bias, bn2.weight, bn2.bias, residual, v_in, bn1.running_mean, bn1.running_var,
-                                   bn1.num_batches_tracked, bn1.momentum, bn1.eps, bn2.running_mean, bn2.running_var,
-                                   bn2.num_batches_tracked, bn2.momentum, bn2.eps, lif, want_pre, keep_v, D, vth, stats, bf16)
-    if lif:
-        y = Spikes(ydata, y) if bf16 else Spikes(y, None)
-    return (u if want_pre else None), (y if lif else None), (v if (lif and keep_v) else None)
+    u, y, ydata, _, v = _BN2Act.apply(z, bn1.weight, bn1.bias, bn2.weight, bn2.bias, residual, v_in, bn1.running_mean, bn1.running_var,
+                                      bn1.num_batches_tracked, bn1.momentum, bn1.eps, bn2.running_mean, bn2.running_var,
+                                      bn2.num_batches_tracked, bn2.momentum, bn2.eps, lif, want_pre, keep_v, D, vth, stats, bf16)
+    return (u if want_pre else None), (_spikes(y, ydata) if lif else None), (v if (lif and keep_v) else None)
 
 
 class _ScaleAffine(torch.autograd.Function):

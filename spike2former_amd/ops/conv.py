@@ -48,7 +48,7 @@ class _DWConv(torch.autograd.Function):
     def backward(ctx, gy, _gpart=None):
         x, w, border = ctx.saved_tensors
         if gy is None:
-            return (None,) * 6
+            return _grads(ctx)
         gy = gy.contiguous()
         N, C, H, W = x.shape
         K = w.shape[-1]
@@ -86,7 +86,7 @@ def dwconv_bn_lif_eval(x, w, pad, running_mean, running_var, gamma, beta, eps, b
                                         _ptr(running_mean), _ptr(running_var), _ptr(gamma), _ptr(beta), float(eps), _ptr(u), _ptr(y),
                                         _ptr(stats), N, C, H, W, K, pad, int(data.dtype == torch.bfloat16), float(vth), int(D), _stream()),
               "s2f_dwconv_bn_lif_fwd")
-    return u, (Spikes(y, _new_tok(y)) if lif else None)
+    return u, (_spikes(None, y) if lif else None)
 
 
 def dwconv(x, w, pad, border=None, stats=False):
@@ -210,7 +210,7 @@ class _ConvDense(torch.autograd.Function):
     def backward(ctx, gy, _gpart=None):
         cols, weight = ctx.saved_tensors
         if gy is None:
-            return (None,) * 8
+            return _grads(ctx)
         N, C, H, W, M, kh, kw, Ho, Wo, stride, padding, has_bias, use_mfma = ctx.geo
         gy = gy.contiguous().view(N, M, Ho * Wo)
         w2d = weight.view(M, -1)

@@ -136,37 +136,6 @@ def _need_cuda(*ts, spikes=None, fp32=True):
             raise RuntimeError(f"spike2former_amd ops compute in fp32; got {t.dtype}")
 
 
-def _pass_through(ctx, x_in, skip):
-    """The forward half of the pass-through port (cfg.FANOUT_PORTS), a Function's last output: x_in as the op received it, for a second
-    reader whose gradient the op's adjoint kernel sums (autograd hands out a view of it), or without `skip` an empty stand-in."""
-    if skip:
-        return x_in
-    aux = x_in.new_empty(0)
-    ctx.mark_non_differentiable(aux)
-    return aux
-
-
-def _pass_through_function(name, doc, launch, launch_bwd_add):
-    """-> the autograd.Function `name` of an op whose only differentiable input is x: apply(x, skip, *args) -> (y, pass-through of x).
-    The whole protocol of the port is here; the op supplies  launch(x, *args) -> y  on a contiguous fp32 CUDA x and
-    launch_bwd_add(gy, gskip, gx, *args):  gx (of x's shape) <- the adjoint of y plus gskip (both contiguous; gskip None: a null addend)."""
-
-    def forward(ctx, x, skip, *args):
-        _need_cuda(x)
-        ctx.x_shape, ctx.args = x.shape, args
-        ctx.set_materialize_grads(False)
-        return launch(x.contiguous(), *args), _pass_through(ctx, x, skip)
-
-    def backward(ctx, gy, gskip):
-        if gy is None:          # only the pass-through sent a gradient
-            return (gskip, None) + (None,) * len(ctx.args)
-        gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=gy.device)
-        launch_bwd_add(gy.contiguous(), None if gskip is None else gskip.contiguous(), gx, *ctx.args)
-        return (gx, None) + (None,) * len(ctx.args)
-
-    return type(name, (torch.autograd.Function,), {"__doc__": doc, "forward": staticmethod(forward), "backward": staticmethod(backward)})
-
-
 # Gradient sinks: {parameter data_ptr: fp32 view of a pre-zeroed flat gradient buffer}.  When a weight has a sink, the
 # split-K weight-gradient kernels add straight into it (no clearing memset per launch, no copy when the gradients are
 # packed) and autograd gets None for that weight.  Installed by dist.FlatGradAllReduce.install_sinks(); None = off.
@@ -512,6 +481,87 @@ class _SpikesToFloat(torch.autograd.Function):
 def _grad_pair(ctx_has_tok, g):
     """gradient slots of a (data, tok) operand pair"""
     return (None, g) if ctx_has_tok else (g, None)
+
+
+class _Outputs:
+    """What a Function that produces spike maps returns, collected in the order it returns it.  An output that was not asked for is
+    an empty stand-in (a Function returns tensors only), and `done()` names every output that carries no gradient in its ONE call of
+    ctx.mark_non_differentiable -- the context keeps the arguments of the last call only."""
+
+    def __init__(self, ctx, like):
+        self.ctx, self.outs, self.nograd, self.none = ctx, [], [], like.new_empty(0)
+
+    def grad(self, t):
+        """a differentiable output; None: a stand-in"""
+        if t is None:
+            return self.fixed(self.none)
+        self.outs.append(t)
+        return self
+
+    def fixed(self, t):
+        """an output without a gradient (bf16 spike data, BatchNorm's border)"""
+        self.outs.append(t)
+        self.nograd.append(t)
+        return self
+
+    def spikes(self, y, bf16, spare=None):
+        """a spike map as the triple `_spikes` reads: bf16 -- its autograd handle, the data, a spare handle for a second reader
+        (`spare`; default: with cfg.FANOUT_PORTS); fp32, or None -- y itself or its stand-in, and two stand-ins"""
+        if y is None or not bf16:
+            return self.grad(y).grad(None).grad(None)
+        spare = cfg.FANOUT_PORTS if spare is None else spare
+        return self.grad(_new_tok(y)).fixed(y).grad(_new_tok(y) if spare else None)
+
+    def through(self, x_in, skip):
+        """the pass-through port (cfg.FANOUT_PORTS): x_in as the op received it, for a second reader whose gradient the op's adjoint
+        kernel sums (autograd hands out a view of it); without `skip` a stand-in"""
+        return self.grad(x_in if skip else None)
+
+    def done(self):
+        self.ctx.set_materialize_grads(False)          # no zero-filled gradients for outputs nobody differentiated
+        self.ctx.mark_non_differentiable(*self.nograd)
+        return tuple(self.outs)
+
+
+def _spikes(handle, data, spare=None):
+    """The triple of _Outputs.spikes -> Spikes; handle None: bf16 spikes of a kernel outside autograd, on a fresh handle."""
+    if data.dtype != torch.bfloat16:
+        return Spikes(handle)
+    return Spikes(data, _new_tok(data) if handle is None else handle, spare if spare is not None and spare.numel() else None)
+
+
+def _grad_in(g):
+    """an incoming gradient as the kernels take it: contiguous; None when it is missing or belongs to a stand-in"""
+    return None if (g is None or g.numel() == 0) else g.contiguous()
+
+
+def _grads(ctx, *lead, at=None):
+    """What backward returns: `lead` for forward's first inputs, None for every other one but those of `at` {input index: gradient}."""
+    out = list(lead) + [None] * (len(ctx.needs_input_grad) - len(lead))
+    for i, g in (at or {}).items():
+        if g is not None:          # (an optional input that this call of apply left out has no slot)
+            out[i] = g
+    return tuple(out)
+
+
+def _pass_through_function(name, doc, launch, launch_bwd_add):
+    """-> the autograd.Function `name` of an op whose only differentiable input is x: apply(x, skip, *args) -> (y, pass-through of x).
+    The op supplies  launch(x, *args) -> y  on a contiguous fp32 CUDA x and
+    launch_bwd_add(gy, gskip, gx, *args):  gx (of x's shape) <- the adjoint of y plus gskip (both contiguous; gskip None: a null addend)."""
+
+    def forward(ctx, x, skip, *args):
+        _need_cuda(x)
+        ctx.x_shape, ctx.args = x.shape, args
+        return _Outputs(ctx, x).grad(launch(x.contiguous(), *args)).through(x, skip).done()
+
+    def backward(ctx, gy, gskip):
+        if gy is None:          # only the pass-through sent a gradient
+            return _grads(ctx, gskip)
+        gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=gy.device)
+        launch_bwd_add(gy.contiguous(), None if gskip is None else gskip.contiguous(), gx, *ctx.args)
+        return _grads(ctx, gx)
+
+    return type(name, (torch.autograd.Function,), {"__doc__": doc, "forward": staticmethod(forward), "backward": staticmethod(backward)})
 
 
 # ------------------------------------------------------------------------------------------------ parameter groups

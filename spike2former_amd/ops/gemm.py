@@ -303,7 +303,7 @@ class _SpikeGemm(torch.autograd.Function):
     def backward(ctx, gy, _gpart=None):
         x, w2d = ctx.saved_tensors
         if gy is None:
-            return (None,) * 5
+            return _grads(ctx)
         gy = gy.contiguous()
         B = x.shape[0]
         gx = gw = gb = None
@@ -441,7 +441,7 @@ def gemm_bn_lif_eval(x, w2d, conv_bias, running_mean, running_var, gamma, beta, 
         check(lib.s2f_gemm_bn_lif_fwd(_ptr(pack_weight(w2d)), _ptr(data), _ptr(conv_bias), _ptr(running_mean), _ptr(running_var),
                                       _ptr(gamma), _ptr(beta), float(eps), _ptr(residual), _ptr(u), _ptr(v_in), _ptr(y), _ptr(v_out),
                                       _ptr(stats), B, M, N, K, float(vth), int(D), _stream()), "s2f_gemm_bn_lif_fwd")
-    return u, (Spikes(y, _new_tok(y)) if lif else None), v_out
+    return u, (_spikes(None, y) if lif else None), v_out
 
 
 def dense_gemm_bn_lif_eval_ok(x, N):
@@ -477,7 +477,7 @@ def dense_gemm_bn_lif_eval(x, ws, conv_bias, running_mean, running_var, gamma, b
         check(lib.s2f_dense_gemm_bn_lif_fwd(packs, G, _ptr(x), G * K * N, K * N, _ptr(conv_bias), _ptr(running_mean), _ptr(running_var),
                                             _ptr(gamma), _ptr(beta), float(eps), _ptr(residual), _ptr(u), _ptr(y), _ptr(stats),
                                             B, K, M, N, float(vth), int(D), _stream()), "s2f_dense_gemm_bn_lif_fwd")
-    return u, (Spikes(y, _new_tok(y)) if lif else None)
+    return u, (_spikes(None, y) if lif else None)
 
 
 def conv3x3_bn_lif_eval(x, weight, running_mean, running_var, gamma, beta, eps, residual=None, want_pre=False, lif=False, v_in=None,
@@ -503,7 +503,7 @@ def conv3x3_bn_lif_eval(x, weight, running_mean, running_var, gamma, beta, eps, 
         check(lib.s2f_conv3x3_bn_lif_fwd(_ptr(pack_weight_conv3(weight)), _ptr(data), 0, _ptr(running_mean), _ptr(running_var),
                                          _ptr(gamma), _ptr(beta), float(eps), _ptr(residual), _ptr(u), _ptr(v_in), _ptr(y), _ptr(v_out),
                                          _ptr(stats), B, M, C, H, W, float(vth), int(D), _stream()), "s2f_conv3x3_bn_lif_fwd")
-    return u, (Spikes(y, _new_tok(y)) if lif else None), v_out
+    return u, (_spikes(None, y) if lif else None), v_out
 
 
 def spike_gemm(x, w2d, bias=None, stats=False):

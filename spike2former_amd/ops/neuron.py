@@ -9,7 +9,7 @@ from .reduce import channel_sum, sum_lead
 # ------------------------------------------------------------------------------------------------ LIF
 class _LIF(torch.autograd.Function):
     """One Q_IFNode call (neuron.py:166-197 + surrogate.py:522-538).  Saves 1 bit/element for backward.
-    Outputs (y or its handle, membrane, bf16 spikes, second handle, pass-through of x): the second handle serves a second consumer of
+    Outputs (y or its handle, bf16 spikes, second handle, membrane, pass-through of x): the second handle serves a second consumer of
     the spike map, the pass-through a residual branch that reads the neuron's input beside it (`x + f(Q_IFNode(x))`); the backward
     kernel sums the gradients arriving on them (s2f_lif_bwd_ports) -- the sums autograd's engine would launch an add for."""
 
@@ -30,25 +30,15 @@ class _LIF(torch.autograd.Function):
                               _stream()), "s2f_lif_fwd")
         ctx.save_for_backward(mask)
         ctx.D, ctx.vth, ctx.has_v = D, vth, v_in is not None
-        ctx.set_materialize_grads(False)          # no zero-filled stand-ins for the gradients of unused / bf16 outputs
-        aux = x.new_empty(0)
-        ctx.mark_non_differentiable(aux)
-        if v_out is None:
-            v_out = x.new_empty(0)
-            ctx.mark_non_differentiable(v_out)
-        through = _pass_through(ctx, x_in, skip)
-        if bf16:                       # (autograd handle, membrane, bf16 spikes, second handle, pass-through)
-            ctx.mark_non_differentiable(y)
-            return _new_tok(x), v_out, y, _new_tok(x), through
-        return y, v_out, aux, aux, through
+        return _Outputs(ctx, x).spikes(y, bf16).grad(v_out).through(x_in, skip).done()
 
     @staticmethod
-    def backward(ctx, gy, gv, _g2, gy2, gskip):
+    def backward(ctx, gy, _gdata, gy2, gv, gskip):
         (mask,) = ctx.saved_tensors
         if gy is None and gy2 is not None:
             gy, gy2 = gy2, None
         if gy is None and gv is None:
-            return (gskip,) + (None,) * 7
+            return _grads(ctx, gskip)
         if gy is None:                              # only the membrane carries a gradient
             gy = torch.zeros_like(gv)
         gy = gy.contiguous()
@@ -66,7 +56,7 @@ class _LIF(torch.autograd.Function):
         check(lib.s2f_lif_bwd_ports(_ptr(gy), _ptr(gy2), _ptr(gv), _ptr(mask), _ptr(gskip) if fold else 0, _ptr(gx), gy.numel(), ctx.vth,
                                     ctx.D, _stream()), "s2f_lif_bwd_ports")
         gx_in = gx if (gskip is None or fold) else gx + gskip.view(gx.shape)
-        return gx_in, (gx if ctx.has_v else None), None, None, None, None, None, None
+        return _grads(ctx, gx_in, gx if ctx.has_v else None)
 
 
 class _LIFLeaky(torch.autograd.Function):
@@ -87,18 +77,14 @@ class _LIFLeaky(torch.autograd.Function):
                                     int(bool(decay_input)), 0, _stream()), "s2f_lif_leaky_fwd")
         ctx.save_for_backward(mask)
         ctx.cfg = (D, vth, tau, int(bool(decay_input)), v_in is not None)
-        ctx.set_materialize_grads(False)
-        if v_out is None:
-            v_out = x.new_empty(0)
-            ctx.mark_non_differentiable(v_out)
-        return y, v_out
+        return _Outputs(ctx, x).grad(y).grad(v_out).done()
 
     @staticmethod
     def backward(ctx, gy, gv):
         (mask,) = ctx.saved_tensors
         D, vth, tau, di, has_v = ctx.cfg
         if gy is None and gv is None:
-            return (None,) * 8
+            return _grads(ctx)
         if gy is None:
             gy = torch.zeros_like(gv)
         gy = _aligned16(gy)
@@ -110,7 +96,7 @@ class _LIFLeaky(torch.autograd.Function):
         gvi = torch.empty(gy.shape, dtype=torch.float32, device=gy.device) if has_v else None
         check(lib.s2f_lif_leaky_bwd(_ptr(gy), _ptr(gv), _ptr(mask), _ptr(gx), _ptr(gvi), gy.numel(), vth, D, tau, di, _stream()),
               "s2f_lif_leaky_bwd")
-        return gx, gvi, None, None, None, None, None, None
+        return _grads(ctx, gx, gvi)
 
 
 def lif_leaky(x, v_in=None, D=8, vth=1.0, tau=2.0, decay_input=True, keep_v=True, stats=None):
@@ -126,9 +112,9 @@ def lif(x, v_in=None, D=8, vth=1.0, keep_v=True, stats=None, spikes=False, skip=
     bf16 = bool(spikes) and spikes_bf16_ok(D) and x.numel() % 4 == 0 and x.numel() > 0
     ports = cfg.FANOUT_PORTS
     fold = bool(skip) and ports and v_in is None and x.numel() > 0
-    y, v, data, tok2, through = _LIF.apply(x, v_in, D, vth, keep_v, stats, bf16, fold)
+    y, data, tok2, v, through = _LIF.apply(x, v_in, D, vth, keep_v, stats, bf16, fold)
     if spikes:
-        y = Spikes(data, y, tok2 if ports else None) if bf16 else Spikes(y, None)
+        y = _spikes(y, data, tok2)
     if skip:
         return y, (v if keep_v else None), (through if fold else x)
     return y, (v if keep_v else None)
@@ -137,9 +123,9 @@ def lif(x, v_in=None, D=8, vth=1.0, keep_v=True, stats=None, spikes=False, skip=
 class _Sum2LIF(torch.autograd.Function):
     """The decoder's value / key neurons on  a = x + e[c]  and  a + pos[b]  in one pass, neither sum materialised
     (maskformer_head.py:535-540 + transformer.py:626-629; s2f.h s2f_sum2_lif_fwd).  Reset, stateless neurons only.
-    Outputs (key handle, value handle, bf16 key spikes, bf16 value spikes, second key handle, second value handle, pass-through of
-    x): see _LIF -- a memory level's spikes are read by two decoder layers, the decoder's `query + attention(query)` reads the query
-    beside its neurons; the gradients arriving on the extra outputs are summed in the backward kernel (s2f_sum2_lif_bwd_ports)."""
+    Outputs (key handle, bf16 key spikes, second key handle, the same three of the value spikes, pass-through of x): see _LIF -- a
+    memory level's spikes are read by two decoder layers, the decoder's `query + attention(query)` reads the query beside
+    its neurons; the gradients arriving on the extra outputs are summed in the backward kernel (s2f_sum2_lif_bwd_ports)."""
 
     @staticmethod
     def forward(ctx, x, e, pos, B, D, vth, bf16, skip):
@@ -158,24 +144,17 @@ class _Sum2LIF(torch.autograd.Function):
         ctx.save_for_backward(mk, mv)
         ctx.D = D
         ctx.tb = (TB // B, B)
-        ctx.set_materialize_grads(False)
-        aux = x.new_empty(0)
-        ctx.mark_non_differentiable(aux)
-        through = _pass_through(ctx, x_in, skip)
-        if bf16:
-            ctx.mark_non_differentiable(yk, yv)
-            return _new_tok(x), _new_tok(x), yk, yv, _new_tok(x), _new_tok(x), through
-        return yk, yv, aux, aux, aux, aux, through
+        return _Outputs(ctx, x).spikes(yk, bf16).spikes(yv, bf16).through(x_in, skip).done()
 
     @staticmethod
-    def backward(ctx, gk, gv, _a, _b, gk2, gv2, gskip):
+    def backward(ctx, gk, _a, gk2, gv, _b, gv2, gskip):
         mk, mv = ctx.saved_tensors
         if gk is None and gk2 is not None:
             gk, gk2 = gk2, None
         if gv is None and gv2 is not None:
             gv, gv2 = gv2, None
         if gk is None and gv is None:
-            return (gskip,) + (None,) * 7
+            return _grads(ctx, gskip)
         # (either gradient may be missing -- a neuron whose spikes nobody differentiated: the kernel takes NULL for zero)
         gk, gv, gk2, gv2 = (None if g is None else g.contiguous() for g in (gk, gv, gk2, gv2))
         like = gk if gk is not None else gv
@@ -196,17 +175,16 @@ class _Sum2LIF(torch.autograd.Function):
             T, B = ctx.tb
             gpos = sum_lead(gxk.view(T, B, *like.shape[1:])) if want_pos else torch.zeros(B, *like.shape[1:], dtype=like.dtype, device=like.device)
         gx_in = gx if (gskip is None or fold) else gx + gskip.view(gx.shape)
-        return gx_in, ge, gpos, None, None, None, None, None
+        return _grads(ctx, gx_in, ge, gpos)
 
 
 def sum2_lif(x, e, pos, B, D=8, vth=1.0, skip=False):
     """x [T*B, C, L], e [C], pos [B, C, L] -> (Q_IFNode(x + e + pos), Q_IFNode(x + e))  (key spikes, value spikes), as Spikes with a
     spare handle each; `skip`: -> (key, value, x') with x' = x for a residual branch (see ops.lif)."""
     bf16 = spikes_bf16_ok(D)
-    ports = cfg.FANOUT_PORTS
-    fold = bool(skip) and ports
-    hk, hv, dk, dv, hk2, hv2, through = _Sum2LIF.apply(x, e, pos, B, D, vth, bf16, fold)
-    out = (Spikes(dk, hk, hk2 if ports else None), Spikes(dv, hv, hv2 if ports else None)) if bf16 else (Spikes(hk), Spikes(hv))
+    fold = bool(skip) and cfg.FANOUT_PORTS
+    *kv, through = _Sum2LIF.apply(x, e, pos, B, D, vth, bf16, fold)
+    out = (_spikes(*kv[:3]), _spikes(*kv[3:]))
     return out + ((through if fold else x),) if skip else out
 
 

@@ -438,3 +438,51 @@ def test_a_retired_environment_variable_changes_nothing():
     assert snapshot(dict(clean, S2F_PGEMM="0")) == base
     assert snapshot(dict(clean, **retired)) == base
     assert snapshot(dict(clean, S2F_DW_PIPE="0")) == dict(base, DW_PIPE=False)          # a switch that stayed is still read
+
+
+@pytest.mark.parametrize("keep_v", [False, True])
+@pytest.mark.parametrize("bf16", [False, True])
+@pytest.mark.parametrize("spare", [False, True])
+@pytest.mark.parametrize("skip", [False, True])
+def test_output_collector_marks_exactly_the_outputs_without_a_gradient(keep_v, bf16, spare, skip):
+    """ops.core._Outputs on a toy neuron: (spike triple, membrane, pass-through).  Exactly the handles, the fp32 spikes and the
+    requested fp32 outputs are differentiable -- stand-ins and bf16 data are not, whichever of them the forward appended last (the
+    context keeps only ONE call of mark_non_differentiable) -- and a gradient on every differentiable output reaches backward."""
+    from spike2former_amd.ops.core import _Outputs, _grad_in, _grads, _spikes
+    seen = []
+
+    class Toy(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, factor, keep_v, bf16, spare, skip):
+            ctx.factor = factor
+            y = (x * factor).to(torch.bfloat16 if bf16 else torch.float32)
+            return _Outputs(ctx, x).spikes(y, bf16, spare).grad(x + 1 if keep_v else None).through(x, skip).done()
+
+        @staticmethod
+        def backward(ctx, gy, gdata, gy2, gv, gskip):
+            seen.append([g is not None for g in (gy, gdata, gy2, gv, gskip)])
+            gx = sum(g * k for g, k in ((_grad_in(gy), ctx.factor), (_grad_in(gy2), ctx.factor), (gv, 1.0), (gskip, 1.0)) if g is not None)
+            return _grads(ctx, gx)
+
+    x = torch.arange(8.0).view(2, 4).requires_grad_()
+    outs = Toy.apply(x * 1.0, 0.5, keep_v, bf16, spare, skip)
+    want = [True, False, bf16 and spare, keep_v, skip]
+    assert [o.requires_grad for o in outs] == want
+    assert [o.grad_fn is not None for o in outs] == want
+    assert [o.numel() == 0 for o in outs] == [False, not bf16, not (bf16 and spare), not keep_v, not skip]
+    s = _spikes(*outs[:3])
+    assert (s.data is outs[1] and s.tok is outs[0] and s.data.dtype == torch.bfloat16) if bf16 else (s.data is outs[0] and s.tok is None)
+    assert s.tok2 is (outs[2] if bf16 and spare else None)
+    assert torch.equal(s.data.float(), x.detach() * 0.5)
+    sum((o * (i + 1)).sum() for i, (o, w) in enumerate(zip(outs, want)) if w).backward()
+    assert seen == [want]          # no zero-filled gradient for an output nobody differentiated
+    slope = 0.5 * (1 + 3 * (bf16 and spare)) + 4 * keep_v + 5 * skip
+    assert torch.equal(x.grad, torch.full((2, 4), slope))
+
+
+def test_bn_act_finds_up_lo_in_its_own_signature():
+    """_BNAct's backward places the gradient of `up_lo` by the argument's position in forward, read from the signature"""
+    import inspect
+    from spike2former_amd.ops import bn
+    names = list(inspect.signature(bn._BNAct.forward).parameters)
+    assert names[0] == "ctx" and names[1 + bn._UP_LO] == "up_lo"
