@@ -29,7 +29,7 @@ extern "C" {
 #define S2F_EALIGN (-2)   /* pointer not aligned as required */
 #define S2F_ELAUNCH (-3)  /* hipLaunch / runtime error */
 
-#define S2F_ABI_VERSION 55
+#define S2F_ABI_VERSION 56
 #define S2F_STAT_SLOTS 256
 
 int s2f_version(void);
@@ -1176,7 +1176,48 @@ int s2f_seg_log_partials(const float* mask, const float* cls, const uint8_t* seg
 int s2f_seg_log_rows(const int32_t* partials, int nl, int per_layer, int K, int64_t* ring, int window, int32_t* streak, int patience,
                      int64_t* head, void* stream);
 
-/* ---- operand census: what a synaptic op really reads (csrc/opcensus.hip, ABI 49) -----------------------------------------------------
+/* ---- match log: what the Hungarian assignment did, from inside the captured step (csrc/matchlog.hip, ABI 56) ------------------------
+ * With the assignment on the device (s2f_lsa_tables) its tables never reach the host.  Two read-only launches behind it turn them,
+ * the costs the assignment read and the decoder's class logits into one row of figures per replay, in a ring the host reads once per
+ * log line.  None of the figures has a counterpart in the reference, whose MaskFormerHead logs losses only; `cls_hit` is the count
+ * behind DETR's class_error.  cost fp32 [L][B][Q][K] and row_class int32 [B][L*Q] as s2f_lsa_tables reads and writes them, cls fp32
+ * [L][B][Q][K+1] (logits, the void column last).  Query q of (layer l, image b) is MATCHED to class c = row_class[b][l*Q + q] where
+ * 0 <= c < K; ANY other value (-1, or one >= K) counts as unmatched and is never used as an index.  Per layer l, summed over the B
+ * images, S2F_MATCH_LOG_FIELDS = 6 int64 fields:
+ *   [0] matched        the matched queries
+ *   [1] cost           the bits of the fp64 sum of (double)cost[l][b][q][c] over the matched pairs: per (l, b) ONE serial sum from +0.0
+ *                      with q ascending, then the images' sums added from +0.0 with b ascending.  No float atomics, no tree.
+ *   [2] greedy         the matched pairs whose q is the first arg-min of cost[l][b][:][c] over all Q queries: best = the value at
+ *                      q = 0, then strict < in fp32 with q ascending (a NaN at q = 0 stands, any other NaN never wins)
+ *   [3] moved          for l >= 1: the matched pairs whose class c is matched to another query in layer l-1 of the same image, or to
+ *                      none there; 0 for l = 0.  (Were a class named by two queries of one layer, its lowest query owns it.)
+ *   [4] cls_hit        the matched pairs whose first arg-max of cls[l][b][q][0 .. K] equals c: best = the value at index 0, then
+ *                      strict > with the index ascending (a NaN at index 0 stands, any other NaN never wins)
+ *   [5] unmatched_obj  the unmatched queries whose first arg-max is not the void column K
+ * A problem the assignment flagged (its rows all -1) so adds to [5] alone.  usage[q] = the images in which the LAST layer matched
+ * query q.  A row of the ring is int64 [6L] followed by usage as int32 [Q], padded with a zero to whole 8-byte words:
+ * 6L + ceil(Q/2) words.
+ *   s2f_match_log_partials  one workgroup per (l, b): partials int64 [L][B][6] and flags int32 [B][Q] (1: the last layer matched q in
+ *                           image b), plain stores, every word written.  S2F_EINVAL before any launch: null pointer, L outside
+ *                           1 .. S2F_MATCH_LOG_MAX_LAYERS, B outside 1 .. 65535, Q outside 1 .. S2F_LSA_MAX_QUERIES, K outside
+ *                           1 .. S2F_LSA_MAX_CLASSES; S2F_EALIGN: partials not 8-byte, another pointer not 4-byte aligned.
+ *   s2f_match_log_rows      ONE workgroup: row head[0] % window of ring int64 [window][6L + ceil(Q/2)] <- the sums above
+ *                           (overwritten, never accumulated into); idle int32 [Q]: idle[q] = 0 where usage[q] > 0, + 1 otherwise;
+ *                           head int64 [4], initialised by the caller to {0, -1, 0, 0}: where idle[q] REACHES `patience` the event
+ *                           head[0] * 2^32 + q is offered to head[1], which keeps the minimum under UNSIGNED comparison (-1: none
+ *                           yet); then head[0] + 1 is stored.  One workgroup: head[2] (the ticket of the other rings) is not used.
+ *                           S2F_EINVAL: null pointer, L / B / Q as above, window or patience < 1; S2F_EALIGN: partials / ring / head
+ *                           not 8-byte, usage / idle not 4-byte aligned.
+ * Both launches only READ cost, cls and row_class; every loop is bounded by L, B, Q or K; nothing allocates or synchronises:
+ * capturable behind the step's last launch. */
+#define S2F_MATCH_LOG_MAX_LAYERS 16
+#define S2F_MATCH_LOG_FIELDS 6
+int s2f_match_log_partials(const float* cost, const float* cls, const int32_t* row_class, int L, int B, int Q, int K, int64_t* partials,
+                           int32_t* usage, void* stream);
+int s2f_match_log_rows(const int64_t* partials, const int32_t* usage, int L, int B, int Q, int64_t* ring, int window, int32_t* idle,
+                       int patience, int64_t* head, void* stream);
+
+/* ---- operand census:what a synaptic op really reads (csrc/opcensus.hip, ABI 49) -----------------------------------------------------
  * The reference's tools/cal_firing_num.py stops at firing rates per neuron (fr_rate.csv) and leaves operations and energy to a
  * spreadsheet.  Not every synaptic layer reads a neuron's output (SepConv.pwconv2 reads the depthwise convolution's real-valued map, the
  * stem the image, the attention / DCNv3 / mask products tensors no neuron counter describes), so the census measures the OPERANDS:

@@ -24,6 +24,7 @@ from .segmentor import EncoderDecoder, ResetModelHook, headline_loss  # noqa: F4
 from .tta import SegTTAModel  # noqa: F401
 from .metrics import ConfusionMatrix, IoUMetric, evaluate  # noqa: F401
 from .seglog import SegLog, SegRead  # noqa: F401
+from .matchlog import MatchLog, MatchRead  # noqa: F401
 from .augment import TestAugment, TrainAugment  # noqa: F401
 from .visualization import FiringMapHook, SegLocalVisualizer, SegVisualizationHook  # noqa: F401
 from .train import LinearThenPoly, OptimWrapper, parse_losses, train_step  # noqa: F401

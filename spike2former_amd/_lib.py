@@ -189,6 +189,8 @@ SIGNATURES = {
     "s2f_seg_log_tile_pixels": (_i, []),
     "s2f_seg_log_partials": (_i, [_p, _p, _p, _p] + [_i] * 7 + [_p, _p]),
     "s2f_seg_log_rows": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p, _p]),
+    "s2f_match_log_partials": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "s2f_match_log_rows": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _p]),
 }
 
 

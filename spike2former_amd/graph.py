@@ -57,7 +57,7 @@ def step_tail(optimizer_in_step, accumulating, world):
 class _Captured:
     """A step with static input `static_in`, recorded as one hipGraph per stage.  `red`: the flat gradient buffer
     (dist.FlatGradAllReduce) of the steps that pack into one; `optimizer`: a train.FlatAdamW captured behind the packing."""
-    optimizer = log = firing = seg_log = None
+    optimizer = log = firing = seg_log = match_log = None
 
     def _tail(self):
         return step_tail(self.optimizer is not None, self.accum is not None, _world_size())
@@ -94,10 +94,10 @@ class _Captured:
 
     def _after_capture(self):
         """once the capture has ended: the table the log's launch reads is uploaded (nothing may be while a capture records), and
-        the firing, gradient and segmentation logs start afresh -- what the warm-up passes appended is not row 0"""
+        the firing, gradient, segmentation and match logs start afresh -- what the warm-up passes appended is not row 0"""
         if self.log is not None and self._tail()[1] != "caller":
             self.log.bind(self.log_terms)
-        for ring in (self.firing, self.grad_log, self.seg_log):
+        for ring in (self.firing, self.grad_log, self.seg_log, self.match_log):
             if ring is not None:
                 ring.clear()
 
@@ -337,16 +337,24 @@ class GraphedHungarianStep(_Captured):
     mask logits of the scored decoder layers, detached -- against `static_seg` at the mask resolution and append the per-class areas
     of intersect_and_union to a ring: train-crop accuracy and mIoU of EVERY iteration (a micro-batch, with an accumulating
     optimizer), read by runner.LoggerHook with the losses; in the one-graph and the two-graph forms alike, and at every world size
-    (each rank scores its own crops).  None: nothing is allocated, launched or captured."""
+    (each rank scores its own crops).  None: nothing is allocated, launched or captured.
+
+    `match_log` (matchlog.MatchLog): behind the assignment and behind `seg_log`, the last graph ends with two more read-only launches
+    that turn the assignment's `row_class`, the costs it read and the class scores into one row of figures per replay -- matched
+    pairs and their cost, greedy and moved shares, DETR's class_error, unmatched queries that claim an object, the usage of every
+    query -- for all decoder layers, read by runner.LoggerHook with the losses; on both `assign` routes (two graphs: in graph B,
+    after the tables' upload).  With it the step HOLDS the tensors of `_costs()` as `match_inputs = (cost, count)`, like `outs`:
+    the pool must not hand their memory out again before the log's launches have read it, and a caller can read exactly what the
+    kernel read.  None: nothing is allocated, held, launched or captured."""
 
     def __init__(self, model, example_input, example_seg, grad_buffer, warmup=3, ignore_index=None, optimizer=None, assign="host",
-                 log=None, firing=None, seg_log=None):
+                 log=None, firing=None, seg_log=None, match_log=None):
         if assign not in ("host", "device"):
             raise ValueError(f"assign must be 'host' or 'device', got {assign!r}")
         if assign == "device" and not (example_input.is_cuda and example_seg.is_cuda):
             raise RuntimeError("GraphedHungarianStep(assign='device') needs CUDA tensors: the device assignment is a HIP kernel and "
                                "has no host fall-back")
-        self.assign, self.log, self.firing, self.seg_log = assign, log, firing, seg_log
+        self.assign, self.log, self.firing, self.seg_log, self.match_log = assign, log, firing, seg_log, match_log
         head = model.decode_head
         self.optimizer = optimizer
         if optimizer is not None:
@@ -366,6 +374,8 @@ class GraphedHungarianStep(_Captured):
             if seg_log.K != self.crit.num_classes:
                 raise ValueError(f"GraphedHungarianStep: a SegLog of {seg_log.K} classes on a head of {self.crit.num_classes}")
             seg_log.bind(L, B, Q, *masks.shape[-2:], device=dev)
+        if match_log is not None:
+            match_log.bind(L, B, Q, self.crit.num_classes, device=dev)
         del cls, masks
         self.tgt_labels = torch.full((L, B, Q), self.crit.num_classes, dtype=torch.int64, device=dev)
         self.row_class = torch.full((B, L * Q), -1, dtype=torch.int32, device=dev)
@@ -406,6 +416,8 @@ class GraphedHungarianStep(_Captured):
             self._record_firing()
             if self.seg_log is not None:          # the step's own prediction against its own labels: two launches, one row
                 self.seg_log.append(self.outs[0], self.outs[1], self.static_seg)
+            if self.match_log is not None:          # what the assignment did with the costs it was given: two launches, one row
+                self.match_log.append(self.match_inputs[0], self.outs[0], self.row_class)
 
         def whole():
             head()
@@ -424,6 +436,9 @@ class GraphedHungarianStep(_Captured):
         static tables (and the status word)"""
         with torch.no_grad():
             cost, count = self.crit.costs_all_classes(outs[0], outs[1], self.static_seg)
+            if self.match_log is not None:          # held like `outs`: the log's launches read the costs at the END of the step
+                cost = cost.contiguous()          # (the assignment makes this copy itself where it is one: no launch more)
+                self.match_inputs = (cost, count)
             if self.assign == "device":
                 self.crit.match_tables_device(cost, count, out=(self.tgt_labels, self.row_class, self.num_masks, self.status))
             else:

@@ -3,7 +3,7 @@ conv (dwconv.hip + the k x k lowering), attention (sdsa.hip, dcnv3.hip), layout 
 sums and fill), resize (upsample.hip, resize.hip: differentiable), predict (resize.hip: inference post-processing; slide.hip), pipeline
 (augment.hip), segeval (segmetric.hip, segdraw.hip), census (opcensus.hip), firingmap (firingmap.hip), maskloss (maskloss.hip, lsa.hip), trainstate
 (trainstate.hip: the training loop's state copy and log ring; firinglog.hip: the firing log's row; gradlog.hip: the gradient log's
-row), seglog (seglog.hip: the segmentation log's row), ema (ema.hip: the weight average's update and swap); `wcache` holds the cached bf16 conversions of the weights that the matrix-core products multiply by, `core`
+row), seglog (seglog.hip: the segmentation log's row), matchlog (matchlog.hip: the match log's row), ema (ema.hip: the weight average's update and swap); `wcache` holds the cached bf16 conversions of the weights that the matrix-core products multiply by, `core`
 the shared plumbing and `config` the process-global switches that are left (ops.cfg: runtime objects, semantics, debugging aids and
 the A/B switches the tests and bench.py set).  `ops.NAME` keeps working for every function and for every switch: reading or assigning
 `ops.STRICT`, `ops.GRAD_SINKS`, ... goes to `ops.cfg`; assigning an ALL-CAPS name that is no switch raises instead of creating a
@@ -11,14 +11,14 @@ module attribute nothing reads."""
 import sys
 import types
 
-from . import (attention, bn, census, config, conv, core, ema, firingmap, gemm, layout, maskloss, neuron, pipeline, predict, reduce, resize,
+from . import (attention, bn, census, config, conv, core, ema, firingmap, gemm, layout, maskloss, matchlog, neuron, pipeline, predict, reduce, resize,
                segeval, seglog, trainstate, wcache)
 from .config import cfg
 from . import glue_mode as glue  # noqa: F401  (the module: ops.glue.ROUTED / UNROUTED / HANDLERS)
 from .glue_mode import GlueMode, glue_mode  # noqa: F401  (ops.glue_mode(): the context manager)
 
 for _m in (core, layout, reduce, resize, predict, pipeline, segeval, census, firingmap, maskloss, neuron, attention, bn, wcache, gemm, conv,
-           trainstate, seglog, ema):
+           trainstate, seglog, matchlog, ema):
     for _k, _v in vars(_m).items():
         if not _k.startswith("__") and _k != "cfg" and not isinstance(_v, types.ModuleType):
             globals()[_k] = _v

@@ -739,6 +739,7 @@ class TrainLoop:
         self.firing = getattr(step, "firing", None)          # a firing.FiringLog the step appends a row to per replay
         self.grad_log = getattr(optimizer, "grad_log", None)          # a gradlog.GradLog `optimizer.step()` appends a row to
         self.seg_log = getattr(step, "seg_log", None)          # a seglog.SegLog the step appends a row to per replay
+        self.match_log = getattr(step, "match_log", None)          # a matchlog.MatchLog the step appends a row to per replay
         self.accum = getattr(optimizer, "accum", None)          # a train.GradAccum: FlatAdamW(accumulative_counts=k), k > 1
         own = getattr(step, "optimizer", None)
         if self.accum is not None and own is not optimizer:
@@ -751,8 +752,8 @@ class TrainLoop:
         self.eager_update = update == "caller" and (own is not None or hasattr(step, "red"))
         self.eager_append = self.log is not None and row == "caller"
         # the ring logs a LoggerHook reports, in the line's order: (log, the map from its row number to the iteration of that row)
-        self.logs = [(log, of) for log, of in ((self.firing, int), (self.grad_log, self.update_iteration), (self.seg_log, int))
-                     if log is not None]
+        self.logs = [(log, of) for log, of in ((self.firing, int), (self.grad_log, self.update_iteration), (self.seg_log, int),
+                                               (self.match_log, int)) if log is not None]
         if self.eager_append:
             self.log.bind({**step.log_terms, "grad_norm": optimizer.grad_norm, "clip_coef": optimizer.clip_coef})
         self.state = TrainState(step.model, optimizer, scheduler, augment, async_write=async_write)
@@ -852,7 +853,7 @@ class TrainLoop:
                     raise ValueError(f"TrainLoop: resumed at iteration {start}, inside a group of accumulative_counts={counts}: the "
                                      f"group's gradients are in no checkpoint")
                 self.accum.total, self.accum.count = self.max_iters, start
-            for log in (self.log, self.firing, self.grad_log, self.seg_log):          # (no ring is in a checkpoint: a resumed run starts them afresh)
+            for log in (self.log, self.firing, self.grad_log, self.seg_log, self.match_log):          # (no ring is in a checkpoint: a resumed run starts them afresh)
                 if log is not None:
                     log.rebase(start, counts if log is self.grad_log else 1)          # (the gradient log's rows count updates)
             self._call("before_run")
